@@ -8,10 +8,15 @@ prioritized replay (the reference's own metric: experiences accepted by save_his
 replay_buffer.py:121 / learners.py:94-109).  N > 1: one process per GPU, environments sharded by global env
 id, weights broadcast from rank 0 over RCCL; no data-path collective (scaling = weak).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, primes and warms up, times ONE region of exactly K steps and prints the headline.  --full adds what
+takes runs of its own: 5 timed regions of >= 1.2 s each (mean +- std), the search kernel's roofline (HIP-event clock and,
+N = 1, the rocprofv3 traffic passes), the split-f16 and policy-gain depth secondaries, the one-replay layout of N > 1 and
+the CPU baselines.  --dump-outputs DIR: rank 0's experience records of the last timed step, one DIR/<field>.npy per field.
 """
 import argparse
 import json
@@ -273,7 +278,7 @@ def live_traffic(workload, split_f16, chunk):
   for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
     d = tempfile.mkdtemp(prefix='mz_pmc_', dir='/tmp')
     cmd = ['rocprofv3', '--pmc', counter, '--output-format', 'csv', '-d', d, '--', sys.executable, os.path.abspath(__file__),
-           '--steps', str(chunk), '--warmup', str(chunk), '--no-cpu-baseline', '--min-seconds', '0.05', '--workload', workload,
+           '--steps', str(chunk), '--warmup', str(chunk), '--no-cpu-baseline', '--min-seconds', '0.05', '--workload', workload, '--full',
            '--chunk', str(chunk)] + (['--split-f16'] if split_f16 else [])
     try:
       subprocess.run(cmd, env=dict(os.environ, MZ_BENCH_CHILD='1', TMPDIR='/tmp'), cwd='/tmp', stdout=subprocess.DEVNULL,
@@ -422,6 +427,19 @@ def ingest_threads_for(world, one_replay_rank0=False):
   return int(max(1, min(4, cores // max(1, world) - 1)))
 
 
+def dump_outputs(dirname, rec, obs_u8):
+  """--dump-outputs: one move of experience records [B, rec_floats] -- what Actor.launch hands the replay for the last timed
+  step -- as one DIR/<field>.npy per field of engine.records_view: the float fields as they are (float32, root value and
+  error float64), the integer fields as float64 (exact)"""
+  from model_based_rl_amd.engine import records_view
+  os.makedirs(dirname, exist_ok=True)
+  for name, v in records_view(rec, O, A, obs_u8=obs_u8).items():
+    v = np.asarray(v)
+    if v.dtype not in (np.float32, np.float64):
+      v = v.astype(np.float64)
+    np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(v))
+
+
 def self_launch(args):
   """`python bench.py --gpus N` with N > 1 and no launcher: start `python -m torch.distributed.run --nproc-per-node N bench.py
   ...` as a CHILD process (this process has not touched the GPU -- and never replaces itself: os.exec* from a GPU process takes
@@ -464,10 +482,16 @@ def main():
                   help='moves between weight pulls (the path\'s one exchange: broadcast + repack)')
   ap.add_argument('--publish-period', type=float, default=0.02,
                   help='seconds between the weight publisher\'s store_weights calls on rank 0 (stand-in for Learner.send_weights)')
-  ap.add_argument('--min-seconds', type=float, default=1.2,
-                  help='the --steps block is repeated back to back until one timed region is at least this long')
-  ap.add_argument('--runs', type=int, default=5,
-                  help='timed regions (SURVEY.md s8d: mean +- std of 5 runs); `value` covers all of them')
+  ap.add_argument('--min-seconds', type=float, default=None,
+                  help='the --steps block is repeated back to back until one timed region is at least this long '
+                       '(default: 0 -- the region is exactly --steps steps; 1.2 with --full)')
+  ap.add_argument('--runs', type=int, default=None,
+                  help='timed regions; `value` covers all of them (default: 1; 5 with --full -- SURVEY.md s8d: mean +- std of 5 runs)')
+  ap.add_argument('--full', action='store_true',
+                  help='everything beyond the headline: 5 regions of >= 1.2 s, roofline (kernel clock, live traffic), the split-f16 '
+                       'and depth secondaries, the one-replay layout of N > 1, the CPU baselines')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='write rank 0\'s experience records of the last timed step as DIR/<field>.npy (float32 / float64)')
   ap.add_argument('--split-f16', action='store_true',
                   help='secondary line: the FCNetwork GEMMs as float16 high/low splits on the f16 matrix pipe '
                        '(mz_config.split_f16; float32-level accuracy, not bit-identical to the exact-f32 default)')
@@ -489,6 +513,13 @@ def main():
   ap.add_argument('--dump-records', default=None,
                   help='(tests) save this rank\'s experience records of the first moves after reset to <path>.rank<r>.npy')
   args = ap.parse_args()
+  selfplay = args.workload in WORKLOADS          # (the other workloads are lines of their own, unchanged by --full)
+  if args.runs is None:
+    args.runs = 5 if args.full or not selfplay else 1
+  if args.min_seconds is None:
+    args.min_seconds = 1.2 if args.full or not selfplay else 0.0
+  if args.dump_outputs and not selfplay:
+    ap.error('--dump-outputs covers the self-play workloads (%s)' % ', '.join(sorted(WORKLOADS)))
   if args.workload == 'breakout':
     import bench_torch             # secondary line: MuZeroNetwork through PyTorch-ROCm (BASELINE.json configs[4])
     return bench_torch.main(args)
@@ -509,7 +540,7 @@ def main():
   preflight = preflight_or_exit(world) if world > 1 else None      # every rank, before it touches its GPU (launcher-started runs)
   # roofline.traffic, live: the two PMC passes run as child processes before this process initialises the GPU
   measured_traffic = None
-  if world == 1 and 'RANK' not in os.environ and not args.no_live_traffic and not args.envs:
+  if args.full and world == 1 and 'RANK' not in os.environ and not args.no_live_traffic and not args.envs:
     measured_traffic = live_traffic(args.workload, args.split_f16, chunk)
   local_rank = int(os.environ.get('LOCAL_RANK', '0'))
   dist = None
@@ -714,14 +745,17 @@ def main():
     dist.all_gather(every, st, group=ctrl)
     shards = [[int(x[0]), int(x[1])] for x in every]
   assert eng.rec_floats == rec_floats, (eng.rec_floats, rec_floats)
-  # calibration: how many --steps blocks make a timed region of >= --min-seconds (same count on every rank)
-  torch.cuda.synchronize(device)
-  t0 = time.perf_counter()
-  actor.launch(whole(64))
-  torch.cuda.synchronize(device)
-  est = (time.perf_counter() - t0) / 64
-  repeats = max(1, int(np.ceil(args.min_seconds / max(1e-6, est * args.steps))))
-  repeats = min(repeats, max(1, 200000 // max(1, args.steps)))
+  # calibration: how many --steps blocks make a timed region of >= --min-seconds (same count on every rank); none without
+  # --min-seconds: the region is then exactly --steps steps
+  repeats = 1
+  if args.min_seconds > 0:
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    actor.launch(whole(64))
+    torch.cuda.synchronize(device)
+    est = (time.perf_counter() - t0) / 64
+    repeats = max(1, int(np.ceil(args.min_seconds / max(1e-6, est * args.steps))))
+    repeats = min(repeats, max(1, 200000 // max(1, args.steps)))
   if dist is not None:
     rt = torch.tensor([repeats], dtype=torch.int64, device=ctrl_dev)
     dist.all_reduce(rt, op=dist.ReduceOp.MAX, group=ctrl)
@@ -733,7 +767,16 @@ def main():
   sync_every = actor.config.weight_sync_frequency = max(chunk, min(sync_every, max(chunk, per_run // 2)))
   actor.launch(whole(max(args.warmup, 64 if not child and not args.envs else 0)))      # --warmup, at least 64 moves: the regions start in steady state
   pulls0 = actor.weight_pulls
+  last_records = []
+  if args.dump_outputs and rank == 0:
+    # the records of the newest chunk the timed regions hand over (one move of B environments: its last row is kept)
+    def keep_last(v):
+      last_records[:] = [v[-1].copy()]
+    actor.record_tap = keep_last
   runs = timed_regions(actor, layout, per_run, n_runs)
+  actor.record_tap = None
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last_records[0], ram)
   frames = sum(r[0] for r in runs)
   dt = sum(r[1] for r in runs)
   host_cores_busy = float(np.mean([r[2] for r in runs]))
@@ -763,13 +806,16 @@ def main():
   # descent, f32-MFMA dynamics + prediction, expand, backup, action/record).  Its duration is measured live with HIP
   # events on the stream it is launched on: start / stop events of every dispatch (mz_selfplay_steps_timed, the
   # timestamps rocprofv3's kernel trace reports) over a stretch of the same self-play loop, launched back to back.
-  pinned = actor._pipe.pinned
-  durs = []
-  for _ in range(4):
-    durs += eng.selfplay_steps_timed(chunk)
-    eng.selfplay_drain(pinned[0], chunk)
-    torch.cuda.synchronize(device)
-  search_us = 1e3 * float(np.mean(durs[chunk:]))       # (first chunk = warm-up)
+  # (--full: a stretch of its own, after the timed regions)
+  search_us = None
+  if args.full:
+    pinned = actor._pipe.pinned
+    durs = []
+    for _ in range(4):
+      durs += eng.selfplay_steps_timed(chunk)
+      eng.selfplay_drain(pinned[0], chunk)
+      torch.cuda.synchronize(device)
+    search_us = 1e3 * float(np.mean(durs[chunk:]))       # (first chunk = warm-up)
   # single-player shapes with their trees in LDS: the loop is ONE kernel -- every launch plays `chunk` whole moves
   # (root, simulations, end of move); mz_selfplay_steps_timed then reports every move as its share of its launch
   persistent = eng.selfplay_moves_per_launch() > 0
@@ -777,7 +823,7 @@ def main():
 
   # N > 1: the topology of `train --ranks N` (ONE replay on rank 0) as a secondary figure of the same line
   one_replay_secondary = None
-  if dist is not None and world > 1 and not one_replay and not args.no_one_replay_secondary:
+  if args.full and dist is not None and world > 1 and not one_replay and not args.no_one_replay_secondary:
     lay2 = Layout(True, 'b')
     actor.replay_buffer = lay2.replay
     # (the ONE replay starts empty: warm up until its window has been filled once, like the priming above)
@@ -800,8 +846,8 @@ def main():
     # algorithmic: SURVEY.md s8(d) per-simulation figure x sims x trees (+ the per-root figure where the root runs
     # inside the launch), x the moves one launch plays
     flops_per_launch = moves_per_launch * (SIMS * FLOP_PER_SIM + (FLOP_PER_ROOT if persistent else 0)) * B
-    launch_us = search_us * moves_per_launch
-    achieved = flops_per_launch / (launch_us * 1e-6) / 1e12
+    launch_us = search_us * moves_per_launch if search_us is not None else None
+    achieved = flops_per_launch / (launch_us * 1e-6) / 1e12 if search_us is not None else None
     traffic, traffic_source = None, None
     tfile = os.path.join(ROOT, 'profiles', 'traffic.json')
     if measured_traffic is not None:
@@ -877,22 +923,24 @@ def main():
                         'what': 'broadcast of the flat f32 weights (%d floats) per pull, MAX / SUM all-reduces of the timing, '
                                 'barriers' % flat.numel()} if dist is not None else None,
         'mcts_sims_per_s_per_gpu': env_steps * SIMS / dt / world,
-        'roofline': {'bound': 'mfma', 'kernel': 'k_search_fused', 'achieved': achieved,
-                     'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / PEAK_F32_MFMA_TFLOPS,
-                     'traffic': traffic, 'traffic_source': traffic_source,
-                     'traffic_per_move': None if traffic is None else traffic / moves_per_launch, 'us_per_launch': launch_us,
-                     'flop_per_launch': flops_per_launch, 'moves_per_launch': moves_per_launch,
-                     'us_per_move': search_us,
-                     'launch': ('one launch = %d whole moves of all trees: root (observation, initial inference, Dirichlet '
-                                'noise, first descent), %d simulations, end of move' % (moves_per_launch, SIMS)) if persistent
-                               else 'one launch = all simulations of one move of all trees + the end of the move (root: k_root)',
-                     'whole_path_frac': (env_steps / dt / world) * (SIMS * FLOP_PER_SIM + FLOP_PER_ROOT) / 1e12 /
-                                        PEAK_F32_MFMA_TFLOPS},
     }
+    if args.full:
+      out['roofline'] = {'bound': 'mfma', 'kernel': 'k_search_fused', 'achieved': achieved,
+                         'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / PEAK_F32_MFMA_TFLOPS,
+                         'traffic': traffic, 'traffic_source': traffic_source,
+                         'traffic_per_move': None if traffic is None else traffic / moves_per_launch, 'us_per_launch': launch_us,
+                         'flop_per_launch': flops_per_launch, 'moves_per_launch': moves_per_launch,
+                         'us_per_move': search_us,
+                         'launch': ('one launch = %d whole moves of all trees: root (observation, initial inference, Dirichlet '
+                                    'noise, first descent), %d simulations, end of move' % (moves_per_launch, SIMS)) if persistent
+                                   else 'one launch = all simulations of one move of all trees + the end of the move (root: k_root)',
+                         'whole_path_frac': (env_steps / dt / world) * (SIMS * FLOP_PER_SIM + FLOP_PER_ROOT) / 1e12 /
+                                            PEAK_F32_MFMA_TFLOPS}
     if one_replay_secondary is not None:
       out['one_replay_secondary'] = one_replay_secondary
     if args.split_f16:
       out['secondary_line'] = True
+    if args.split_f16 and args.full:
       # the split kernel executes 300 v_mfma_f32_16x16x32_f16 per wave and simulation (3 products per block, K padded to
       # 64 in the two fc1 stages): price it against the f16 matrix pipe, and show the stream that actually bounds it
       exec_flop = SIMS * B * (300 * 4 * 16384 // 16)
@@ -909,7 +957,7 @@ def main():
                                'an XCD\'s L2 delivers: that, not the matrix pipe (0.22 busy), bounds the stages (DESIGN.md s3.4)'},
           'note': 'achieved / peak = EXECUTED float16 MFMA FLOP against the dense f16 peak; the algorithmic float32 FLOP of the '
                   'same work are a third of that minus the K padding'}
-    elif world == 1 and O + 1 <= 64 and A <= 13 and not game and not child:
+    elif args.full and not args.split_f16 and world == 1 and O + 1 <= 64 and A <= 13 and not game and not child:
       # the opt-in split-f16 search kernel on the same workload, as a SECONDARY figure inside the same line (never `value`)
       try:
         with contextlib.redirect_stdout(sys.stderr):
@@ -919,14 +967,14 @@ def main():
     if args.policy_gain != 1.0:
       out['secondary_line'] = True
       out['config']['policy_gain'] = args.policy_gain
-    if world == 1 and not args.no_depth_sensitivity and WNAME.startswith('Lunar') and not args.envs and not child and not args.split_f16 \
+    if args.full and world == 1 and not args.no_depth_sensitivity and WNAME.startswith('Lunar') and not args.envs and not child and not args.split_f16 \
        and args.policy_gain == 1.0:
       try:
         with contextlib.redirect_stdout(sys.stderr):
           out['depth_sensitivity'] = depth_sensitivity(device, weights, chunk)
       except Exception as exc:          # the headline must not depend on it
         out['depth_sensitivity'] = {'error': str(exc)[:200]}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline({k: v.numpy() for k, v in net.state_dict().items()})
       out['cpu_baseline']['reference_shaped'] = cpu_baseline_reference_shaped()
     print(json.dumps(out), flush=True)

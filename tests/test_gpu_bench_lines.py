@@ -13,12 +13,16 @@ KEYS = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', '
         'dtype', 'data', 'config', 'roofline')
 
 
-def line_of(args):
+def run_line(args):
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args, capture_output=True, text=True, timeout=900, cwd=ROOT)
   assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
   rows = [l for l in out.stdout.splitlines() if l.startswith('{')]
   assert len(rows) == 1, out.stdout[-2000:]
-  line = json.loads(rows[0])
+  return json.loads(rows[0])
+
+
+def line_of(args):
+  line = run_line(args)
   for k in KEYS:
     assert k in line, k
   r = line['roofline']
@@ -30,7 +34,8 @@ def line_of(args):
 
 
 def test_tictactoe_line():
-  line = line_of(['--workload', 'tictactoe', '--envs', '256', '--steps', '16', '--warmup', '4', '--no-cpu-baseline', '--min-seconds', '0.2'])
+  line = line_of(['--workload', 'tictactoe', '--envs', '256', '--steps', '16', '--warmup', '4', '--no-cpu-baseline', '--min-seconds', '0.2',
+                   '--full'])
   assert 'TicTacToe on the device' in line['config']['environment'] and line['roofline']['bound'] == 'mfma'
   assert line['roofline']['moves_per_launch'] == 16         # whole moves inside the two-player launch
   assert 0.5 * 256 * line['timed_steps'] < line['value'] * line['timed_seconds'] < 1.5 * 256 * line['timed_steps']
@@ -51,7 +56,7 @@ def test_breakout_line():
 
 def test_pong_split_line():
   line = line_of(['--workload', 'pong', '--split-f16', '--envs', '256', '--steps', '16', '--warmup', '4', '--no-cpu-baseline',
-                  '--min-seconds', '0.2'])
+                  '--min-seconds', '0.2', '--full'])
   assert line.get('secondary_line') and line['roofline']['kernel'] == 'k_search_h2' and 'f16x2' in line['dtype']
 
 
@@ -85,7 +90,7 @@ def test_depth_sensitivity_block_and_policy_gain():
   w = {'policy_head.policy.weight': torch.ones(4, 8), 'policy_head.policy.bias': torch.ones(4), 'x': torch.ones(2)}
   s4 = sharpened(w, 4)
   assert float(s4['policy_head.policy.weight'][0, 0]) == 4.0 and float(s4['policy_head.policy.bias'][0]) == 4.0 and float(s4['x'][0]) == 1.0
-  line = line_of(['--steps', '32', '--warmup', '16', '--runs', '1', '--no-cpu-baseline', '--no-live-traffic', '--min-seconds', '0.2'])
+  line = line_of(['--steps', '32', '--warmup', '16', '--runs', '1', '--no-cpu-baseline', '--no-live-traffic', '--min-seconds', '0.2', '--full'])
   rows = line['depth_sensitivity']['rows']
   assert [r_['policy_gain'] for r_ in rows] == [1, 4, 24, 96]
   assert rows[2]['mean_leaf_depth'] > 3.5 and rows[3]['mean_leaf_depth'] > 5.5 and rows[0]['mean_leaf_depth'] < 3.0      # depth ~4 and ~6 beside the headline's 2.5
@@ -93,5 +98,38 @@ def test_depth_sensitivity_block_and_policy_gain():
     assert r_['env_steps_per_s'] > 1e6 and 0.2 < r_['frac'] < 1 and r_['cycles_per_sim_wave0']['t_select'] > 0
   assert rows[-1]['cycles_per_sim_wave0']['t_select'] > rows[0]['cycles_per_sim_wave0']['t_select']
   assert 'share_of_added' in rows[-1]
-  g = line_of(['--steps', '32', '--warmup', '16', '--runs', '1', '--no-cpu-baseline', '--no-live-traffic', '--min-seconds', '0.2', '--policy_gain', '4'])
+  g = line_of(['--steps', '32', '--warmup', '16', '--runs', '1', '--no-cpu-baseline', '--no-live-traffic', '--min-seconds', '0.2', '--policy_gain', '4',
+                '--full'])
   assert g.get('secondary_line') and g['config']['policy_gain'] == 4.0 and 'depth_sensitivity' not in g
+
+
+def test_plain_line_times_exactly_the_steps_and_dumps_the_last_one(tmp_path):
+  """A plain run (no --full): ONE timed region of exactly --steps steps, ms_per_step = its time / --steps, none of the figures that
+  take runs of their own; --dump-outputs writes the records of the last timed step, field by field, identical from run to run."""
+  import numpy as np
+  B, steps = 256, 48
+  lines, dumps = [], []
+  for i in range(2):
+    d = str(tmp_path / ('out%d' % i))
+    lines.append(run_line(['--envs', str(B), '--steps', str(steps), '--warmup', '16', '--dump-outputs', d]))
+    dumps.append(d)
+  for line in lines:
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+      assert k in line, k
+    assert line['timed_steps'] == steps and line['repeats'] == 1 and line['runs']['n'] == 1
+    assert abs(line['ms_per_step'] - 1e3 * line['timed_seconds'] / steps) < 1e-9 * line['ms_per_step']
+    assert 0.5 * B * steps < line['value'] * line['timed_seconds'] < 1.5 * B * steps
+    for k in ('roofline', 'cpu_baseline', 'depth_sensitivity', 'split_f16_secondary'):
+      assert k not in line, k
+  names = sorted(os.listdir(dumps[0]))
+  assert names == sorted(os.listdir(dumps[1]))
+  assert {'obs.npy', 'child_visits.npy', 'root_value.npy', 'reward.npy', 'action.npy', 'env_id.npy'} <= set(names)
+  total = 0
+  for n in names:
+    a, b = np.load(os.path.join(dumps[0], n)), np.load(os.path.join(dumps[1], n))
+    assert a.dtype in (np.float32, np.float64) and a.shape[0] == B, (n, a.dtype, a.shape)
+    assert np.array_equal(a, b), n
+    total += a.nbytes
+  assert total <= 64 << 20
+  assert np.array_equal(np.load(os.path.join(dumps[0], 'env_id.npy')), np.arange(B))
+  assert np.allclose(np.load(os.path.join(dumps[0], 'child_visits.npy')).sum(1), 1.0, atol=1e-5)
