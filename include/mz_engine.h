@@ -209,6 +209,31 @@ int mz_finalize(mz_engine *e, const double *temperature, const double *uniform, 
                 int32_t *action, double *child_visits, double *root_value, double *error,
                 int32_t *visit_counts, void *stream);
 
+/* Evaluator.play_game's move after the search (evaluate.py:305-327), B evaluation games in lock-step:
+ *   actions: from the root, while the node is expanded, Config.select_action (config.py:70-81) over its children -- the legal
+ *   actions in ascending order at the root (mcts.py:47-55), range(A) below it (mcts.py:97) -- and on to the chosen child,
+ *   at most max_actions = M times (--apply_mcts_actions).  temperature [dev][B] float64; uniform [dev][B][M] float64 in [0,1):
+ *   the draw of each step (temperature 0: the floor(u*n_ties)-th arg-max child, as mz_finalize), or NULL = device RNG keyed
+ *   (seed, env, move, step).  Outputs: actions [dev][B][M] int32 (-1 past the last), pred_rewards [dev][B][M] float32
+ *   (the chosen child's reward, evaluate.py:318; 0 for a child never expanded), n_actions [dev][B] int32, path_lengths
+ *   [dev][B][num_simulations] int32 or NULL: len(search_path) of every simulation of the last search (evaluate.py:306-307,
+ *   mcts.py:101-102; 0 past the simulations run).  Reads the trees mz_search (or the stepwise loop) left. */
+int mz_eval_walk(mz_engine *e, int max_actions, const double *temperature, const double *uniform, uint64_t move,
+                 int32_t *actions, float *pred_rewards, int32_t *n_actions, int32_t *path_lengths, void *stream);
+
+/* --only_prior / --only_value (evaluate.py:278-304) after mz_initial_inference + mz_root_prepare, no search: two launches,
+ * no host synchronisation between or after them.  mode 2 (only_value): BaseNetwork.recurrent_inference (networks.py:31-34) of every root's hidden
+ * state with every action (B*A rows, the arithmetic of mz_recurrent_inference), q = reward + discount * value (reward -
+ * discount * value with two players) in float32; the first strict maximum over the legal actions in ascending order;
+ * child_visits 1/|legal| on the legal actions.  mode 1 (only_prior): max((prior, action)) over the root's children -- the
+ * largest float64 prior after mz_root_prepare's noise, ties to the largest action -- and one recurrent inference for its
+ * reward; child_visits one-hot.  Outputs: action [dev][B] int32, pred_reward [dev][B] float32 (the chosen action's reward),
+ * child_visits [dev][B][A] float64 or NULL, row_reward / row_value [dev] or NULL: the rows' rewards and values ([B][A] in
+ * mode 2, [B] in mode 1).  The root value is Node.value() of a root never visited: 0.  The FIRST call allocates the rows' scratch
+ * (B*A rows) and so synchronises; later calls do not. */
+int mz_eval_lookahead(mz_engine *e, int mode, int32_t *action, float *pred_reward, double *child_visits, float *row_reward,
+                      float *row_value, void *stream);
+
 /* Raw tree dump (Node objects of mcts.py:28-45 in SoA form) to [host] arrays, synchronous.
  * Each per-node array is [B][NN]; minmax [B][2]; legal_mask [B] (bit a = root child a exists);
  * noise [B][A] (the Dirichlet draw last mixed in).  Any pointer may be NULL. */

@@ -187,3 +187,41 @@ def make_config(argv=None, **overrides):
   if not hasattr(cfg, 'obs_u8'):
     cfg.obs_u8 = obs_are_bytes(cfg)
   return cfg
+
+
+def get_evaluation_args(argv=None):
+  """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
+  engine; default min(num_games, 4096)) and --out (a JSON summary).  Checkpoints are saves_dir + net for every pair."""
+  p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
+  a = p.add_argument
+  a('--seed', type=int, default=None)
+  a('--num_games', type=int, default=1)
+  a('--saves_dir', nargs='+', type=str, default=[''])
+  a('--nets', nargs='+', type=str, default=[''])
+  a('--num_simulations', nargs='+', type=int, default=[None])
+  a('--temperatures', nargs='+', type=float, default=[0])
+  a('--only_prior', nargs='+', type=int, default=[0])
+  a('--only_value', nargs='+', type=int, default=[0])
+  a('--use_exploration_noise', nargs='+', type=int, default=[0])
+  a('--apply_mcts_actions', nargs='+', type=int, default=[1])
+  a('--render', action='store_true')
+  a('--sleep', type=float, default=0)
+  a('--human_opp', type=int, choices=[-1, 1], default=None)
+  a('--random_opp', type=int, choices=[-1, 1], default=None)
+  a('--plot_summary', action='store_true')
+  a('--include_bounds', action='store_true')
+  a('--include_policy', action='store_true')
+  a('--detailed_label', action='store_true')
+  a('--smooth', type=int, default=None)
+  a('--save_gif_as', type=str, default='')
+  a('--save_mcts', action='store_true')
+  a('--save_mcts_after_step', type=int, default=0)
+  a('--parallel', action='store_true', help='accepted and ignored: the games are already played in lock-step batches')
+  a('--use_gpu', action='store_true', help='accepted and implied: there is no CPU path')
+  a('--verbose', action='store_true')
+  a('--batch', type=int, default=None, help='games played in lock-step on one engine (default: min(num_games, 4096))')
+  a('--out', type=str, default=None, help='write the summary of every configuration to this JSON file')
+  args = p.parse_args(argv)
+  if args.batch is None:
+    args.batch = min(args.num_games, 4096)
+  return args

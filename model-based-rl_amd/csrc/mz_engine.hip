@@ -30,6 +30,7 @@
 #include "mz_fused_h2.hip.h"
 #include "mz_learner.hip.h"
 #include "mz_fcl.hip.h"
+#include "mz_eval.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are launched
 #include "mz_kernels.inc"
 MZ_ALL_FUSED(extern)
@@ -137,6 +138,7 @@ struct mz_engine {
   double *draw_uniform = nullptr;   // [B] host-given uniforms of a game environment's parity run (mz_selfplay_set_draws)
   bool draws_noise = false, draws_set = false;
   std::vector<float> obs_norm_host;
+  float *eval_rows = nullptr;       // mz_eval_lookahead's scratch [B*A][50 + A + 2] (hidden, logits, reward, value), first use
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -1637,6 +1639,54 @@ int mz_finalize(mz_engine *e, const double *temperature, const double *uniform, 
                      e->tv, temperature, uniform, e->cfg.seed, move_counter, (const unsigned long long *)nullptr,
                      e->cfg.env_id_offset, action, child_visits, root_value, error, visit_counts);
   HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+int mz_eval_walk(mz_engine *e, int max_actions, const double *temperature, const double *uniform, uint64_t move,
+                 int32_t *actions, float *pred_rewards, int32_t *n_actions, int32_t *path_lengths, void *stream) {
+  if (!e || !temperature || !actions || !pred_rewards || !n_actions) return fail("mz_eval_walk: null argument");
+  MZ_ENTER(e);
+  if (!e->root_ready) return fail("mz_eval_walk: no tree (call mz_root_prepare and mz_search first)");
+  if (max_actions < 1) return fail("mz_eval_walk: max_actions must be >= 1");
+  const size_t lds = (size_t)(e->sims + 1) * sizeof(int32_t);
+  if (lds > 48 * 1024) return fail("mz_eval_walk: num_simulations = %d exceeds the walk's LDS map", e->sims);
+  hipLaunchKernelGGL(k_eval_walk, dim3(e->B), dim3(64), lds, (hipStream_t)stream, e->tv, e->sims_done + 1, max_actions,
+                     temperature, uniform, e->cfg.seed, move, e->cfg.env_id_offset, actions, pred_rewards, n_actions,
+                     path_lengths);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+int mz_eval_lookahead(mz_engine *e, int mode, int32_t *action, float *pred_reward, double *child_visits,
+                      float *row_reward, float *row_value, void *stream) {
+  if (!e || !action || !pred_reward) return fail("mz_eval_lookahead: null argument");
+  if (mode != 1 && mode != 2) return fail("mz_eval_lookahead: mode must be 1 (only_prior) or 2 (only_value), got %d", mode);
+  MZ_ENTER(e);
+  if (!e->weights_set) return fail("mz_eval_lookahead: weights not set (call mz_set_weights)");
+  if (!e->root_ready) return fail("mz_eval_lookahead: no root (call mz_initial_inference and mz_root_prepare first)");
+  const size_t rows_max = (size_t)e->B * e->A;
+  // scratch of the rows, allocated on the first call (which therefore synchronises: hipMalloc + hipMemset; header)
+  if (!e->eval_rows && dmalloc(e, &e->eval_rows, rows_max * (MZ_H + e->A + 2))) return -1;
+  float *hout = e->eval_rows, *logits = hout + rows_max * MZ_H, *rew = logits + rows_max * e->A, *val = rew + rows_max;
+  hipStream_t s = (hipStream_t)stream;
+  const int threads = 128, tblocks = (e->B + threads - 1) / threads;
+  if (mode == 2) {      // --only_value: every (tree, action) row, then the choice
+    const int n = e->B * e->A;
+    float *rr = row_reward ? row_reward : rew, *rv = row_value ? row_value : val;
+    NET_LAUNCH(k_eval_rows, (n + MZ_ROWS - 1) / MZ_ROWS, s, e->nv, e->tv, e->A, (const int32_t *)nullptr, n, hout, rr, rv, logits);
+    HIPCHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_eval_choose_value, dim3(tblocks), dim3(threads), 0, s, e->tv, (const float *)rr, (const float *)rv,
+                       (float)e->cfg.discount, action, pred_reward, child_visits);
+    HIPCHECK(hipGetLastError());
+  } else {              // --only_prior: the choice, then one row per tree for its reward
+    hipLaunchKernelGGL(k_eval_choose_prior, dim3(tblocks), dim3(threads), 0, s, e->tv, action, child_visits);
+    HIPCHECK(hipGetLastError());
+    NET_LAUNCH(k_eval_rows, (e->B + MZ_ROWS - 1) / MZ_ROWS, s, e->nv, e->tv, 1, (const int32_t *)action, e->B, hout,
+               pred_reward, row_value ? row_value : val, logits);
+    HIPCHECK(hipGetLastError());
+    if (row_reward)
+      HIPCHECK(hipMemcpyAsync(row_reward, pred_reward, (size_t)e->B * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
   return 0;
 }
 

@@ -11,6 +11,7 @@
 #define MZ_RNG_REWARD 2u
 #define MZ_RNG_DIRICHLET 3u
 #define MZ_RNG_ACTION 4u
+#define MZ_RNG_EVAL 5u       // evaluation walk (mz_eval.hip.h): one uniform per applied action, counter (env, move, step)
 
 struct mz_u4 { uint32_t x, y, z, w; };
 

@@ -338,6 +338,46 @@ class Engine(object):
                                     _ptr(vc), self.stream), 'mz_finalize')
     return dict(action=action, child_visits=cv, root_value=rv, error=err, visit_counts=vc)
 
+  # ---- evaluation (evaluate.py:278-327; csrc/mz_eval.hip.h)
+  def eval_walk(self, max_actions, temperature, uniform=None, move=0, path_lengths=True):
+    """mz_eval_walk: after a search, the up to max_actions actions Evaluator.play_game applies (evaluate.py:314-326) and
+    their predicted rewards, and len(search_path) of every simulation (evaluate.py:306-307).  temperature: scalar or [B];
+    uniform [B, max_actions] float64 (the draws of select_action) or None = device RNG keyed (seed, env, move, step).
+    Returns dict(actions [B, M] int32 (-1 past n_actions), pred_rewards [B, M] float32, n_actions [B] int32,
+    path_lengths [B, sims] int32 or None), device tensors."""
+    M = int(max_actions)
+    if torch.is_tensor(temperature):
+      t = self._dev(temperature.to(self.device, torch.float64).expand(self.B), torch.float64)
+    else:
+      t = self._dev(torch.as_tensor(np.broadcast_to(np.asarray(temperature, np.float64), (self.B,)).copy()), torch.float64)
+    u = self._dev(None if uniform is None else np.asarray(uniform, np.float64).reshape(self.B, M), torch.float64)
+    out = dict(actions=torch.empty(self.B, M, dtype=torch.int32, device=self.device),
+               pred_rewards=torch.empty(self.B, M, dtype=torch.float32, device=self.device),
+               n_actions=torch.empty(self.B, dtype=torch.int32, device=self.device),
+               path_lengths=torch.empty(self.B, self.sims, dtype=torch.int32, device=self.device) if path_lengths else None)
+    _abi.check(self.lib.mz_eval_walk(self._h, M, _ptr(t), _ptr(u), int(move), _ptr(out['actions']), _ptr(out['pred_rewards']),
+                                     _ptr(out['n_actions']), _ptr(out['path_lengths']), self.stream), 'mz_eval_walk')
+    return out
+
+  EVAL_MODES = {'only_prior': 1, 'only_value': 2}
+
+  def eval_lookahead(self, mode, rows=False):
+    """mz_eval_lookahead: --only_prior / --only_value (evaluate.py:278-304) on the prepared roots, no search.  Returns
+    dict(action [B] int32, pred_reward [B] float32, child_visits [B, A] float64) and with rows=True the rows' reward and value
+    (row_reward / row_value: [B, A] for only_value, [B] for only_prior), device tensors."""
+    m = self.EVAL_MODES[mode] if isinstance(mode, str) else int(mode)
+    shape = (self.B, self.A) if m == 2 else (self.B,)
+    out = dict(action=torch.empty(self.B, dtype=torch.int32, device=self.device),
+               pred_reward=torch.empty(self.B, dtype=torch.float32, device=self.device),
+               child_visits=torch.empty(self.B, self.A, dtype=torch.float64, device=self.device))
+    if rows:
+      out['row_reward'] = torch.empty(shape, dtype=torch.float32, device=self.device)
+      out['row_value'] = torch.empty(shape, dtype=torch.float32, device=self.device)
+    _abi.check(self.lib.mz_eval_lookahead(self._h, m, _ptr(out['action']), _ptr(out['pred_reward']), _ptr(out['child_visits']),
+                                          _ptr(out.get('row_reward')), _ptr(out.get('row_value')), self.stream),
+               'mz_eval_lookahead')
+    return out
+
   def export_tree(self, hidden=False):
     B, NN, A = self.B, self.NN, self.A
     d = dict(N=np.zeros((B, NN), np.int32), W=np.zeros((B, NN)), P=np.zeros((B, NN)),

@@ -1,0 +1,332 @@
+"""Evaluation of saved networks: the reference's evaluate.py (Evaluator, get_label, state_generator, run, the summary), with
+the games played in lock-step on the GPU instead of one at a time.
+
+Per move and live game: initial inference, root expansion (+ Dirichlet noise with --use_exploration_noise), then either
+the search and the walk that picks the actions to apply (mz_search + mz_eval_walk) or the one-step lookahead of
+--only_prior / --only_value (mz_eval_lookahead); the host environments apply the actions exactly as evaluate.py:331-376 does.
+Game i of a run uses seed + i (evaluate.py:476-479): its host draws (the random opponent, the Dirichlet noise) come from
+np.random.RandomState(seed_i + 3) -- the numpy stream set_all_seeds(seed_i) leaves (utils.py:136-144) -- and its device draws
+(select_action's uniforms) from the counter-based RNG keyed by seed_i, so a game's record does not depend on the batch it
+was played in.
+
+FCNetwork checkpoints on host environments (envs.get_environment) only; the interactive tools of the reference (rendering,
+GIFs, plots, human play, MCTS PNG dumps) are refused.  One departure from the reference's output: its '[Game done]' line after
+every game (evaluate.py:376-379) is printed only with --verbose -- thousands of games are played per configuration here, and
+the summary block carries the same numbers."""
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from .config import get_evaluation_args
+from .engine import Engine, flatten_weights
+from .envs import get_environment
+
+MAX_BATCH = 4096
+
+REFUSED = (
+    ('render', 'rendering is an interactive tool and is not part of this evaluator (no display on the GPU machines).'),
+    ('save_gif_as', 'saving GIFs needs rendered frames, which this evaluator does not produce.'),
+    ('save_mcts', 'MCTS PNG dumps (pydot) are an interactive tool and are not part of this evaluator.'),
+    ('human_opp', 'human play is an interactive tool and is not part of this evaluator; use --random_opp.'),
+    ('plot_summary', 'plots are an interactive tool and are not part of this evaluator; use --out for a JSON summary.'),
+)
+
+
+def refuse_unsupported(args_or_config):
+  """one sentence per interactive flag the evaluator leaves out (NotImplementedError)"""
+  for name, why in REFUSED:
+    if getattr(args_or_config, name, None):
+      raise NotImplementedError('--%s: %s' % (name, why))
+
+
+class SummaryTools(object):
+
+  def summary(self, games):
+    """the six (mean, std) pairs print_summary prints (evaluate.py:79-104), as a dict"""
+    lengths = [game.step for game in games]
+    returns = [sum(game.history.rewards) for game in games]
+    pred_returns = [sum(game.pred_rewards) for game in games]
+    pred_values = [np.mean(game.pred_values) for game in games]
+    root_values = [np.mean(game.history.root_values) for game in games]
+    # (the reference's quirk, kept: max() of the per-move lists of search depths is the LEXICOGRAPHIC maximum list, and its
+    # mean is taken -- not the deepest simulation)
+    search_depths = [np.mean(max(game.search_depths)) for game in games]
+    out = {}
+    for key, vals in (('length', lengths), ('return', returns), ('pred_return', pred_returns), ('pred_value', pred_values),
+                      ('mcts_value', root_values), ('search_depth', search_depths)):
+      out[key] = [float(np.mean(vals)), float(np.std(vals))]
+    return out
+
+  def print_summary(self, games):
+    s = self.summary(games)
+    print("\n\033[92mEvaluation finished! - label: ({})\033[0m".format(self.config.label))
+    print("Average length: {:.1f}({:.1f})".format(*s['length']))
+    print("Average return: {:.1f}({:.1f})".format(*s['return']))
+    print("Average predicted return: {:.1f}({:.1f})".format(*s['pred_return']))
+    print("Average predicted value: {:.1f}({:.1f})".format(*s['pred_value']))
+    print("Average mcts value: {:.1f}({:.1f})".format(*s['mcts_value']))
+    print("Average search depth: {:.1f}({:.1f})\n".format(*s['search_depth']))
+    return s
+
+
+class Evaluator(SummaryTools):
+
+  def __init__(self, state, device=None):
+    self.config = state['config']
+    self.state = state
+    if getattr(self.config, 'architecture', 'FCNetwork') != 'FCNetwork':
+      raise NotImplementedError('the evaluator runs FCNetwork checkpoints only (%s has no batched evaluation path here)'
+                                % self.config.architecture)
+    refuse_unsupported(self.config)
+    if not torch.cuda.is_available():
+      raise RuntimeError('the evaluator needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
+    self.device = torch.device(device if device is not None else 'cuda')
+    self.batch = int(getattr(self.config, 'batch', None) or MAX_BATCH)
+    self.weights = None
+    self.host_seconds = 0.0
+    if getattr(self.config, 'norm_obs', False):
+      self.obs_min = np.array(self.config.obs_range[::2], dtype=np.float32)
+      self.obs_max = np.array(self.config.obs_range[1::2], dtype=np.float32)
+      self.obs_range = self.obs_max - self.obs_min
+
+  def load_network(self):
+    self.weights = flatten_weights(self.state['weights'])
+    self.state = None
+
+  def play_game(self, environment, seed=None, draws=None):
+    """one game (evaluate.py:242-385) on a one-tree engine; seed: the game's seed (run() passes it)"""
+    return self.play_games(1, None if seed is None else [seed], environments=[environment],
+                           draws=None if draws is None else [draws])[0]
+
+  def play_games(self, num_games, seeds=None, environments=None, draws=None):
+    """num_games games, up to self.batch of them in lock-step per engine.  seeds: one per game, consecutive (seed + i); None
+    draws a base seed.  draws (parity runs): per game a dict of recorded draws -- 'walk' [moves][M] uniforms, 'noise' [moves][A]
+    Dirichlet draws at the legal positions, 'opp' the random opponent's choices (indices into the legal actions)."""
+    assert self.weights is not None, '.load_network() needs to be called before playing.'
+    if seeds is None:
+      base = int(np.random.randint(0, 2 ** 30))
+      seeds = list(range(base, base + num_games))
+    seeds = [int(s) for s in seeds]
+    if len(seeds) != num_games or any(s != seeds[0] + i for i, s in enumerate(seeds)):
+      raise ValueError('play_games takes consecutive seeds, one per game (evaluate.py:476-479)')
+    games = []
+    for lo in range(0, num_games, self.batch):
+      hi = min(num_games, lo + self.batch)
+      envs = environments[lo:hi] if environments is not None else [get_environment(self.config) for _ in range(lo, hi)]
+      games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
+    return games
+
+  def _play_batch(self, envs, seeds, draws):
+    cfg = self.config
+    B, A = len(envs), int(cfg.action_space)
+    O = int(np.prod(cfg.obs_space))
+    only_prior, only_value = bool(getattr(cfg, 'only_prior', 0)), bool(getattr(cfg, 'only_value', 0))
+    noise_on = bool(getattr(cfg, 'use_exploration_noise', 0))
+    two = bool(cfg.two_players)
+    random_opp = getattr(cfg, 'random_opp', None)
+    M = int(getattr(cfg, 'apply_mcts_actions', 1))
+    if M <= 0:        # (the reference's loop then runs until an unexpanded node: at most num_simulations + 1 actions)
+      M = int(cfg.num_simulations) + 1
+    T = float(getattr(cfg, 'temperature', 0) or 0)
+    # the device RNG's key: (engine seed 0, env id = the game's seed, move, step)
+    eng = Engine.from_config(cfg, B, device=self.device, seed=0, env_id_offset=seeds[0])
+    eng.set_weights(self.weights)
+    rngs = [np.random.RandomState(s + 3) for s in seeds]
+    opp_pos = [0] * B
+    games = []
+    for env, s in zip(envs, seeds):
+      env.seed(s)
+      g = cfg.new_game(env)
+      g.pred_values, g.pred_rewards, g.search_depths = [], [], []
+      games.append(g)
+    t_host = 0.0
+    move = 0
+    while True:
+      th = time.perf_counter()
+      live = [i for i in range(B) if not games[i].terminal]
+      if not live:
+        break
+      obs = np.zeros((B, O), np.float32)
+      legal = np.ones((B, A), np.uint8)
+      legal_actions = [None] * B
+      to_play = np.ones(B, np.int8)
+      noise = np.zeros((B, A)) if noise_on else None
+      uniform = np.zeros((B, M)) if draws is not None else None
+      for i in live:
+        g = games[i]
+        ob = np.float32(g.get_observation(-1))
+        if getattr(cfg, 'norm_obs', False):
+          ob = (ob - self.obs_min) / self.obs_range
+        obs[i] = np.asarray(ob, np.float32).reshape(-1)
+        env = g.environment
+        la = env.legal_actions() if hasattr(env, 'legal_actions') else np.arange(A)
+        legal_actions[i] = la
+        legal[i] = 0
+        legal[i, np.asarray(la, np.int64)] = 1
+        to_play[i] = g.to_play
+        if noise_on:      # Node.add_exploration_noise (mcts.py:57-61): one Dirichlet draw over the legal actions
+          nz = draws[i]['noise'][move] if draws is not None else rngs[i].dirichlet([cfg.root_dirichlet_alpha] * len(la))
+          nz = np.asarray(nz, np.float64)
+          noise[i, np.asarray(la, np.int64)] = nz[np.asarray(la, np.int64)] if draws is not None else nz
+        if draws is not None and not (only_prior or only_value):
+          w = np.asarray(draws[i]['walk'][move], np.float64)
+          uniform[i, :len(w)] = w
+      t_host += time.perf_counter() - th
+      eng.initial_inference(obs)
+      eng.root_prepare(to_play, legal, noise, device_rng=False)
+      if only_prior or only_value:
+        out = eng.eval_lookahead('only_prior' if only_prior else 'only_value')
+        actions, preds = out['action'].reshape(B, 1), out['pred_reward'].reshape(B, 1)
+        n_act = torch.ones(B, dtype=torch.int32)
+        child_visits = out['child_visits']
+        root_values = torch.zeros(B, dtype=torch.float64)
+        depths = None
+      else:
+        eng.search()
+        w = eng.eval_walk(M, T, uniform, move=move)
+        fin = eng.finalize(0.0, np.full(B, 0.5), move=move)
+        actions, preds, n_act, depths = w['actions'], w['pred_rewards'], w['n_actions'], w['path_lengths']
+        child_visits, root_values = fin['child_visits'], fin['root_value']
+      pred_value = eng.root_outputs()[0].cpu().numpy()
+      actions, preds, n_act = actions.cpu().numpy(), preds.cpu().numpy(), n_act.cpu().numpy()
+      child_visits, root_values = child_visits.cpu().numpy(), root_values.cpu().numpy()
+      depths = None if depths is None else depths.cpu().numpy()
+      th = time.perf_counter()
+      for i in live:
+        g = games[i]
+        g.search_depths.append([0] if only_prior else [1] if only_value else [int(x) for x in depths[i]])
+        g.pred_values.append(float(pred_value[i]))
+        g.store_search_statistics([float(x) for x in child_visits[i]], float(root_values[i]))
+        for j in range(int(n_act[i])):      # evaluate.py:331-374
+          action, reward = int(actions[i, j]), float(preds[i, j])
+          g.pred_rewards.append(reward)
+          if two:
+            if g.to_play == random_opp:
+              if draws is not None:
+                action = int(legal_actions[i][draws[i]['opp'][opp_pos[i]]])
+                opp_pos[i] += 1
+              else:
+                action = int(rngs[i].choice(legal_actions[i]))
+            to_play_i = g.to_play
+          g.apply(action)
+          if g.terminal or g.step >= cfg.max_steps:
+            g.environment.was_real_done = True
+            g.terminal = True
+            if two and to_play_i == random_opp:
+              g.history.rewards[-1] *= -1
+            break
+        if getattr(cfg, 'verbose', False) and g.terminal:
+          msg = "\033[92m[Game done]\033[0m --> "
+          msg += "length: {:.1f}, return: {:.1f}, pred return: {:.1f}, pred value: {:.1f}, mcts value: {:.1f}"
+          print(msg.format(g.step, np.sum(g.history.rewards), np.sum(g.pred_rewards), np.mean(g.pred_values),
+                           np.mean(g.history.root_values)))
+      t_host += time.perf_counter() - th
+      move += 1
+    eng.close()
+    self.host_seconds += t_host
+    for g in games:
+      g.history.observations = []
+      g.environment = None
+    return games
+
+
+def get_label(state, detailed=False, path_idx=None):
+  label_parts = ['net:{}'.format(state['training_step'])]
+  if detailed:
+    if path_idx is not None:
+      label_parts.append('path:{}'.format(path_idx))
+    if state['config'].only_value:
+      label_parts.append('only value')
+    elif state['config'].only_prior:
+      label_parts.append('only prior')
+    else:
+      label_parts.append('sims:{}'.format(state['config'].num_simulations))
+      if state['config'].apply_mcts_actions > 1:
+        label_parts.append('mcts-actions:{}'.format(state['config'].apply_mcts_actions))
+      if state['config'].temperature:
+        label_parts.append('temp:{}'.format(state['config'].temperature))
+      if state['config'].use_exploration_noise:
+        label_parts.append('with noise')
+  return ', '.join(label_parts)
+
+
+def state_generator(args):
+  """evaluate.py:406-439: one state per (checkpoint, temperature, simulations, only_prior, only_value, noise, mcts actions),
+  only_prior together with only_value excluded"""
+  for path_idx, saves_dir in enumerate(args.saves_dir):
+    for net in args.nets:
+      meta_state = torch.load(saves_dir + net, map_location=torch.device('cpu'), weights_only=False)
+      for temperature in args.temperatures:
+        for num_simulations in args.num_simulations:
+          for only_prior in args.only_prior:
+            for only_value in args.only_value:
+              for use_exploration_noise in args.use_exploration_noise:
+                for apply_mcts_actions in args.apply_mcts_actions:
+                  if not (only_prior and only_value):
+                    state = copy.deepcopy(meta_state)
+                    c = state['config']
+                    c.saves_dir = saves_dir
+                    if num_simulations is not None:
+                      c.num_simulations = num_simulations
+                    c.temperature = temperature
+                    c.only_value = only_value
+                    c.only_prior = only_prior
+                    c.use_exploration_noise = use_exploration_noise
+                    c.apply_mcts_actions = apply_mcts_actions
+                    c.render = args.render
+                    c.save_mcts = args.save_mcts
+                    c.save_mcts_after_step = args.save_mcts_after_step
+                    c.save_gif_as = args.save_gif_as
+                    c.sleep = args.sleep
+                    c.random_opp = args.random_opp
+                    c.human_opp = args.human_opp
+                    c.label = get_label(state, args.detailed_label, path_idx)
+                    c.use_gpu = True
+                    c.verbose = args.verbose
+                    c.batch = args.batch
+                    yield state
+
+
+def run(evaluator, seed=None):
+  """evaluate.py:441-452: one game with its own seed"""
+  environment = get_environment(evaluator.config)
+  return evaluator.play_game(environment, seed=seed)
+
+
+def main(argv=None):
+  args = get_evaluation_args(argv)
+  refuse_unsupported(args)
+  evaluators = [Evaluator(state) for state in state_generator(args)]
+  print("\n\033[92mStarting a {} episode evaluation of {} configurations\033[0m...".format(args.num_games, len(evaluators)))
+  seeds = list(range(args.seed, args.num_games + args.seed)) if args.seed is not None else None
+  results = []
+  for evaluator in evaluators:
+    print("\n\033[92mEvaluating... - label: ({}) on {}\033[0m".format(evaluator.config.label, evaluator.device))
+    evaluator.load_network()
+    t0 = time.perf_counter()
+    games = evaluator.play_games(args.num_games, seeds)
+    wall = time.perf_counter() - t0
+    s = evaluator.print_summary(games)
+    s['label'] = evaluator.config.label
+    s['num_games'] = len(games)
+    if evaluator.config.two_players and args.random_opp is not None:
+      returns = np.array([sum(g.history.rewards) for g in games])
+      s['wins'], s['draws'], s['losses'] = int((returns > 0).sum()), int((returns == 0).sum()), int((returns < 0).sum())
+      print("Against a random opponent (the agent moves {}): wins {} draws {} losses {}\n".format(
+          'second' if args.random_opp == 1 else 'first', s['wins'], s['draws'], s['losses']))
+    s['games_per_s'] = len(games) / wall
+    s['host_share'] = evaluator.host_seconds / wall
+    results.append(s)
+  if args.out:
+    with open(args.out, 'w') as f:
+      json.dump({'num_games': args.num_games, 'seed': args.seed, 'configurations': results}, f, indent=1)
+  return results
+
+
+if __name__ == '__main__':
+  main(sys.argv[1:])
