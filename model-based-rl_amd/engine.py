@@ -41,6 +41,32 @@ def flatten_weights(weights):
   return torch.from_numpy(out)
 
 
+def weight_shapes(obs_dim, action_space, value_outputs, reward_outputs):
+  """{WEIGHT_ORDER key: shape} of an FCNetwork state_dict (networks.py:122-140) with these output sizes"""
+  O, A, F = int(obs_dim), int(action_space), 512
+  layers = {'representation_head.fc1': (F, O), 'representation_head.out': (H, F), 'value_head.fc1': (F, H),
+            'value_head.value': (int(value_outputs), F), 'policy_head.fc1': (F, H), 'policy_head.policy': (A, F),
+            'reward_head.fc1': (F, H + A), 'reward_head.reward': (int(reward_outputs), F), 'transition_head.fc1': (F, H + A),
+            'transition_head.out': (H, F)}
+  out = {}
+  for k, s in layers.items():
+    out[k + '.weight'], out[k + '.bias'] = s, s[:1]
+  out['LN.weight'] = out['LN.bias'] = (H,)
+  return out
+
+
+def check_weight_shapes(weights, obs_dim, action_space, value_outputs, reward_outputs):
+  """ValueError naming the first key of a state_dict that is missing or whose shape is not the one these sizes need: the
+  flat vector's length alone cannot tell a (15, 5) support pair from (5, 15), nor (32, 30) from (31, 31)."""
+  for k, want in weight_shapes(obs_dim, action_space, value_outputs, reward_outputs).items():
+    if k not in weights:
+      raise ValueError('weights: %s is missing' % k)
+    got = tuple(weights[k].shape)
+    if got != want:
+      raise ValueError('weights: %s has shape %s, expected %s (obs_dim %d, action_space %d, value outputs %d, reward outputs %d)'
+                       % (k, got, want, obs_dim, action_space, value_outputs, reward_outputs))
+
+
 def weights_scale_ok(flat_host, obs_dim, action_space, value_outputs, reward_outputs):
   """mz_weights_scale_ok (include/mz_engine.h): does this weight set admit the search kernel's clamp-ReLU scale?  Host
   arithmetic on a host copy of the flat weights (engine.WEIGHT_ORDER); no GPU."""
@@ -177,8 +203,9 @@ class Engine(object):
     is decided on the host copy, mz_weights_scale_ok).  Weights on the DEVICE (the buffer a broadcast filled): the same
     when the caller passes `scale_ok` (the learner rank's mz_weights_scale_ok on its host copy; the tensor must stay valid
     until the stream has passed the call), else mz_set_weights, which reads the decision back and so waits for the stream.
-    sync: force mz_set_weights."""
+    sync: force mz_set_weights.  A state_dict's tensors must have this engine's shapes; a flat vector, its length."""
     if isinstance(weights, dict):
+      check_weight_shapes(weights, self.O, self.A, *self._outputs)
       weights = flatten_weights(weights)
     if not torch.is_tensor(weights):
       weights = torch.from_numpy(np.ascontiguousarray(weights, np.float32))

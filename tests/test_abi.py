@@ -214,3 +214,42 @@ def test_headline_kernel_keeps_its_register_budget():
   assert len(head) == 1, sorted(usage)
   assert head[0]['VGPRs'] == 256 and head[0]['AGPRs'] == 256
   assert head[0]['ScratchSize'] <= 48, head[0]
+
+
+def host_scale_exponent(sd, A):
+  """k of the host's decision (mz_weights_scale_ok): the clamp-ReLU bound of the four fc1 layers times 1.02 is f 2^k"""
+  import numpy as np
+  w = {k: np.asarray(v, np.float64) for k, v in sd.items()}
+  hb = 7.01 * np.abs(w['LN.weight']) + np.abs(w['LN.bias'])
+  bound = 0.0
+  for head, onehot in (('reward_head', A), ('transition_head', A), ('value_head', 0), ('policy_head', 0)):
+    W, b = np.abs(w[head + '.fc1.weight']), np.abs(w[head + '.fc1.bias'])
+    s = (W[:, :50] * hb).sum(1) + (W[:, 50:].max(1) if onehot else 0.0) + b
+    bound = max(bound, float(s.max()))
+  return int(np.frexp(bound * 1.02)[1]) if bound * 1.02 > 1.0 else 0
+
+
+@pytest.mark.parametrize('vs,rs', [((-7, 7), (-2, 2)), ((-2, 2), (-7, 7))], ids=['Sv15_Sr5', 'Sv5_Sr15'])
+def test_weights_scale_ok_reads_each_output_head_at_its_own_size(vs, rs):
+  """the consuming-layer bound of mz_weights_scale_ok covers every real row of the value and the reward output layer at
+  its OWN support size: the largest weight planted in the last real row of the larger head, then of the smaller one,
+  decides -- refused when it is above the limit both the host and k_relu_scale apply (w2max >= 2^(100-k)), accepted well
+  inside it.  (A bound that took the other head's size would read only part of the larger head.)"""
+  import types
+  import numpy as np
+  import torch
+  from model_based_rl_amd.engine import flatten_weights, weights_scale_ok
+  from model_based_rl_amd.networks import FCNetwork
+  O, A = 8, 6
+  cfg = types.SimpleNamespace(value_support=vs, reward_support=rs, no_support=False, no_target_transform=False)
+  torch.manual_seed(1)
+  sd = {k: v.detach().clone() for k, v in FCNetwork(O, A, torch.device('cpu'), cfg).state_dict().items()}
+  sv, sr = vs[1] - vs[0] + 1, rs[1] - rs[0] + 1
+  assert weights_scale_ok(flatten_weights(sd), O, A, sv, sr) == 1
+  k = host_scale_exponent({n: v.numpy() for n, v in sd.items()}, A)
+  heads = sorted([('value_head.value.weight', sv), ('reward_head.reward.weight', sr)], key=lambda h: -h[1])
+  for key, rows in heads:                                 # the larger head first, then the smaller
+    for val, want in ((2.0 ** (102 - k), 0), (2.0 ** (90 - k), 1)):
+      g = {n: v.clone() for n, v in sd.items()}
+      g[key][rows - 1, 511] = -val
+      assert weights_scale_ok(flatten_weights(g), O, A, sv, sr) == want, (key, rows, val)
