@@ -344,6 +344,13 @@ size_t mz_fcl_num_params(mz_fcl *c);
 int mz_fcl_bind(mz_fcl *c, float *params, float *exp_avg, float *exp_avg_sq, float *steps, int nsteps, const float *lr,
                 void *stream);
 int mz_fcl_repack(mz_fcl *c, void *stream);
+/* mz_fcl_set_optimizer: which optimiser the steps of this handle run (utils.py:73-83).  kind 0 = Adam / AdamW (the default: a
+ *   handle that never calls this steps as before; the steps' beta1, beta2 and adamw apply), 1 = SGD (torch.optim.SGD: dampening
+ *   0, no Nesterov), 2 = RMSprop (torch.optim.RMSprop: not centred, smoothing constant alpha).  For kinds 1 and 2 the steps' eps,
+ *   weight_decay and clip_grad apply and beta1, beta2, adamw are ignored; mz_fcl_bind's exp_avg holds the momentum buffer (not read
+ *   or written with momentum 0), exp_avg_sq RMSprop's square_avg (SGD: not touched); the step counters advance as for Adam.
+ *   Refuses an unknown kind, momentum < 0 and alpha outside [0, 1) (mz_last_error). */
+int mz_fcl_set_optimizer(mz_fcl *c, int kind, double momentum, double alpha);
 int mz_fcl_step(mz_fcl *c, const float *obs, const void *actions, int actions_are_i32, const float *target_rewards, const float *target_values,
                 const float *target_policies, const void *is_weights, int weights_are_f64, double beta1, double beta2, double eps,
                 double weight_decay, double clip_grad, int adamw, int no_update, float *new_errors, double *loss_sums, void *stream);

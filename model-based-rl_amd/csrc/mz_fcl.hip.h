@@ -1065,10 +1065,25 @@ struct FclJob {
   int M, N, Mp, Np, tm, ng, npos, na, hd, pad_;        // Mp, Np: feature counts of the two tapes (their row-chunk strides / 16); tile: 16 na rows from row 16 na tm, columns from 16 ni ng (ni: the kernel's)
 };
 
+// optimiser kinds (FclOpt::kind, mz_fcl_set_optimizer); every kernel that updates weights has one instantiation per kind (template
+// argument OK), so that Adam's register allocation stays what it is.  SGD / RMSprop with a momentum buffer: OK = kind | FCL_MOM (the
+// buffer's loads and stores are straight-line code; without momentum there are none)
+#define FCL_ADAM 0
+#define FCL_SGD 1
+#define FCL_RMSPROP 2
+#define FCL_MOM 4
+__host__ __device__ constexpr bool fcl_rms(int OK) { return (OK & 3) == FCL_RMSPROP; }
+__host__ __device__ constexpr bool fcl_has_m(int OK) { return OK == FCL_ADAM || (OK & FCL_MOM) != 0; }      // exp_avg / momentum_buffer
+__host__ __device__ constexpr bool fcl_has_v(int OK) { return OK == FCL_ADAM || fcl_rms(OK); }              // exp_avg_sq / square_avg
+
 struct FclOpt {
   double beta1, beta2, eps, wd;
   float clip;
   int adamw, no_update;
+  int kind;                 // FCL_ADAM / FCL_SGD / FCL_RMSPROP (SGD, RMSprop: beta1, beta2, adamw unused)
+  // SGD / RMSprop: their hyper-parameters as floats, as torch's foreach kernels take them: momentum (0: no buffer), RMSprop's alpha
+  // and 1 - alpha (rounded from double), eps, weight decay
+  float mom, alpha, alpha_c, eps_f, wd_f;
 };
 
 struct FclDw {              // what a weight-gradient workgroup does with its strip
@@ -1105,6 +1120,41 @@ __device__ __forceinline__ void fcl_adam_elem(const FclDw &a, size_t i, float g,
   if (pb >= 0) a.pk[pb] = p;
 }
 
+// SGD / RMSprop on one weight as torch.optim.SGD / RMSprop step it (utils.py:73-83: dampening 0, no Nesterov, not centred; RMSprop eps
+// 0.01), in float32 and in the order of torch's foreach kernels: weight decay into the gradient; RMSprop: square_avg <- alpha square_avg +
+// (1 - alpha) g^2, direction g / (sqrt(square_avg) + eps); momentum: buf <- mom buf + direction (a zero buffer gives torch's first step,
+// buf = direction); p - lr * direction.  ea / es: momentum buffer / square_avg in and out; returns the new weight
+template <int OK>
+__device__ __forceinline__ float fcl_sgd_rms(const FclOpt &o, float g, float p, float &ea, float &es, float lr) {
+  if (o.wd_f != 0.f) g = g + o.wd_f * p;
+  float d = g;
+  if constexpr (fcl_rms(OK)) {
+    es = es * o.alpha + o.alpha_c * (g * g);
+    d = g / (sqrtf(es) + o.eps_f);
+  }
+  if constexpr (fcl_has_m(OK)) {
+    ea = ea * o.mom + d;
+    d = ea;
+  }
+  return p - lr * d;
+}
+
+// the kind's update of one weight of the fused paths: new weight (and the state the kind keeps) written back, the packed copies too
+template <int OK>
+__device__ __forceinline__ void fcl_opt_elem(const FclDw &a, size_t i, float g, float p, float ea, float es, int pa, int pb, float bc1,
+                                             float bc2, double lr) {
+  if constexpr (OK == FCL_ADAM) {
+    fcl_adam_elem(a, i, g, p, ea, es, pa, pb, bc1, bc2, lr);
+  } else {
+    p = fcl_sgd_rms<OK>(a.o, g, p, ea, es, (float)lr);
+    if constexpr (fcl_has_m(OK)) a.m[i] = ea;
+    if constexpr (fcl_has_v(OK)) a.vv[i] = es;
+    a.P[i] = p;
+    if (pa >= 0) a.pk[pa] = p;
+    if (pb >= 0) a.pk[pb] = p;
+  }
+}
+
 // the two bias corrections of this step (steps[0] has been advanced by k_fcl_heads), by one lane, into LDS
 __device__ __forceinline__ void fcl_bias_corr(const FclDw &a, float *dst) {
   const double step = (double)a.steps[0];
@@ -1125,13 +1175,14 @@ __device__ __forceinline__ void fcl_bias_corr(const FclDw &a, float *dst) {
 // ONEBUF: ONE register set of NF units per wave -- where NF x NW covers the job's units (the chain layers' jobs of the step's last launch:
 // 80 units, NF = 10) every tape load of the job is requested before its first MFMA: one round trip to HBM (the chain's deltas were written
 // by other XCDs in the launch before) instead of three
-template <int NW, int NA, int NI, int NF, bool FUSABLE, bool WT = false, bool ONEBUF = false>
+// OK: the optimiser kind of the fused update (FCL_ADAM, FCL_SGD / FCL_RMSPROP [| FCL_MOM])
+template <int NW, int NA, int NI, int NF, bool FUSABLE, bool WT = false, bool ONEBUF = false, int OK = FCL_ADAM>
 __device__ __forceinline__ void fcl_dw_job(const FclJob *jp, int slab, const FclDw &a, float *sh, const unsigned *wait_flag = nullptr,
                                            unsigned wait_for = 0u, unsigned *err = nullptr) {
   constexpr int Q = FCL_DW_Q(NA, NI);
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, g4 = lane >> 4, m16 = lane & 15;
   const FclJob j = *jp;
-  if constexpr (!WT) { if (a.fuse && tid == NW * 64 - 1) fcl_bias_corr(a, sh + NW * Q * 64); }     // (a lane of the last wave: the first waves carry the remainder units)
+  if constexpr (!WT && OK == FCL_ADAM) { if (a.fuse && tid == NW * 64 - 1) fcl_bias_corr(a, sh + NW * Q * 64); }     // (a lane of the last wave: the first waves carry the remainder units)
   const int nch = a.R >> 4, per = (nch + a.S - 1) / a.S, c_lo = slab * per, c_hi = c_lo + per < nch ? c_lo + per : nch;
   const int nchs = c_hi > c_lo ? c_hi - c_lo : 0, U = j.npos * nchs;
   // tapes: [row chunk][feature][16 rows] -- 16 features x 16 rows of chunk c are one contiguous KiB
@@ -1182,7 +1233,12 @@ __device__ __forceinline__ void fcl_dw_job(const FclJob *jp, int slab, const Fcl
           ok_ = j.ng == 0 && 16 * j.tm + m < j.M;
         }
         pre_p[k] = 0.f; pre_m[k] = 0.f; pre_v[k] = 0.f; pre_a[k] = -1; pre_b[k] = -1;
-        if (ok_) { pre_p[k] = a.P[ix]; pre_m[k] = a.m[ix]; pre_v[k] = a.vv[ix]; pre_a[k] = a.posA[ix]; pre_b[k] = a.posB[ix]; }
+        if (ok_) {
+          pre_p[k] = a.P[ix];
+          if constexpr (fcl_has_m(OK)) pre_m[k] = a.m[ix];      // (SGD / RMSprop without momentum: no buffer)
+          if constexpr (fcl_has_v(OK)) pre_v[k] = a.vv[ix];     // (SGD: no second moment)
+          pre_a[k] = a.posA[ix]; pre_b[k] = a.posB[ix];
+        }
       }
     }
   }
@@ -1225,7 +1281,7 @@ __device__ __forceinline__ void fcl_dw_job(const FclJob *jp, int slab, const Fcl
     // (the optimiser's operands above are in flight; the step counter was written through by chain workgroup 0 before its first signal)
     if (tid == 0) fcl_wait_flag<64>(wait_flag, wait_for, err);
     fcl_bar();
-    if (a.fuse && tid == NW * 64 - 1) {
+    if (OK == FCL_ADAM && a.fuse && tid == NW * 64 - 1) {
       const double step = (double)fcl_load_wt(a.steps);
       sh[NW * Q * 64] = (float)(1.0 - pow(a.o.beta1, step));
       sh[NW * Q * 64 + 1] = (float)(1.0 - pow(a.o.beta2, step));
@@ -1308,7 +1364,7 @@ __device__ __forceinline__ void fcl_dw_job(const FclJob *jp, int slab, const Fcl
       size_t idx;
       if (element(tid + k * T, g, idx)) {
         a.grad[idx] = g;
-        fcl_adam_elem(a, idx, g, pre_p[k], pre_m[k], pre_v[k], pre_a[k], pre_b[k], bc1, bc2, lr);
+        fcl_opt_elem<OK>(a, idx, g, pre_p[k], pre_m[k], pre_v[k], pre_a[k], pre_b[k], bc1, bc2, lr);
       }
     }
   }
@@ -1384,7 +1440,7 @@ __device__ __forceinline__ void fcl_loss_block(const float *lossb, const void *w
 // (a chain workgroup that has finished its forward pass does not idle the ~13 us until its last position's units have finished: three of a
 // sample group's four chain workgroups run THOSE units themselves -- value, policy, reward of position K: no CU waits 17 us for them with
 // nothing to do -- and the fourth takes one of the other positions' units, which are handed out through a counter in position order)
-template <int KP>
+template <int KP, int OK = FCL_ADAM>
 __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fb(FclView v, int nchain, const FclJob *jobs, FclDw a) {
   extern __shared__ __attribute__((aligned(16))) float fcl_smem[];
   __shared__ int s_unit;
@@ -1394,7 +1450,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fb(FclView v, int nchain, c
   if (!chain && (int)blockIdx.x - nchain >= units) {
     const FclJob *jp = jobs + ((int)blockIdx.x - nchain - units);
     const int hd = jp->hd;
-    fcl_dw_job<FCL_NW, 1, 4, 4, true, true>(jp, 0, a, fcl_smem, v.flags + (size_t)2 * G * K1 + 32 * (1 + hd), (unsigned)(G * (hd == 2 ? v.K : K1)), v.err);      // (a 128-byte line per head's counter)
+    fcl_dw_job<FCL_NW, 1, 4, 4, true, true, false, OK>(jp, 0, a, fcl_smem, v.flags + (size_t)2 * G * K1 + 32 * (1 + hd), (unsigned)(G * (hd == 2 ? v.K : K1)), v.err);      // (a 128-byte line per head's counter)
     if (v.prof && threadIdx.x == 0) atomicMax(v.prof + 64, (unsigned long long)__builtin_amdgcn_s_memrealtime());      // (development: the last job's end)
     return;
   }
@@ -1444,7 +1500,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fb(FclView v, int nchain, c
 // when it is done; that workgroup zeroes it again) stores `seq` into the update's pinned host word, system scope: every read of the
 // update's staging slot and every store of its results lies before it.  The loop polls that word instead of recording an event behind
 // every update: an event record between two updates cost 3.4 us of the GPU's timeline)
-template <int NFJ, int MINW>
+template <int NFJ, int MINW, int OK = FCL_ADAM>
 __global__ __launch_bounds__(FCL_THREADS, MINW) void k_fcl_dwa(const FclJob *jobs, int njobs, FclDw a, int tail, const float *lnpart, int nwg,
                                                                   size_t ln_w, const float *lossb, const void *w, int w_f64, int bs, int K1,
                                                                   double *loss_acc, int nheads, unsigned *flags, int nflags,
@@ -1454,23 +1510,26 @@ __global__ __launch_bounds__(FCL_THREADS, MINW) void k_fcl_dwa(const FclJob *job
   if (b == 0 && flags)
     for (int i = threadIdx.x; i < nflags; i += FCL_THREADS) flags[i] = 0u;
   if (b < nheads) {
-    fcl_dw_job<FCL_NW, 1, 4, 4, true>(jobs + b, 0, a, fcl_smem);
+    fcl_dw_job<FCL_NW, 1, 4, 4, true, false, false, OK>(jobs + b, 0, a, fcl_smem);
   } else if (b < njobs) {
-    fcl_dw_job<FCL_NW, 1, 2, NFJ, true, false, (NFJ > 4)>(jobs + b, 0, a, fcl_smem);
+    fcl_dw_job<FCL_NW, 1, 2, NFJ, true, false, (NFJ > 4), OK>(jobs + b, 0, a, fcl_smem);
   } else if (tail && b == njobs) {
     const int k = threadIdx.x;
-    if (k == 2 * MZ_H) fcl_bias_corr(a, fcl_smem);
+    if constexpr (OK == FCL_ADAM) { if (k == 2 * MZ_H) fcl_bias_corr(a, fcl_smem); }
     float g = 0.f, pv = 0.f, ea = 0.f, es = 0.f;
     const float lr_pre = a.fuse ? *a.lr_p : 0.f;
     int pa = -1, pb = -1;
     const size_t i = ln_w + (size_t)(k < 2 * MZ_H ? k : 0);
     if (k < 2 * MZ_H) {
-      pv = a.P[i]; ea = a.m[i]; es = a.vv[i]; pa = a.posA[i]; pb = a.posB[i];
+      pv = a.P[i];
+      if constexpr (fcl_has_m(OK)) ea = a.m[i];
+      if constexpr (fcl_has_v(OK)) es = a.vv[i];
+      pa = a.posA[i]; pb = a.posB[i];
       g = fcl_ln_grad(k, lnpart, nwg);
       a.grad[i] = g;
     }
     __syncthreads();
-    if (k < 2 * MZ_H && a.fuse) fcl_adam_elem(a, i, g, pv, ea, es, pa, pb, fcl_smem[0], fcl_smem[1], (double)lr_pre);
+    if (k < 2 * MZ_H && a.fuse) fcl_opt_elem<OK>(a, i, g, pv, ea, es, pa, pb, fcl_smem[0], fcl_smem[1], (double)lr_pre);
   } else if (tail) {
     fcl_loss_block(lossb, w, w_f64, bs, K1, loss_acc, (double *)fcl_smem);
   }
@@ -1524,12 +1583,13 @@ __global__ __launch_bounds__(256, 2) void k_fcl_dwt(const FclJob *jobs, int njob
 // The backward chain (batch / 4 workgroups: 64 of 256 CUs at batch 256) and the heads' weight-gradient jobs -- they read only
 // what k_fcl_heads wrote -- in ONE launch: the jobs (16 x 64 strips) run on the CUs the chain leaves idle (r05 tried the same
 // overlap with a side stream and two events: the cross-stream waits cost what it saved)
+template <int OK = FCL_ADAM>
 __global__ __launch_bounds__(FCL_THREADS) void k_fcl_bwd_dw(FclView v, int nchain, const FclJob *jobs, FclDw a) {
   extern __shared__ __attribute__((aligned(16))) float fcl_smem[];
   if (blockIdx.x == 0 && v.flags)          // (the fused forward launch's arrival counters, for the next step)
     for (int i = threadIdx.x; i < v.nflags; i += FCL_THREADS) v.flags[i] = 0u;
   if ((int)blockIdx.x < nchain) fcl_chain_bwd4_body<1>(v, blockIdx.x, fcl_smem);
-  else fcl_dw_job<FCL_NW, 1, 4, 4, true>(jobs + ((int)blockIdx.x - nchain), 0, a, fcl_smem);
+  else fcl_dw_job<FCL_NW, 1, 4, 4, true, false, false, OK>(jobs + ((int)blockIdx.x - nchain), 0, a, fcl_smem);
 }
 
 // ------------------------------------------------------------------------------------------------ gradient, optimiser (unfused paths)
@@ -1573,16 +1633,17 @@ __global__ __launch_bounds__(256) void k_fcl_grad(const float *part, int nslab, 
   if (threadIdx.x == 0) bsq[blockIdx.x] = sh[0];
 }
 
-// clip_grad_norm_ (learners.py:217-218), Adam / AdamW with torch's fused-kernel arithmetic (utils.py:73-83: eps 1.5e-4),
-// new weights -> flat vector + the packed copies; one more block (the last) adds the three weighted loss means up
-// (learners.py:205-207,228-230).  steps[0] has been advanced by k_fcl_heads.
+// clip_grad_norm_ (learners.py:217-218), Adam / AdamW with torch's fused-kernel arithmetic (utils.py:73-83: eps 1.5e-4) -- or
+// SGD / RMSprop (OK, fcl_sgd_rms) -- new weights -> flat vector + the packed copies; one more block (the last) adds the three weighted
+// loss means up (learners.py:205-207,228-230).  steps[0] has been advanced by k_fcl_heads.
+template <int OK = FCL_ADAM>
 __global__ __launch_bounds__(256) void k_fcl_adam(float *P, float *pk, const int32_t *posA, const int32_t *posB, float *grad,
                                                   const float *part, int nslab, const float *lnpart, int nwg, size_t ln_w,
                                                   const float *bsq, int nblk, float *m, float *vv, const float *steps,
                                                   const float *lr_p, FclOpt o, size_t nflat, const float *lossb, const void *w,
                                                   int w_f64, int bs, int K1, double *loss_acc) {
   __shared__ float sh[256];
-  __shared__ float shc[4];
+  __shared__ float shc[2];
   if ((int)blockIdx.x == nblk) {
     __shared__ double shd3[3 * 256];
     fcl_loss_block(lossb, w, w_f64, bs, K1, loss_acc, shd3);
@@ -1595,7 +1656,7 @@ __global__ __launch_bounds__(256) void k_fcl_adam(float *P, float *pk, const int
   if (o.clip > 0.f)
     for (int b = threadIdx.x; b < nblk; b += 256) s += bsq[b];
   sh[threadIdx.x] = s;
-  if (threadIdx.x == 0) {
+  if (OK == FCL_ADAM && threadIdx.x == 0) {
     const double step = (double)steps[0];
     shc[0] = (float)(1.0 - pow(o.beta1, step));
     shc[1] = (float)(1.0 - pow(o.beta2, step));
@@ -1608,7 +1669,18 @@ __global__ __launch_bounds__(256) void k_fcl_adam(float *P, float *pk, const int
   const float norm = sqrtf(sh[0]);
   float coef = 1.f;
   if (o.clip > 0.f) coef = fminf(o.clip / (norm + 1e-6f), 1.f);
-  if (i < nflat) {
+  if (OK != FCL_ADAM && i < nflat) {
+    float ea = 0.f, es = 0.f;
+    if constexpr (fcl_has_m(OK)) ea = m[i];
+    if constexpr (fcl_has_v(OK)) es = vv[i];
+    const float p = fcl_sgd_rms<OK>(o, grad[i] * coef, P[i], ea, es, *lr_p);
+    if constexpr (fcl_has_m(OK)) m[i] = ea;
+    if constexpr (fcl_has_v(OK)) vv[i] = es;
+    P[i] = p;
+    if (posA[i] >= 0) pk[posA[i]] = p;
+    if (posB[i] >= 0) pk[posB[i]] = p;
+  }
+  if (OK == FCL_ADAM && i < nflat) {
     // (the hyper-parameters are doubles in torch's fused kernel and the moments' updates are evaluated in double there:
     // 1 - 0.999 as a float is 4.7e-5 off)
     const double lr = (double)*lr_p;

@@ -27,6 +27,9 @@ struct mz_fcl {
   FclJob *jobs = nullptr;
   float *P = nullptr, *m = nullptr, *v = nullptr, *steps = nullptr;
   const float *lr = nullptr;
+  // mz_fcl_set_optimizer: FCL_ADAM (the default) / FCL_SGD / FCL_RMSPROP, momentum and RMSprop's alpha
+  int opt_kind = FCL_ADAM;
+  double opt_mom = 0.0, opt_alpha = 0.0;
   // mz_fcl_update: FCL_SLOTS pinned staging slots for a batch, its device copy, the new errors' way back
   char *stage_h[FCL_SLOTS] = {}, *stage_d = nullptr;
   size_t stage_bytes = 0, soff[6] = {0, 0, 0, 0, 0, 0};
@@ -48,7 +51,7 @@ struct mz_fcl {
   char *stage_hd[FCL_SLOTS] = {};          // device addresses of stage_h / err_h (hipHostGetDevicePointer)
   float *err_hd[FCL_SLOTS] = {};
   hipGraphExec_t run_graph[FCL_SLOTS] = {};
-  double run_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double run_key[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   double run_stats[6] = {0, 0, 0, 0, 0, 0};      // host seconds in: waiting for a slot, refresh, sampling, launching, the whole call; updates
   hipStream_t run_cap = nullptr;
   size_t soff_lr = 0;
@@ -273,9 +276,13 @@ int mz_fcl_create(int batch, int unroll_steps, int obs_dim, int action_space, in
   c->lds_bwd_dw = c->lds_bytes > (size_t)FCL_DW_LDS(FCL_NW, 1, 4) ? c->lds_bytes : (size_t)FCL_DW_LDS(FCL_NW, 1, 4);
   if (hipFuncSetAttribute((const void *)k_fcl_dwt, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_DW_LDS(4, 4, 4)) != hipSuccess)
     return bail(fail("mz_fcl_create: %d bytes of LDS per workgroup refused", FCL_DW_LDS(4, 4, 4)));
-  if (c->lds_bwd_dw > 64 * 1024 &&
-      hipFuncSetAttribute((const void *)k_fcl_bwd_dw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd_dw) != hipSuccess)
-    return bail(fail("mz_fcl_create: %zu bytes of LDS per workgroup refused", c->lds_bwd_dw));
+  if (c->lds_bwd_dw > 64 * 1024) {
+    const void *fn[5] = {(const void *)k_fcl_bwd_dw<FCL_ADAM>, (const void *)k_fcl_bwd_dw<FCL_SGD>, (const void *)k_fcl_bwd_dw<FCL_SGD | FCL_MOM>,
+                         (const void *)k_fcl_bwd_dw<FCL_RMSPROP>, (const void *)k_fcl_bwd_dw<FCL_RMSPROP | FCL_MOM>};
+    for (int i = 0; i < 5; ++i)
+      if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd_dw) != hipSuccess)
+        return bail(fail("mz_fcl_create: %zu bytes of LDS per workgroup refused", c->lds_bwd_dw));
+  }
   if (hipFuncSetAttribute((const void *)k_fcl_heads, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess)
     return bail(fail("mz_fcl_create: %d bytes of LDS per workgroup refused", FCL_LDS_HEADS * 4));
   {
@@ -299,11 +306,13 @@ int mz_fcl_create(int batch, int unroll_steps, int obs_dim, int action_space, in
         hipHostGetDevicePointer((void **)&c->done_hd, c->done_h, 0) != hipSuccess || fcl_alloc(c, &c->done_ctr, (size_t)16))
       return bail(fail("mz_fcl_create: pinned completion words refused"));
     memset(c->done_h, 0, FCL_SLOTS * 64);
-    if (hipFuncSetAttribute((const void *)k_fcl_fwd<56>, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_fcl_fwd<64>, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_fcl_fb<56>, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_fcl_fb<64>, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess)
-      return bail(fail("mz_fcl_create: %d bytes of LDS per workgroup refused", FCL_LDS_HEADS * 4));
+    const void *fn[12] = {(const void *)k_fcl_fwd<56>, (const void *)k_fcl_fwd<64>, (const void *)k_fcl_fb<56, FCL_ADAM>, (const void *)k_fcl_fb<64, FCL_ADAM>,
+                          (const void *)k_fcl_fb<56, FCL_SGD>, (const void *)k_fcl_fb<64, FCL_SGD>, (const void *)k_fcl_fb<56, FCL_SGD | FCL_MOM>,
+                          (const void *)k_fcl_fb<64, FCL_SGD | FCL_MOM>, (const void *)k_fcl_fb<56, FCL_RMSPROP>, (const void *)k_fcl_fb<64, FCL_RMSPROP>,
+                          (const void *)k_fcl_fb<56, FCL_RMSPROP | FCL_MOM>, (const void *)k_fcl_fb<64, FCL_RMSPROP | FCL_MOM>};
+    for (int i = 0; i < 12; ++i)
+      if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess)
+        return bail(fail("mz_fcl_create: %d bytes of LDS per workgroup refused", FCL_LDS_HEADS * 4));
   }
   {
     const size_t sz[6] = {(size_t)batch * obs_dim * 4, (size_t)batch * unroll_steps * 8, (size_t)batch * K1 * 4, (size_t)batch * K1 * 4,
@@ -369,6 +378,19 @@ int mz_fcl_slots(mz_fcl *c) { return c ? c->nslots : -1; }
   MzDeviceGuard fcl_guard_;                                                                 \
   if (fcl_guard_.enter((c)->device)) return fail("hipSetDevice(%d) failed", (c)->device)
 
+int mz_fcl_set_optimizer(mz_fcl *c, int kind, double momentum, double alpha) {
+  if (!c) return fail("mz_fcl_set_optimizer: null argument");
+  if (kind != FCL_ADAM && kind != FCL_SGD && kind != FCL_RMSPROP)
+    return fail("mz_fcl_set_optimizer: unknown optimiser kind %d (0 Adam / AdamW, 1 SGD, 2 RMSprop)", kind);
+  if (!(momentum >= 0.0) || !std::isfinite(momentum)) return fail("mz_fcl_set_optimizer: momentum %g must be finite and >= 0", momentum);
+  if (!(alpha >= 0.0 && alpha < 1.0)) return fail("mz_fcl_set_optimizer: alpha %g outside [0, 1)", alpha);
+  c->opt_kind = kind;
+  c->opt_mom = kind == FCL_ADAM ? 0.0 : momentum;
+  c->opt_alpha = kind == FCL_RMSPROP ? alpha : 0.0;
+  fcl_drop_run_graphs(c);
+  return 0;
+}
+
 int mz_fcl_repack(mz_fcl *c, void *stream) {
   if (!c || !c->P) return fail("mz_fcl_repack: no parameters bound");
   FCL_ENTER(c);
@@ -420,6 +442,8 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
   FclOpt o;
   o.beta1 = beta1; o.beta2 = beta2; o.eps = eps; o.wd = weight_decay; o.clip = (float)clip_grad;
   o.adamw = adamw ? 1 : 0; o.no_update = no_update ? 1 : 0;
+  o.kind = c->opt_kind; o.mom = (float)c->opt_mom; o.alpha = (float)c->opt_alpha; o.alpha_c = (float)(1.0 - c->opt_alpha);
+  o.eps_f = (float)eps; o.wd_f = (float)weight_decay;
   FclDw a;
   a.tapes = c->tapes; a.tape_bytes = (unsigned)(c->tape_floats * 4); a.R = c->bs; a.S = c->S; a.part = c->part; a.nflat = c->nflat; a.grad = c->grad;
   a.fuse = (c->S == 1 && !clip && !no_update) ? 1 : 0;
@@ -432,14 +456,17 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
   v.flags = c->flags; v.nflags = 2 * (c->bs / 16) * K1 + 192; v.err = c->wedge_hd;
   const int nchain_jobs = c->njobs - c->njobs_heads;
   const int lds_dwa = FCL_DW_LDS(FCL_NW, 1, 4) > 3 * 256 * 8 ? FCL_DW_LDS(FCL_NW, 1, 4) : 3 * 256 * 8;
+  // the launches, with the optimiser kind's instantiation of every kernel that updates weights
+  auto launches = [&](auto kind) {
+  constexpr int OK = decltype(kind)::value;
   if (c->fuse_fb) {
     // batch <= 256: TWO launches -- forward chain, heads and backward chain (k_fcl_fb); every weight-gradient job with Adam in its
     // workgroup, the LayerNorm parameters and the loss sums (k_fcl_dwa)
     const int units = (c->bs / 16) * (3 * c->K - 1);      // (position K's units run in the chain workgroups)
     const int inl = c->fb_jobs ? c->njobs_heads : 0;        // the heads' jobs inside k_fcl_fb (MZ_FCL_FB_JOBS=0: in the last launch, A/B)
-    if (v.tr.ks1 == 56) hipLaunchKernelGGL(k_fcl_fb<56>, dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
-    else hipLaunchKernelGGL(k_fcl_fb<64>, dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
-    hipLaunchKernelGGL((k_fcl_dwa<10, 2>), dim3(c->njobs - inl + (a.fuse ? 2 : 0)), dim3(FCL_THREADS), lds_dwa, s, (const FclJob *)c->jobs + inl, c->njobs - inl, a, a.fuse,
+    if (v.tr.ks1 == 56) hipLaunchKernelGGL((k_fcl_fb<56, OK>), dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
+    else hipLaunchKernelGGL((k_fcl_fb<64, OK>), dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
+    hipLaunchKernelGGL((k_fcl_dwa<10, 2, OK>), dim3(c->njobs - inl + (a.fuse ? 2 : 0)), dim3(FCL_THREADS), lds_dwa, s, (const FclJob *)c->jobs + inl, c->njobs - inl, a, a.fuse,
                        (const float *)c->lnpart, c->nln, c->L.ln_w, (const float *)v.lossb, is_weights, v.w_f64, c->bs, K1, loss_sums,
                        c->njobs_heads - inl, c->flags, v.nflags, c->done_ctr, dflag, seq);
   } else if (c->fuse_fwd) {
@@ -461,8 +488,8 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
     // batch <= 512: FOUR launches -- the heads' weight-gradient jobs run beside the backward chain in its launch, the chain's
     // in the last one; every job covers all unroll positions, so its strip is the gradient and (no clipping) Adam follows in
     // the same workgroup; the last launch also carries the LayerNorm parameters and the loss sums
-    hipLaunchKernelGGL(k_fcl_bwd_dw, dim3(c->nwg + c->njobs_heads), dim3(FCL_THREADS), c->lds_bwd_dw, s, v, c->nwg, (const FclJob *)c->jobs, a);
-    hipLaunchKernelGGL((k_fcl_dwa<4, 2>), dim3(nchain_jobs + (a.fuse ? 2 : 0)), dim3(FCL_THREADS), lds_dwa, s,
+    hipLaunchKernelGGL(k_fcl_bwd_dw<OK>, dim3(c->nwg + c->njobs_heads), dim3(FCL_THREADS), c->lds_bwd_dw, s, v, c->nwg, (const FclJob *)c->jobs, a);
+    hipLaunchKernelGGL((k_fcl_dwa<4, 2, OK>), dim3(nchain_jobs + (a.fuse ? 2 : 0)), dim3(FCL_THREADS), lds_dwa, s,
                        (const FclJob *)c->jobs + c->njobs_heads, nchain_jobs, a, a.fuse, (const float *)c->lnpart, c->nln, c->L.ln_w,
                        (const float *)v.lossb, is_weights, v.w_f64, c->bs, K1, loss_sums, 0, (unsigned *)nullptr, 0, c->done_ctr, dflag, seq);
   } else {
@@ -481,11 +508,18 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
     if (clip)
       hipLaunchKernelGGL(k_fcl_grad, dim3(c->nblk), dim3(256), 0, s, (const float *)c->part, c->S, lnp, lnn,
                          c->L.ln_w, c->nflat, c->grad, c->bsq);
-    hipLaunchKernelGGL(k_fcl_adam, dim3(c->nblk + 1), dim3(256), 0, s, c->P, c->pk, (const int32_t *)c->posA, (const int32_t *)c->posB,
+    hipLaunchKernelGGL(k_fcl_adam<OK>, dim3(c->nblk + 1), dim3(256), 0, s, c->P, c->pk, (const int32_t *)c->posA, (const int32_t *)c->posB,
                        c->grad, clip ? (const float *)nullptr : (const float *)c->part, c->S, lnp, lnn, c->L.ln_w,
                        (const float *)c->bsq, c->nblk, c->m, c->v, (const float *)c->steps, lr ? lr : c->lr, o, c->nflat,
                        (const float *)v.lossb, is_weights, v.w_f64, c->bs, K1, loss_sums);
   }
+  };
+  const bool mom = c->opt_mom != 0.0;
+  if (c->opt_kind == FCL_SGD && mom) launches(std::integral_constant<int, FCL_SGD | FCL_MOM>{});
+  else if (c->opt_kind == FCL_SGD) launches(std::integral_constant<int, FCL_SGD>{});
+  else if (c->opt_kind == FCL_RMSPROP && mom) launches(std::integral_constant<int, FCL_RMSPROP | FCL_MOM>{});
+  else if (c->opt_kind == FCL_RMSPROP) launches(std::integral_constant<int, FCL_RMSPROP>{});
+  else launches(std::integral_constant<int, FCL_ADAM>{});
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -567,8 +601,8 @@ int mz_fcl_run(mz_fcl *c, const mz_fcl_source *src, int n_updates, const uint32_
   const char *ev_env = getenv("MZ_FCL_RUN_EVENTS");      // (1: an event behind every update instead of the completion word; A/B and tests)
   const bool use_flag = !(ev_env && ev_env[0] == '1');
   // the captured update of each slot (rebuilt when a hyper-parameter or an address it holds changes)
-  const double key[8] = {beta1, beta2, eps, weight_decay, clip_grad, (double)(adamw ? 1 : 0) + (lrs ? 2 : 0), (double)(uintptr_t)loss_sums,
-                         (double)(uintptr_t)c->lr};
+  const double key[11] = {beta1, beta2, eps, weight_decay, clip_grad, (double)(adamw ? 1 : 0) + (lrs ? 2 : 0), (double)(uintptr_t)loss_sums,
+                          (double)(uintptr_t)c->lr, (double)c->opt_kind, c->opt_mom, c->opt_alpha};
   if (memcmp(key, c->run_key, sizeof key)) { fcl_drop_run_graphs(c); memcpy(c->run_key, key, sizeof key); }
   if (!c->run_cap) HIPCHECK(hipStreamCreateWithFlags(&c->run_cap, hipStreamNonBlocking));
   for (int k = 0; k < c->nslots; ++k) {

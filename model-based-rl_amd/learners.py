@@ -4,12 +4,12 @@ recurrent steps, 0.5 gradient scale on the hidden state per step (learners.py:20
 cross-entropy losses on the categorical supports, 1/K gradient scale on the total loss (214), AdamW with eps 1.5e-4
 (utils.py:85-97).
 
-On a GPU, for FCNetwork with Adam / AdamW and categorical losses, the whole update is `mz_fcl_update` (_NativeFC): two
+On a GPU, for FCNetwork with Adam / AdamW, SGD or RMSprop and categorical losses, the whole update is `mz_fcl_update` (_NativeFC): two
 hand-written HIP launches at the reference's batch 256 (csrc/mz_fcl.hip.h) straight from the host batch -- no PyTorch operator, no autograd tape, no graph
 to capture; the parameters and the optimiser's state are views of the flat vectors those kernels update.  Every other case
-(MuZeroNetwork / TinyNetwork, scalar losses, other optimisers, `--no_native_learner`) runs the same step as PyTorch
-operators, captured in ONE hipGraph per update (stock `torch.cuda.CUDAGraph`: static batch tensors, capturable optimiser);
-`--no_graph_learner` and CPU learners run that tensor code eagerly.  The loop (`learn`) takes its batches through
+(MuZeroNetwork / TinyNetwork, scalar losses, `--no_native_learner`) runs the same step as PyTorch operators, captured in
+ONE hipGraph per update with Adam / AdamW (stock `torch.cuda.CUDAGraph`: static batch tensors, capturable optimiser);
+`--no_graph_learner`, SGD / RMSprop off the native step and CPU learners run that tensor code eagerly.  The loop (`learn`) takes its batches through
 _BatchSource: sampled a few updates ahead, priority refreshes one update behind and not waited for (the reference's learner
 prefetches `batches_per_fetch` batches and sends its refresh fire-and-forget, learners.py:124,182)."""
 import os
@@ -174,10 +174,28 @@ class _NativeFC(object):
   chain + heads (losses, their backward) + backward chain + the heads' weight gradients handing over inside one launch, the chain's weight gradients -- each strip
   followed by Adam / AdamW on its weights in the same workgroup -- no GEMM library, no
   autograd tape, nothing PyTorch launches.  The network's parameters and the optimiser's exp_avg / exp_avg_sq / step
-  tensors become VIEWS of three flat device vectors (engine.WEIGHT_ORDER) the kernels update in place, so state_dicts,
+  tensors (SGD: momentum_buffer; RMSprop: step / square_avg / momentum_buffer) become VIEWS of three flat device vectors
+  (engine.WEIGHT_ORDER) the kernels update in place, so state_dicts,
   checkpoints, get_weights and the PyTorch step itself keep working on the same storage.  The kernels read the weights
   from packed fragment-order copies they rewrite at every step; a write from PyTorch's side (load_state_dict, the
   graph capture's restore) is noticed through the parameters' version counters and repacked (sync)."""
+
+  ADAM, SGD, RMSPROP = 0, 1, 2          # mz_fcl_set_optimizer's kinds
+
+  @staticmethod
+  def kind_of(optimizer):
+    """the native kind of a torch optimiser the native step runs exactly (utils.py:73-83 builds no other form), else None"""
+    gs = optimizer.param_groups
+    g = gs[0]
+    if len(gs) != 1 or g.get('maximize'):
+      return None
+    if isinstance(optimizer, (torch.optim.AdamW, torch.optim.Adam)):
+      return None if g.get('amsgrad') or not torch.is_tensor(g['lr']) else _NativeFC.ADAM
+    if isinstance(optimizer, torch.optim.SGD):
+      return None if g.get('nesterov') or g.get('dampening', 0) != 0 else _NativeFC.SGD
+    if isinstance(optimizer, torch.optim.RMSprop):
+      return None if g.get('centered') else _NativeFC.RMSPROP
+    return None
 
   @staticmethod
   def eligible(learner, host):
@@ -185,10 +203,15 @@ class _NativeFC(object):
     cfg, net = learner.config, learner.network
     if learner.device.type != 'cuda' or not isinstance(net, FCNetwork) or getattr(cfg, 'no_native_learner', False):
       return False
-    if getattr(cfg, 'no_support', False) or getattr(cfg, 'optimizer', 'AdamW') not in ('AdamW', 'Adam') or not learner.use_graph:
+    if getattr(cfg, 'no_support', False):
       return False
-    g = learner.optimizer.param_groups[0]
-    if len(learner.optimizer.param_groups) != 1 or g.get('amsgrad') or g.get('maximize') or not torch.is_tensor(g['lr']):
+    name = getattr(cfg, 'optimizer', 'AdamW')
+    if name in ('AdamW', 'Adam'):
+      if not learner.use_graph:
+        return False
+    elif name not in ('SGD', 'RMSprop') or not learner.native_only:
+      return False
+    if _NativeFC.kind_of(learner.optimizer) is None:
       return False
     bs, K, A = host['obs'].shape[0], host['act'].shape[1], net.action_space
     Sv = cfg.value_support_max - cfg.value_support_min + 1
@@ -203,6 +226,7 @@ class _NativeFC(object):
     from .engine import WEIGHT_ORDER
     cfg, net, dev, opt = learner.config, learner.network, learner.device, learner.optimizer
     self.lib, self.learner, self.dev = _abi.load(), learner, dev
+    self.kind = _NativeFC.kind_of(opt)
     self.bs, self.K = host['obs'].shape[0], host['act'].shape[1]
     self.shape = {k: host[k].shape for k in _GraphedUpdate.ORDER}
     self.h = C.c_void_p()
@@ -210,6 +234,10 @@ class _NativeFC(object):
       _abi.check(self.lib.mz_fcl_create(self.bs, self.K, host['obs'].shape[1], net.action_space, int(cfg.value_support_min),
                                         int(cfg.value_support_max), int(cfg.reward_support_min), int(cfg.reward_support_max),
                                         int(bool(cfg.no_target_transform)), C.byref(self.h)), 'mz_fcl_create')
+    g = opt.param_groups[0]
+    mom = float(g.get('momentum', 0.0) or 0.0) if self.kind != self.ADAM else 0.0
+    _abi.check(self.lib.mz_fcl_set_optimizer(self.h, self.kind, mom, float(g.get('alpha', 0.0)) if self.kind == self.RMSPROP else 0.0),
+               'mz_fcl_set_optimizer')
     named = dict(net.named_parameters())
     self.params = [named[k] for k in WEIGHT_ORDER]
     n = sum(p.numel() for p in self.params)
@@ -221,19 +249,41 @@ class _NativeFC(object):
     with torch.no_grad():
       for i, p in enumerate(self.params):
         k = p.numel()
-        st = opt.state[p]
         self.flat[off:off + k].copy_(p.reshape(-1))
-        if 'exp_avg' in st:
-          self.m[off:off + k].copy_(st['exp_avg'].reshape(-1))
-          self.v[off:off + k].copy_(st['exp_avg_sq'].reshape(-1))
-          self.steps[i] = float(st['step'])
-        p.data = self.flat[off:off + k].view(p.shape)
-        st['step'] = self.steps[i]
-        st['exp_avg'] = self.m[off:off + k].view(p.shape)
-        st['exp_avg_sq'] = self.v[off:off + k].view(p.shape)
+        m, v = self.m[off:off + k].view(p.shape), self.v[off:off + k].view(p.shape)
+        if self.kind == self.ADAM:
+          st = opt.state[p]
+          if 'exp_avg' in st:
+            self.m[off:off + k].copy_(st['exp_avg'].reshape(-1))
+            self.v[off:off + k].copy_(st['exp_avg_sq'].reshape(-1))
+            self.steps[i] = float(st['step'])
+          p.data = self.flat[off:off + k].view(p.shape)
+          st['step'] = self.steps[i]
+          st['exp_avg'] = m
+          st['exp_avg_sq'] = v
+        else:
+          # the state torch's SGD / RMSprop keep, under their keys (SGD: momentum_buffer -- none with momentum 0, not even an empty
+          # entry; RMSprop: step, square_avg, momentum_buffer when momentum > 0); a loaded state is copied in first (torch's SGD has no
+          # buffer before its first step: the zero buffer gives the same first step)
+          old = opt.state.get(p, {})
+          if old.get('momentum_buffer') is not None:
+            m.copy_(old['momentum_buffer'])
+          if 'square_avg' in old:
+            v.copy_(old['square_avg'])
+          if 'step' in old:
+            self.steps[i] = float(old['step'])
+          p.data = self.flat[off:off + k].view(p.shape)
+          if self.kind == self.RMSPROP:
+            st = opt.state[p]
+            st['step'] = self.steps[i]
+            st['square_avg'] = v
+          if mom != 0.0:
+            opt.state[p]['momentum_buffer'] = m
         off += k
-    g = opt.param_groups[0]
-    self.lr = g['lr']
+    # Adam / AdamW: the rate is the capturable optimiser's device tensor; SGD / RMSprop keep a Python float (their PyTorch step is
+    # eager): the native step reads a device float of its own, written in stream order before every step whose rate changed
+    self.lr = g['lr'] if self.kind == self.ADAM else torch.tensor(float(g['lr']), dtype=torch.float32, device=dev)
+    self._lr_host = None if self.kind == self.ADAM else float(g['lr'])
     self.versions = None
     self._source = None           # (replay object, its mz_fcl_source table) of run()
     self.in_flight = False        # run() returned with updates in flight whose refreshes are owed
@@ -243,6 +293,20 @@ class _NativeFC(object):
 
   def fits(self, host):
     return all(host[k].shape == self.shape[k] for k in _GraphedUpdate.ORDER)
+
+  def _hyper(self):
+    """(beta1, beta2, eps, weight_decay, clip_grad, adamw) of the next step; SGD / RMSprop: their rate into the device float first"""
+    cfg, opt = self.learner.config, self.learner.optimizer
+    g = opt.param_groups[0]
+    clip = float(getattr(cfg, 'clip_grad', 0) or 0)
+    if self.kind == self.ADAM:
+      b1, b2 = g['betas']
+      return float(b1), float(b2), float(g['eps']), float(g['weight_decay']), clip, int(isinstance(opt, torch.optim.AdamW))
+    lr = float(g['lr'])
+    if lr != self._lr_host:
+      self.lr.fill_(lr)
+      self._lr_host = lr
+    return 0.0, 0.0, float(g.get('eps', 0.0)), float(g['weight_decay']), clip, 0
 
   def sync(self, force=False):
     """the packed weight copies follow the parameters: (re)bind after a write that did not come from mz_fcl_step"""
@@ -258,13 +322,11 @@ class _NativeFC(object):
   def step(self, obs, act, t_rew, t_val, t_pol, w, no_update=False):
     import ctypes as C
     from . import _abi
-    cfg, g = self.learner.config, self.learner.optimizer.param_groups[0]
     ptr = lambda t: C.c_void_p(t.data_ptr())
     new_errors = torch.empty(self.bs, dtype=torch.float32, device=self.dev)
-    b1, b2 = g['betas']
+    b1, b2, eps, wd, clip, adamw = self._hyper()
     _abi.check(self.lib.mz_fcl_step(self.h, ptr(obs), ptr(act), int(act.dtype == torch.int32), ptr(t_rew), ptr(t_val), ptr(t_pol), ptr(w), int(w.dtype == torch.float64),
-                                    float(b1), float(b2), float(g['eps']), float(g['weight_decay']), float(getattr(cfg, 'clip_grad', 0) or 0),
-                                    int(isinstance(self.learner.optimizer, torch.optim.AdamW)), int(bool(no_update)), ptr(new_errors),
+                                    b1, b2, eps, wd, clip, adamw, int(bool(no_update)), ptr(new_errors),
                                     ptr(self.learner._loss_dev), _stream_ptr(self.flat)), 'mz_fcl_step')
     return new_errors
 
@@ -274,14 +336,12 @@ class _NativeFC(object):
     import ctypes as C
     from . import _abi
     self.flush()
-    cfg, g = self.learner.config, self.learner.optimizer.param_groups[0]
     ptr = lambda a: C.c_void_p(a.__array_interface__['data'][0])
-    b1, b2 = g['betas']
+    b1, b2, eps, wd, clip, adamw = self._hyper()
     slot = C.c_int(0)
     _abi.check(self.lib.mz_fcl_update(self.h, ptr(host['obs']), ptr(host['act']), int(host['act'].dtype == np.int32), ptr(host['t_rew']),
                                       ptr(host['t_val']), ptr(host['t_pol']), ptr(host['w']), int(host['w'].dtype == np.float64),
-                                      float(b1), float(b2), float(g['eps']), float(g['weight_decay']), float(getattr(cfg, 'clip_grad', 0) or 0),
-                                      int(isinstance(self.learner.optimizer, torch.optim.AdamW)), C.c_void_p(self.learner._loss_dev.data_ptr()),
+                                      b1, b2, eps, wd, clip, adamw, C.c_void_p(self.learner._loss_dev.data_ptr()),
                                       _stream_ptr(self.flat), C.byref(slot)), 'mz_fcl_update')
     return slot.value
 
@@ -294,7 +354,7 @@ class _NativeFC(object):
     import ctypes as C
     import random
     from . import _abi
-    cfg, g, lib = self.learner.config, self.learner.optimizer.param_groups[0], self.lib
+    cfg, lib = self.learner.config, self.lib
     if self._source is None or self._source[0] is not replay:
       rlib = _abi.load_replay()
       src = _abi.MzFclSource(replay._h.value if hasattr(replay._h, 'value') else replay._h,
@@ -329,10 +389,9 @@ class _NativeFC(object):
     rg = np.ascontiguousarray(np.broadcast_to(self.learner.obs_range.reshape(-1), (O,)), np.float32) if norm else None
     lr = None if lrs is None else np.ascontiguousarray(lrs, np.float32)
     ptr = lambda a: None if a is None else C.c_void_p(a.__array_interface__['data'][0])
-    b1, b2 = g['betas']
+    b1, b2, eps, wd, clip, adamw = self._hyper()
     _abi.check(lib.mz_fcl_run(self.h, C.byref(src), int(n), None, ptr(key), C.byref(pos), C.byref(beta), ptr(mn), ptr(rg),
-                              float(b1), float(b2), float(g['eps']), float(g['weight_decay']), float(getattr(cfg, 'clip_grad', 0) or 0),
-                              int(isinstance(self.learner.optimizer, torch.optim.AdamW)), ptr(lr),
+                              b1, b2, eps, wd, clip, adamw, ptr(lr),
                               C.c_void_p(self.learner._loss_dev.data_ptr()), _stream_ptr(self.flat), C.byref(pads), ptr(py_key),
                               C.byref(py_pos)), 'mz_fcl_run')
     replay.beta = np.float64(beta.value) if float(replay.beta) < 1 else replay.beta
@@ -573,6 +632,9 @@ class Learner(Logger):
     # one captured hipGraph per update on a GPU (module docstring); the optimisers with a capturable step only
     self.use_graph = (self.device.type == 'cuda' and not getattr(config, 'no_graph_learner', False) and
                       getattr(config, 'optimizer', 'AdamW') in ('AdamW', 'Adam'))
+    # SGD / RMSprop on a GPU: the native step where it applies (FCNetwork), their eager PyTorch step elsewhere (no captured graph)
+    self.native_only = (self.device.type == 'cuda' and not getattr(config, 'no_graph_learner', False) and
+                        not getattr(config, 'no_native_learner', False) and getattr(config, 'optimizer', 'AdamW') in ('SGD', 'RMSprop'))
     self.optimizer = make_optimizer(config, self.network.parameters(), capturable=self.use_graph)
     self.lr_scheduler = make_lr_scheduler(config, self.optimizer)
     if getattr(config, 'scalar_loss', 'MSE') not in ('MSE', 'Huber'):
@@ -584,7 +646,7 @@ class Learner(Logger):
     # kernels on a CPU learner and with --no_hip_learner_ops
     self.hip_ops = self.device.type == 'cuda' and not getattr(config, 'no_hip_learner_ops', False)
     self._graph = None          # _GraphedUpdate, built from the first batch
-    self._native = None         # _NativeFC (FCNetwork, Adam / AdamW, categorical losses), built from the first batch
+    self._native = None         # _NativeFC (FCNetwork, Adam / AdamW / SGD / RMSprop, categorical losses), built from the first batch
     self._source = None         # _BatchSource while learn() runs
     self._pending = None        # (idxs, slot) of the update whose priority refresh has not reached the replay yet
     self.native_loop_updates = 0      # updates taken by mz_fcl_run (the loop body in native code)
@@ -852,7 +914,7 @@ class Learner(Logger):
     """One training step (learners.py:164-230).  defer_priorities (learn()'s loop): this batch's new errors go to the replay
     at the NEXT call, i.e. while the following update is already running on the GPU."""
     host, idxs = self._host_batch(batch)
-    if self.use_graph:
+    if self.use_graph or self.native_only:
       if self._native is not None and not self._native.fits(host):
         self.flush_priorities()
         self._native.close()
@@ -860,6 +922,7 @@ class Learner(Logger):
       if self._native is None and (self._graph is None or not self._graph.fits(host)) and _NativeFC.eligible(self, host):
         self.flush_priorities()
         self._native = _NativeFC(self, host)
+    if self._native is not None or self.use_graph:
       if self._native is not None:
         # FCNetwork: the step's HIP launches from the host batch (mz_fcl_update), no PyTorch operator, no graph to capture
         self._native.sync()
@@ -942,7 +1005,7 @@ class Learner(Logger):
     from .networks import FCNetwork
     cfg = self.config
     replay = getattr(self.replay_buffer, '_obj', self.replay_buffer)
-    return (self.device.type == 'cuda' and self.use_graph and isinstance(self.network, FCNetwork) and hasattr(replay, '_h') and
+    return (self.device.type == 'cuda' and (self.use_graph or self.native_only) and isinstance(self.network, FCNetwork) and hasattr(replay, '_h') and
             hasattr(replay, 'sample_batches_arrays') and not getattr(cfg, 'no_native_learner', False) and
             not getattr(cfg, 'no_native_loop', False) and not getattr(cfg, 'no_support', False))
 
