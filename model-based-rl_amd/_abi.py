@@ -5,6 +5,7 @@ There is NO CPU fallback: if the HIP library is missing or no GPU is visible, lo
 loudly."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
@@ -16,20 +17,26 @@ _lib = None
 
 HIPCC_FLAGS = ['-O3', '--offload-arch=gfx950', '-ffp-contract=off', '-std=c++17', '-fPIC', '-Wno-unused-value',
                '-Wno-unused-result']
-# translation units of libmz_hip.so: the host side + root / stepwise kernels, and one unit per shape of the two search
-# kernels (mz_kernels.inc; the same list as launch_fused / launch_h2 in mz_engine.hip dispatch to)
-FUSED_SHAPES = [(14, 1, 4), (14, 1, 8), (15, 1, 8), (15, 1, 16), (16, 1, 16), (18, 1, 16), (18, 2, 32), (21, 2, 32)]
-H2_SHAPES = [4, 8, 16]
-DEV_FUSED_SHAPES, DEV_H2_SHAPES = [(14, 1, 4), (14, 1, 8)], [4, 8]      # -DMZ_DEV_ONLY: the two bench shapes
 
 
 def translation_units(extra=()):
-  dev = '-DMZ_DEV_ONLY' in extra
+  """translation units of libmz_hip.so: the host side + root / stepwise kernels, and one unit per shape of the two search
+  kernels.  The shapes are read from the rows of csrc/mz_kernels.inc (`#define MZ_..._ROWS_DEV(X) X(..) X(..)`), the one
+  list mz_engine.hip generates its dispatch from; -DMZ_DEV_ONLY: the _DEV rows (the two bench shapes) only"""
+  with open(os.path.join(_CSRC, 'mz_kernels.inc')) as f:
+    text = f.read().replace('\\\n', ' ')      # (a list may continue over lines)
+  ints = lambda t: tuple(int(v) for v in t.split(','))
+
+  def rows(name):      # the X(...) tuples of the list's _DEV (+ _MORE) part; [0] is the row's largest action count
+    parts = ['_DEV'] if '-DMZ_DEV_ONLY' in extra else ['_DEV', '_MORE']
+    bodies = [re.search(r'^#define %s%s\(X\)(.*)$' % (name, p), text, re.M).group(1) for p in parts]
+    return [ints(r) for body in bodies for r in re.findall(r'X\(([^)]*)\)', body)]
+  game = ints(re.search(r'^#define MZ_GAME_SHAPE (.*)$', text, re.M).group(1))
   units = [('mz_engine', 'mz_engine.hip', [])]
-  for ks1, jtp, g in (DEV_FUSED_SHAPES if dev else FUSED_SHAPES):
+  for _, ks1, jtp, g in rows('MZ_FUSED_ROWS'):
     units.append(('mz_inst_f_%d_%d_%d' % (ks1, jtp, g), 'mz_inst.hip', ['-DMZ_INST_F=%d,%d,%d' % (ks1, jtp, g)] +
-                  (['-DMZ_INST_GAME=1'] if (ks1, jtp, g) == (15, 1, 16) else [])))
-  for g in (DEV_H2_SHAPES if dev else H2_SHAPES):
+                  (['-DMZ_INST_GAME=1'] if (ks1, jtp, g) == game else [])))
+  for _, g in rows('MZ_H2_ROWS'):
     units.append(('mz_inst_h_%d' % g, 'mz_inst.hip', ['-DMZ_INST_H=%d' % g]))
   return units
 

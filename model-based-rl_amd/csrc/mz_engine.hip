@@ -9,11 +9,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <deque>
 #include <functional>
 #include <string>
-#include <chrono>
 #include <vector>
 
 #include "../../include/mz_engine.h"
@@ -31,14 +31,45 @@
 #include "mz_learner.hip.h"
 #include "mz_fcl.hip.h"
 #include "mz_eval.hip.h"
-// the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are launched
+// the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
+// tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
-MZ_ALL_FUSED(extern)
-MZ_ALL_H2(extern)
-#ifndef MZ_DEV_ONLY
-// whole moves of the device TicTacToe environment (two players, 9 actions: the <15, 1, 16> shape, compact LDS trees)
-extern template __global__ void k_search_fused<15, 1, 16, 2, false, false, true, true> MZ_KARGS;
-#endif
+#define MZ_KF(S, ...) extern template __global__ void k_search_fused<MZ_UNPACK S, __VA_ARGS__> MZ_KARGS;
+#define MZ_KG MZ_KF
+#define MZ_KH(S, ...) extern template __global__ void k_search_h2<MZ_UNPACK S, __VA_ARGS__> MZ_KARGS;
+MZ_ALL_KERNELS
+#undef MZ_KF
+#undef MZ_KG
+#undef MZ_KH
+
+// a row of the shape lists (k_search_h2: ks1 = jtp = 0); an engine runs the first row with amax >= its action count
+struct SearchShape { int amax, ks1, jtp, g; };
+#define MZ_ROW_F(AMAX, KS1, JTP, G) {AMAX, KS1, JTP, G},
+#define MZ_ROW_H(AMAX, G) {AMAX, 0, 0, G},
+static constexpr SearchShape g_fused_shapes[] = {MZ_FUSED_ROWS(MZ_ROW_F)};
+static constexpr SearchShape g_h2_shapes[] = {MZ_H2_ROWS(MZ_ROW_H)};
+static_assert(g_fused_shapes[sizeof g_fused_shapes / sizeof *g_fused_shapes - 1].amax == MZ_MAX_ACTIONS &&
+              g_h2_shapes[sizeof g_h2_shapes / sizeof *g_h2_shapes - 1].amax == MZ_H2_MAXA, "the last row covers every action count");
+template <size_t N>
+static const SearchShape *shape_for(const SearchShape (&rows)[N], int A) {
+  for (const SearchShape &r : rows) if (A <= r.amax) return &r;
+  return nullptr;
+}
+
+// every compiled search kernel: its address beside the template arguments it was instantiated with (kind 1
+// k_search_fused, 2 k_search_h2).  Kernels are found by those arguments, never by position.
+struct SearchKernel { int kind; SearchShape shape; int lt; bool prof, sp, head, game; const void *fn; };
+#define MZ_KF(S, LT, PROF, SP, HEAD) {1, {0, MZ_UNPACK S}, LT, PROF, SP, HEAD, false, (const void *)k_search_fused<MZ_UNPACK S, LT, PROF, SP, HEAD>},
+#define MZ_KG(S, LT, PROF, SP, HEAD, GAME) {1, {0, MZ_UNPACK S}, LT, PROF, SP, HEAD, GAME, (const void *)k_search_fused<MZ_UNPACK S, LT, PROF, SP, HEAD, GAME>},
+#define MZ_KH(S, LT, PROF, SP, HEAD) {2, {0, 0, 0, MZ_UNPACK S}, LT, PROF, SP, HEAD, false, (const void *)k_search_h2<MZ_UNPACK S, LT, PROF, SP, HEAD>},
+static const SearchKernel g_search_kernels[] = {MZ_ALL_KERNELS};
+static const void *find_kernel(int kind, const SearchShape &sh, int lt, bool prof, bool sp, bool head, bool game) {
+  for (const SearchKernel &k : g_search_kernels)
+    if (k.kind == kind && k.shape.ks1 == sh.ks1 && k.shape.jtp == sh.jtp && k.shape.g == sh.g && k.lt == lt &&
+        k.prof == prof && k.sp == sp && k.head == head && k.game == game)
+      return k.fn;
+  return nullptr;
+}
 
 static thread_local std::string g_err;
 
@@ -93,19 +124,12 @@ struct mz_engine {
   const f32x4 *wstream = nullptr;   // per-wave cyclic weight stream for the fused search kernel
   const f32x4 *istream = nullptr;   // per-wave weight stream of the root kernel (initial inference)
   int nst0 = 0;                     // its run-time first-stage steps (obs_dim + 1 columns, two k-steps per step)
-  int ks1sel = 0;                   // fc1 k-steps of the fused kernel instantiation chosen for this A
+  const SearchShape *shape = nullptr, *shape_h2 = nullptr;   // this A's rows of the shape lists (shape_h2: split_f16 only)
   bool use_fused = true;
   bool use_lds_trees = true;
   bool use_lds_hybrid = true;
-  bool fuse_record = false;         // set by the self-play loop around its search launch: finalize + record in the kernel tail
-  unsigned long long *prof_buf = nullptr;   // non-null only inside mz_search_phase_profile
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // non-null only inside mz_search_timed: bracket the search kernel's dispatch
-  bool lds_attr_set = false, lds_attr_set_prof = false;   // hipFuncAttributeMaxDynamicSharedMemorySize is per device: set once per engine
-  bool lds_attr_set_head = false;
+  std::vector<const void *> lds_attr_done;   // kernels whose hipFuncAttributeMaxDynamicSharedMemorySize is set (per device: once per engine)
   bool use_persist = true;          // self-play loop: whole moves inside ONE launch of the search kernel (its HEAD instantiation)
-  int persist_moves = 0;            // > 0 only around that launch: moves it plays
-  float *direct_records = nullptr;  // mz_selfplay_steps_into: device mapping of the caller's pinned buffer, around its launches
-  unsigned long long *head_prof = nullptr;   // non-null only inside mz_selfplay_phase_profile
   // record drain on a copy stream (mz_selfplay_drain): event behind the last copy, and how far the compute stream
   // has been ordered behind the copies
   hipEvent_t drain_ev = nullptr;    // the LATEST drain's copy (chains drains issued on different streams)
@@ -498,7 +522,7 @@ static int build_packing(mz_engine *e) {
   // fused kernel: fc1 weights with the bias inside the packed matrix -- prediction: one more input column (constant-1
   // input); dynamics: added to the one-hot columns (fill_fc1_foldbias); the k-step count is that of the kernel
   // instantiation chosen for this action count (zero-padded above 50+A)
-  const int ks1f = e->ks1sel, ks3f = (MZ_H + 1 + 3) / 4;
+  const int ks1f = e->shape->ks1, ks3f = (MZ_H + 1 + 3) / 4;
   const size_t p_w1f = seg((size_t)4 * 4 * ks1f * 256), p_w3f = seg((size_t)4 * 4 * ks3f * 256);
   const int nj2 = 2 + jtp;
   const int real_steps = ks1f + 12 + ks3f + 2 * nj2;
@@ -644,17 +668,18 @@ static int build_packing(mz_engine *e) {
     else hipLaunchKernelGGL(kern<2>, dim3(grid), dim3(256), 0, s, __VA_ARGS__);                \
   } while (0)
 
-// (e->ev_start set: the dispatch carries start / stop events -- mz_tree_pair_timed, the clock of bench.py --workload tree)
+// (ev0 set: the dispatch carries start / stop events -- mz_tree_pair_timed, the clock of bench.py --workload tree)
 #define TREE_GO_(kern, G_, s, ...)                                                                                \
   do {                                                                                                            \
-    if (e->ev_start) hipExtLaunchKernelGGL(kern<G_>, dim3(blocks_), dim3(threads_), 0, s, e->ev_start, e->ev_stop, 0, __VA_ARGS__); \
+    if (ev0_) hipExtLaunchKernelGGL(kern<G_>, dim3(blocks_), dim3(threads_), 0, s, ev0_, ev1_, 0, __VA_ARGS__);     \
     else hipLaunchKernelGGL(kern<G_>, dim3(blocks_), dim3(threads_), 0, s, __VA_ARGS__);                          \
   } while (0)
-#define TREE_LAUNCH(kern, s, ...)                                                             \
+#define TREE_LAUNCH_EV(kern, s, ev0, ev1, ...)                                                \
   do {                                                                                        \
     const int threads_ = 256;                                                                 \
     const int total_ = e->B * e->G;                                                           \
     const int blocks_ = (total_ + threads_ - 1) / threads_;                                   \
+    const hipEvent_t ev0_ = (ev0), ev1_ = (ev1);                                              \
     switch (e->G) {                                                                           \
       case 4: TREE_GO_(kern, 4, s, __VA_ARGS__); break;                                       \
       case 8: TREE_GO_(kern, 8, s, __VA_ARGS__); break;                                       \
@@ -662,7 +687,7 @@ static int build_packing(mz_engine *e) {
       default: TREE_GO_(kern, 32, s, __VA_ARGS__); break;                                     \
     }                                                                                         \
   } while (0)
-
+#define TREE_LAUNCH(kern, s, ...) TREE_LAUNCH_EV(kern, s, nullptr, nullptr, __VA_ARGS__)
 
 // BaseNetwork.initial_inference for all B rows; selfplay: + synthetic observation, root expansion, Dirichlet
 // noise and first descent (mz_root.hip.h)
@@ -695,229 +720,89 @@ static size_t fused_head_dyn_lds(int sims, int NN, int lt) {
   return root > trees ? root : trees;
 }
 
-template <int KS1, int JTP, int G, int LT, bool SP>
-static int launch_fused_sp(mz_engine *e, int num_simulations, int sims_done, hipStream_t s) {
-  const size_t dyn = mz_fused_dyn_lds(e->sims, e->NN, LT);
-  const MzRootArgs ra0 = {nullptr, 0, 1, 0.0, 0.0};
-  if constexpr (LT != 0 && SP) {
-    if (e->persist_moves > 0) {      // the self-play loop: persist_moves whole moves in this launch
-      const size_t dynh = fused_head_dyn_lds(e->sims, e->NN, LT);
-      const MzRootArgs ra = {e->istream, e->nst0, e->persist_moves, e->cfg.root_dirichlet_alpha,
-                             e->cfg.root_exploration_fraction};
-      if (!e->lds_attr_set_head) {
-        HIPCHECK(hipFuncSetAttribute((const void *)k_search_fused<KS1, JTP, G, LT, false, SP, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(float) * mz_fused_lds_floats(LT)));
-        e->lds_attr_set_head = true;
-      }
-      if (e->ev_start)
-        hipExtLaunchKernelGGL((k_search_fused<KS1, JTP, G, LT, false, SP, true>), dim3(e->Bp / MZ_ROWS), dim3(256), dynh, s,
-                              e->ev_start, e->ev_stop, 0, e->nv, e->tv, e->wstream, num_simulations, 0,
-                              (unsigned long long *)nullptr, e->sp, 1, (uint64_t)e->cfg.seed, ra);
-      else
-        hipLaunchKernelGGL((k_search_fused<KS1, JTP, G, LT, false, SP, true>), dim3(e->Bp / MZ_ROWS), dim3(256), dynh, s,
-                           e->nv, e->tv, e->wstream, num_simulations, 0, e->head_prof, e->sp, 1,
-                           (uint64_t)e->cfg.seed, ra);
-      HIPCHECK(hipGetLastError());
-      return 0;
-    }
-  }
-#ifndef MZ_DEV_ONLY
-  if constexpr (KS1 == 15 && JTP == 1 && G == 16 && LT == 2 && !SP) {
-    if (e->persist_moves > 0 && e->sp.env_kind == 1) {      // whole moves of the device TicTacToe environment in this launch
-      const size_t dynh = fused_head_dyn_lds(e->sims, e->NN, LT);
-      const MzRootArgs ra = {e->istream, e->nst0, e->persist_moves, e->cfg.root_dirichlet_alpha,
-                             e->cfg.root_exploration_fraction};
-      if (!e->lds_attr_set_head) {
-        HIPCHECK(hipFuncSetAttribute((const void *)k_search_fused<15, 1, 16, 2, false, false, true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(float) * mz_fused_lds_floats(LT)));
-        e->lds_attr_set_head = true;
-      }
-      if (e->ev_start)
-        hipExtLaunchKernelGGL((k_search_fused<15, 1, 16, 2, false, false, true, true>), dim3(e->Bp / MZ_ROWS), dim3(256), dynh, s,
-                              e->ev_start, e->ev_stop, 0, e->nv, e->tv, e->wstream, num_simulations, 0,
-                              (unsigned long long *)nullptr, e->sp, 1, (uint64_t)e->cfg.seed, ra);
-      else
-        hipLaunchKernelGGL((k_search_fused<15, 1, 16, 2, false, false, true, true>), dim3(e->Bp / MZ_ROWS), dim3(256), dynh, s,
-                           e->nv, e->tv, e->wstream, num_simulations, 0, e->head_prof, e->sp, 1,
-                           (uint64_t)e->cfg.seed, ra);
-      HIPCHECK(hipGetLastError());
-      return 0;
-    }
-  }
+// The LDS of a CU: a search kernel's static LDS and the dynamic LDS of a launch have to fit it together
+static const size_t MZ_LDS_BYTES = 160 * 1024;
+static bool lds_fits(size_t static_bytes, size_t dyn_bytes) { return static_bytes + dyn_bytes <= MZ_LDS_BYTES; }
+
+// Which search kernel this engine runs right now, and on how much LDS: read by the launch, the self-play loop,
+// mz_selfplay_moves_per_launch and mz_search_kernel_info alike.  Computed on demand (sp.env_kind, stream_scaled and
+// root_hidden_external change after mz_create).
+struct SearchPlan {
+  int kind;                      // what launch_search runs now: 0 the stand-alone kernels, else fkind
+  int fkind;                     // the engine's fused kernel: 2 k_search_h2 where split_f16 applies, else 1 k_search_fused
+  const SearchShape *shape;      // its row of the shape list
+  int lt;                        // its tree placement: 1 whole trees in LDS, 2 compact, 0 global pool
+  bool sp;                       // its single-player instantiation
+  size_t lds_static, dyn, dyn_head;   // bytes: static LDS, dynamic LDS of a plain launch / of a whole-moves (HEAD) launch
+  bool game;                     // whole moves are those of the device TicTacToe environment (the game kernel)
+  bool persist;                  // the self-play loop runs as whole moves inside one launch
+};
+static SearchPlan search_plan(const mz_engine *e) {
+  SearchPlan p = {};
+  auto lds_static = [](int kind, int lt) { return sizeof(float) * (size_t)(kind == 2 ? mz_h2_lds_floats(lt) : mz_fused_lds_floats(lt)); };
+  // trees in LDS when 16 of them fit beside the kernel's static LDS; if not, at least the fields the descent reads
+  // (N, E, P, reward + discount * Q); else (0) in the global pool
+  auto place = [&](int kind) {
+    for (int lt = 1; lt <= (!e->use_lds_trees ? 0 : (e->use_lds_hybrid ? 2 : 1)); ++lt)
+      if (lds_fits(lds_static(kind, lt), mz_fused_dyn_lds(e->sims, e->NN, lt))) return lt;
+    return 0;
+  };
+  p.fkind = 2;
+  p.lt = e->split_f16 ? place(2) : 0;
+  if (p.lt == 0) { p.fkind = 1; p.lt = place(1); }      // (the split-f16 kernel has no global-pool placement: the exact one)
+  p.shape = p.fkind == 2 ? e->shape_h2 : e->shape;
+  p.sp = !e->cfg.two_players;       // single-player games (every reference environment but TicTacToe): no to_play handling
+  p.lds_static = lds_static(p.fkind, p.lt);
+  p.dyn = mz_fused_dyn_lds(e->sims, e->NN, p.lt);
+  p.dyn_head = fused_head_dyn_lds(e->sims, e->NN, p.lt);
+  p.kind = fused_usable(e) && !e->root_hidden_external ? p.fkind : 0;
+  p.game = e->sp.env_kind == 1;
+  // whole moves: LDS trees and a HEAD kernel -- single player on the synthetic environment, or the device TicTacToe
+  // environment on the exact-f32 game kernel (host-given uniforms / draws work there too)
+  p.persist = e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
+              (p.game ? !e->split_f16 && e->cfg.two_players && find_kernel(1, *p.shape, p.lt, false, false, true, true) != nullptr
+                      : p.sp && !e->sp.env_kind);
+  return p;
+}
+
+// arguments of one search launch
+struct SearchOpts {
+  int sims;                              // simulations to run
+  int sims_done = 0;                     // simulations the trees already hold
+  int moves = 0;                         // > 0: that many whole self-play moves inside the launch (HEAD); 0: one search
+  bool record = false;                   // self-play: finalize the move and write its record in the kernel tail
+  unsigned long long *prof = nullptr;    // phase-cycle counters (mz_search_phase_profile, mz_selfplay_phase_profile)
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // bracket the dispatch itself (what rocprofv3's kernel trace reports)
+};
+
+static int launch_fused(mz_engine *e, const SearchPlan &p, const SearchOpts &o, hipStream_t s) {
+  const bool head = o.moves > 0;
+  const void *fn = find_kernel(p.fkind, *p.shape, p.lt, !head && o.prof, p.sp, head, head && p.game);
+  if (!fn) {
+#ifdef MZ_DEV_ONLY      // kernel development: only the two bench shapes are instantiated
+    if (!find_kernel(p.fkind, *p.shape, p.lt, false, p.sp, false, false))
+      return fail("MZ_DEV_ONLY build: action_space %d not instantiated", e->A);
 #endif
-  if (e->persist_moves > 0) return fail("internal: no HEAD instantiation for this configuration");
-  if (e->prof_buf) {
-    if (!e->lds_attr_set_prof) {
-      HIPCHECK(hipFuncSetAttribute((const void *)k_search_fused<KS1, JTP, G, LT, true, SP>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(float) * mz_fused_lds_floats(LT)));
-      e->lds_attr_set_prof = true;
-    }
-    hipLaunchKernelGGL((k_search_fused<KS1, JTP, G, LT, true, SP>), dim3(e->Bp / MZ_ROWS), dim3(256), dyn, s, e->nv,
-                       e->tv, e->wstream, num_simulations, sims_done, e->prof_buf, e->sp, 0, (uint64_t)e->cfg.seed, ra0);
-  } else {
-    if (!e->lds_attr_set) {
-      HIPCHECK(hipFuncSetAttribute((const void *)k_search_fused<KS1, JTP, G, LT, false, SP>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(float) * mz_fused_lds_floats(LT)));
-      e->lds_attr_set = true;
-    }
-    if (e->ev_start)      // timestamps of the dispatch itself (what rocprofv3's kernel trace reports), no launch gap inside
-      hipExtLaunchKernelGGL((k_search_fused<KS1, JTP, G, LT, false, SP>), dim3(e->Bp / MZ_ROWS), dim3(256), dyn, s,
-                            e->ev_start, e->ev_stop, 0, e->nv, e->tv, e->wstream, num_simulations, sims_done,
-                            (unsigned long long *)nullptr, e->sp, e->fuse_record ? 1 : 0, (uint64_t)e->cfg.seed, ra0);
-    else
-    hipLaunchKernelGGL((k_search_fused<KS1, JTP, G, LT, false, SP>), dim3(e->Bp / MZ_ROWS), dim3(256), dyn, s, e->nv,
-                       e->tv, e->wstream, num_simulations, sims_done, (unsigned long long *)nullptr, e->sp,
-                       e->fuse_record ? 1 : 0, (uint64_t)e->cfg.seed, ra0);
+    return fail("internal: no HEAD instantiation for this configuration");
   }
-  HIPCHECK(hipGetLastError());
+  if (std::find(e->lds_attr_done.begin(), e->lds_attr_done.end(), fn) == e->lds_attr_done.end()) {
+    HIPCHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MZ_LDS_BYTES - p.lds_static)));
+    e->lds_attr_done.push_back(fn);
+  }
+  // MZ_KARGS; a HEAD launch plays its moves from the root on (mz_root_body, on the LDS the trees are about to occupy)
+  const f32x4 *ws = p.fkind == 2 ? (const f32x4 *)e->packed_h2 : e->wstream;
+  int nsims = o.sims, slot0 = head ? 0 : o.sims_done, record = head || o.record ? 1 : 0;
+  unsigned long long *prof = o.prof;
+  uint64_t seed = e->cfg.seed;
+  MzRootArgs ra = {nullptr, 0, 1, 0.0, 0.0};
+  if (head) ra = {e->istream, e->nst0, o.moves, e->cfg.root_dirichlet_alpha, e->cfg.root_exploration_fraction};
+  void *args[] = {&e->nv, &e->tv, &ws, &nsims, &slot0, &prof, &e->sp, &record, &seed, &ra};
+  const dim3 grid(e->Bp / MZ_ROWS), block(256);
+  const size_t dyn = head ? p.dyn_head : p.dyn;
+  if (o.ev_start) (void)hipExtLaunchKernel(fn, grid, block, args, dyn, s, o.ev_start, o.ev_stop, 0);
+  else (void)hipLaunchKernel(fn, grid, block, args, dyn, s);
+  HIPCHECK(hipGetLastError());      // (this launch, or a k_tree_select issued just before it)
   return 0;
-}
-
-// the split-f16 variant (mz_fused_h2.hip.h): same arguments, its own weight stream and static LDS
-template <int G, int LT, bool SP>
-static int launch_h2_sp(mz_engine *e, int num_simulations, int sims_done, hipStream_t s) {
-  const size_t dyn = mz_fused_dyn_lds(e->sims, e->NN, LT);
-  const f32x4 *ws = (const f32x4 *)e->packed_h2;
-  const int maxdyn = 160 * 1024 - (int)sizeof(float) * mz_h2_lds_floats(LT);
-  const MzRootArgs ra0 = {nullptr, 0, 1, 0.0, 0.0};
-  if constexpr (SP) {
-    if (e->persist_moves > 0) {      // the self-play loop: persist_moves whole moves in this launch
-      const size_t dynh = fused_head_dyn_lds(e->sims, e->NN, LT);
-      const MzRootArgs ra = {e->istream, e->nst0, e->persist_moves, e->cfg.root_dirichlet_alpha,
-                             e->cfg.root_exploration_fraction};
-      if (!e->lds_attr_set_head) {
-        HIPCHECK(hipFuncSetAttribute((const void *)k_search_h2<G, LT, false, SP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxdyn));
-        e->lds_attr_set_head = true;
-      }
-      if (e->ev_start)
-        hipExtLaunchKernelGGL((k_search_h2<G, LT, false, SP, true>), dim3(e->Bp / MZ_ROWS), dim3(256), dynh, s, e->ev_start,
-                              e->ev_stop, 0, e->nv, e->tv, ws, num_simulations, 0, (unsigned long long *)nullptr, e->sp, 1,
-                              (uint64_t)e->cfg.seed, ra);
-      else
-        hipLaunchKernelGGL((k_search_h2<G, LT, false, SP, true>), dim3(e->Bp / MZ_ROWS), dim3(256), dynh, s, e->nv, e->tv, ws,
-                           num_simulations, 0, (unsigned long long *)nullptr, e->sp, 1, (uint64_t)e->cfg.seed, ra);
-      HIPCHECK(hipGetLastError());
-      return 0;
-    }
-  }
-  if (e->persist_moves > 0) return fail("internal: no HEAD instantiation for this configuration");
-  if (e->prof_buf) {
-    if (!e->lds_attr_set_prof) {
-      HIPCHECK(hipFuncSetAttribute((const void *)k_search_h2<G, LT, true, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, maxdyn));
-      e->lds_attr_set_prof = true;
-    }
-    hipLaunchKernelGGL((k_search_h2<G, LT, true, SP>), dim3(e->Bp / MZ_ROWS), dim3(256), dyn, s, e->nv, e->tv, ws,
-                       num_simulations, sims_done, e->prof_buf, e->sp, 0, (uint64_t)e->cfg.seed, ra0);
-  } else {
-    if (!e->lds_attr_set) {
-      HIPCHECK(hipFuncSetAttribute((const void *)k_search_h2<G, LT, false, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, maxdyn));
-      e->lds_attr_set = true;
-    }
-    if (e->ev_start)
-      hipExtLaunchKernelGGL((k_search_h2<G, LT, false, SP>), dim3(e->Bp / MZ_ROWS), dim3(256), dyn, s, e->ev_start,
-                            e->ev_stop, 0, e->nv, e->tv, ws, num_simulations, sims_done, (unsigned long long *)nullptr,
-                            e->sp, e->fuse_record ? 1 : 0, (uint64_t)e->cfg.seed, ra0);
-    else
-      hipLaunchKernelGGL((k_search_h2<G, LT, false, SP>), dim3(e->Bp / MZ_ROWS), dim3(256), dyn, s, e->nv, e->tv, ws,
-                         num_simulations, sims_done, (unsigned long long *)nullptr, e->sp, e->fuse_record ? 1 : 0,
-                         (uint64_t)e->cfg.seed, ra0);
-  }
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// -1: the split-f16 kernel does not apply (trees fit neither LDS placement beside its larger static LDS)
-template <int G>
-static int launch_h2(mz_engine *e, int num_simulations, int sims_done, hipStream_t s) {
-  if (!e->use_lds_trees) return -2;
-  const bool two = e->cfg.two_players != 0;
-  if (sizeof(float) * mz_h2_lds_floats(1) + mz_fused_dyn_lds(e->sims, e->NN, 1) <= 160 * 1024)
-    return two ? launch_h2_sp<G, 1, false>(e, num_simulations, sims_done, s) : launch_h2_sp<G, 1, true>(e, num_simulations, sims_done, s);
-  if (e->use_lds_hybrid && sizeof(float) * mz_h2_lds_floats(2) + mz_fused_dyn_lds(e->sims, e->NN, 2) <= 160 * 1024)
-    return two ? launch_h2_sp<G, 2, false>(e, num_simulations, sims_done, s) : launch_h2_sp<G, 2, true>(e, num_simulations, sims_done, s);
-  return -2;
-}
-
-// single-player games (every reference environment but TicTacToe) run the instantiation without to_play handling
-template <int KS1, int JTP, int G, int LT>
-static int launch_fused_lt(mz_engine *e, int num_simulations, int sims_done, hipStream_t s) {
-  return e->cfg.two_players ? launch_fused_sp<KS1, JTP, G, LT, false>(e, num_simulations, sims_done, s)
-                            : launch_fused_sp<KS1, JTP, G, LT, true>(e, num_simulations, sims_done, s);
-}
-
-// trees in LDS when 16 of them fit beside the kernel's static LDS (160 KiB per CU); if not, at least the fields the
-// descent reads (N, E, P, reward + discount * Q); else in the global pool
-template <int KS1, int JTP, int G>
-static int launch_fused_t(mz_engine *e, int num_simulations, int sims_done, hipStream_t s) {
-  if (e->use_lds_trees) {
-    if (sizeof(float) * mz_fused_lds_floats(1) + mz_fused_dyn_lds(e->sims, e->NN, 1) <= 160 * 1024)
-      return launch_fused_lt<KS1, JTP, G, 1>(e, num_simulations, sims_done, s);
-    if (e->use_lds_hybrid && sizeof(float) * mz_fused_lds_floats(2) + mz_fused_dyn_lds(e->sims, e->NN, 2) <= 160 * 1024)
-      return launch_fused_lt<KS1, JTP, G, 2>(e, num_simulations, sims_done, s);
-  }
-  return launch_fused_lt<KS1, JTP, G, 0>(e, num_simulations, sims_done, s);
-}
-
-// fused-kernel instantiations: (fc1 k-steps, policy tiles, lanes per tree) by action count
-// (dynamics fc1: K = 50 + A columns in k-steps of 4 -- the bias rides in the one-hot columns, fill_fc1_foldbias)
-static int fused_ks1(int A) { return A <= 6 ? 14 : (A <= 10 ? 15 : (A <= 13 ? 16 : (A <= 21 ? 18 : 21))); }
-
-static int launch_fused(mz_engine *e, int num_simulations, int sims_done, hipStream_t s) {
-  const int A = e->A;
-  if (e->split_f16) {
-    int rc = -2;
-    if (A <= 4) rc = launch_h2<4>(e, num_simulations, sims_done, s);
-    else if (A <= 8) rc = launch_h2<8>(e, num_simulations, sims_done, s);
-#ifndef MZ_DEV_ONLY
-    else rc = launch_h2<16>(e, num_simulations, sims_done, s);
-#endif
-    if (rc != -2) return rc;          // (-2: trees do not fit its LDS budget -> the exact-f32 kernel)
-  }
-#ifdef MZ_DEV_ONLY      // kernel development: only the two bench shapes are instantiated (a quarter of the build time)
-  if (A <= 4) return launch_fused_t<14, 1, 4>(e, num_simulations, sims_done, s);
-  if (A >= 5 && A <= 6) return launch_fused_t<14, 1, 8>(e, num_simulations, sims_done, s);
-  return fail("MZ_DEV_ONLY build: action_space %d not instantiated", A);
-#else
-  if (A <= 4) return launch_fused_t<14, 1, 4>(e, num_simulations, sims_done, s);
-  if (A <= 6) return launch_fused_t<14, 1, 8>(e, num_simulations, sims_done, s);
-  if (A <= 8) return launch_fused_t<15, 1, 8>(e, num_simulations, sims_done, s);
-  if (A <= 10) return launch_fused_t<15, 1, 16>(e, num_simulations, sims_done, s);
-  if (A <= 13) return launch_fused_t<16, 1, 16>(e, num_simulations, sims_done, s);
-  if (A <= 16) return launch_fused_t<18, 1, 16>(e, num_simulations, sims_done, s);
-  if (A <= 21) return launch_fused_t<18, 2, 32>(e, num_simulations, sims_done, s);
-  return launch_fused_t<21, 2, 32>(e, num_simulations, sims_done, s);
-#endif
-}
-
-// LDS placement of the trees the exact-f32 fused kernel will choose (launch_fused_t)
-static int fused_lt(const mz_engine *e) {
-  if (e->use_lds_trees) {
-    if (sizeof(float) * mz_fused_lds_floats(1) + mz_fused_dyn_lds(e->sims, e->NN, 1) <= 160 * 1024) return 1;
-    if (e->use_lds_hybrid && sizeof(float) * mz_fused_lds_floats(2) + mz_fused_dyn_lds(e->sims, e->NN, 2) <= 160 * 1024) return 2;
-  }
-  return 0;
-}
-// Can the self-play loop run as whole moves inside one launch (HEAD instantiation of the fused kernel)?
-static bool selfplay_persist_ok(const mz_engine *e) {
-  if (!e->use_persist || !fused_usable(e) || e->prof_buf) return false;
-  if (e->sp.env_kind == 1) {
-    // the device TicTacToe environment: whole moves inside the launch of the two-player <15, 1, 16> instantiation with
-    // its trees compact in LDS (the exact-f32 kernel; host-given uniforms / draws work there too)
-#ifdef MZ_DEV_ONLY
-    return false;
-#else
-    return !e->split_f16 && e->cfg.two_players && e->A > 8 && e->A <= 10 && fused_lt(e) == 2 &&
-           sizeof(float) * mz_fused_lds_floats(2) + fused_head_dyn_lds(e->sims, e->NN, 2) <= 160 * 1024;
-#endif
-  }
-  if (e->cfg.two_players || e->sp.env_kind) return false;
-  if (e->split_f16 && e->use_lds_trees) {      // the split-f16 kernel where it applies (launch_h2), else the exact one below
-    for (int lt = 1; lt <= (e->use_lds_hybrid ? 2 : 1); ++lt)
-      if (sizeof(float) * mz_h2_lds_floats(lt) + mz_fused_dyn_lds(e->sims, e->NN, lt) <= 160 * 1024)
-        return sizeof(float) * mz_h2_lds_floats(lt) + fused_head_dyn_lds(e->sims, e->NN, lt) <= 160 * 1024;
-  }
-  const int lt = fused_lt(e);
-  return lt != 0 && sizeof(float) * mz_fused_lds_floats(lt) + fused_head_dyn_lds(e->sims, e->NN, lt) <= 160 * 1024;
 }
 
 static int launch_root_priors(mz_engine *e, const int8_t *to_play, const uint8_t *legal, const double *priors,
@@ -927,16 +812,18 @@ static int launch_root_priors(mz_engine *e, const int8_t *to_play, const uint8_t
   return 0;
 }
 
-static int launch_search(mz_engine *e, int num_simulations, bool selection_valid, int sims_done, hipStream_t s) {
-  if (fused_usable(e) && !e->root_hidden_external) {
-    if (!selection_valid) TREE_LAUNCH(k_tree_select, s, e->tv);
-    return launch_fused(e, num_simulations, sims_done, s);
+// (o.ev_start / o.ev_stop also ride on the tree kernels' dispatches here, as they do on the fused kernel's)
+static int launch_search(mz_engine *e, const SearchOpts &o, bool selection_valid, hipStream_t s) {
+  const SearchPlan p = search_plan(e);
+  if (p.kind) {
+    if (!selection_valid) TREE_LAUNCH_EV(k_tree_select, s, o.ev_start, o.ev_stop, e->tv);
+    return launch_fused(e, p, o, s);
   }
-  for (int i = 0; i < num_simulations; ++i) {
-    if (!selection_valid) TREE_LAUNCH(k_tree_select, s, e->tv);
-    NET_LAUNCH(k_net_recurrent_tree, e->Bp / MZ_ROWS, s, e->nv, e->tv, sims_done + i + 1);
-    const int more = (i + 1 < num_simulations) ? 1 : 0;
-    TREE_LAUNCH(k_tree_step, s, e->tv, more);
+  for (int i = 0; i < o.sims; ++i) {
+    if (!selection_valid) TREE_LAUNCH_EV(k_tree_select, s, o.ev_start, o.ev_stop, e->tv);
+    NET_LAUNCH(k_net_recurrent_tree, e->Bp / MZ_ROWS, s, e->nv, e->tv, o.sims_done + i + 1);
+    const int more = (i + 1 < o.sims) ? 1 : 0;
+    TREE_LAUNCH_EV(k_tree_step, s, o.ev_start, o.ev_stop, e->tv, more);
     selection_valid = more;
   }
   HIPCHECK(hipGetLastError());
@@ -975,9 +862,9 @@ int mz_create(const mz_config *cfg, mz_engine **out) {
   e->sims = cfg->num_simulations;
   e->NN = 1 + (e->sims + 1) * e->A;
   e->PL = e->sims + 2;
-  e->G = e->A <= 4 ? 4 : (e->A <= 8 ? 8 : (e->A <= 16 ? 16 : 32));
-  e->jtp = e->A <= 16 ? 1 : 2;
-  e->ks1sel = fused_ks1(e->A);
+  e->shape = shape_for(g_fused_shapes, e->A);
+  e->G = e->shape->g;
+  e->jtp = e->shape->jtp;
   e->use_graph = getenv("MZ_NO_GRAPH") == nullptr;
   e->use_fused = getenv("MZ_NO_FUSED") == nullptr;
   e->use_persist = getenv("MZ_NO_PERSIST") == nullptr;
@@ -991,6 +878,7 @@ int mz_create(const mz_config *cfg, mz_engine **out) {
       return fail("mz_create: split_f16 supports action_space <= %d (got %d)", MZ_H2_MAXA, cfg->action_space);
     }
     e->split_f16 = want && cfg->action_space <= MZ_H2_MAXA;
+    if (e->split_f16) e->shape_h2 = shape_for(g_h2_shapes, e->A);
   }
   TreeView &t = e->tv;
   memset(&t, 0, sizeof t);
@@ -1366,7 +1254,7 @@ int mz_search(mz_engine *e, int num_simulations, void *stream) {
       if (e->search_graph) { hipGraphExecDestroy(e->search_graph); e->search_graph = nullptr; }
       hipGraph_t g = nullptr;
       HIPCHECK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-      int rc = launch_search(e, num_simulations, true, 0, e->cap_stream);
+      int rc = launch_search(e, {num_simulations}, true, e->cap_stream);
       hipError_t ce = hipStreamEndCapture(e->cap_stream, &g);
       if (rc || ce != hipSuccess) return fail("mz_search: graph capture failed");
       HIPCHECK(hipGraphInstantiate(&e->search_graph, g, nullptr, nullptr, 0));
@@ -1375,7 +1263,7 @@ int mz_search(mz_engine *e, int num_simulations, void *stream) {
     }
     HIPCHECK(hipGraphLaunch(e->search_graph, s));
   } else {
-    if (launch_search(e, num_simulations, e->selection_valid, e->sims_done, s)) return -1;
+    if (launch_search(e, {num_simulations, e->sims_done}, e->selection_valid, s)) return -1;
   }
   e->sims_done += num_simulations;
   e->selection_valid = false;
@@ -1388,14 +1276,8 @@ int mz_search(mz_engine *e, int num_simulations, void *stream) {
 // they mean to exercise.)
 int mz_search_kernel_info(const mz_engine *e, int *out4) {
   if (!e || !out4) return fail("mz_search_kernel_info: null argument");
-  int kind = 0, lt = -1;
-  if (fused_usable(e) && !e->root_hidden_external) {
-    kind = 1; lt = fused_lt(e);
-    if (e->split_f16 && e->use_lds_trees)
-      for (int l = 1; l <= (e->use_lds_hybrid ? 2 : 1); ++l)
-        if (sizeof(float) * mz_h2_lds_floats(l) + mz_fused_dyn_lds(e->sims, e->NN, l) <= 160 * 1024) { kind = 2; lt = l; break; }
-  }
-  out4[0] = kind; out4[1] = lt; out4[2] = e->ks1sel; out4[3] = e->G;
+  const SearchPlan p = search_plan(e);
+  out4[0] = p.kind; out4[1] = p.kind ? p.lt : -1; out4[2] = e->shape->ks1; out4[3] = e->G;
   return 0;
 }
 
@@ -1461,14 +1343,14 @@ int mz_search_timed(mz_engine *e, int num_simulations, float *ms_out, void *stre
     return fail("mz_search_timed: call right after mz_root_prepare");
   if (num_simulations < 1 || num_simulations > e->sims) return fail("mz_search_timed: bad num_simulations");
   hipStream_t s = (hipStream_t)stream;
-  HIPCHECK(hipEventCreate(&e->ev_start));
-  HIPCHECK(hipEventCreate(&e->ev_stop));
-  const int rc = launch_fused(e, num_simulations, 0, s);
+  SearchOpts o = {num_simulations};
+  HIPCHECK(hipEventCreate(&o.ev_start));
+  HIPCHECK(hipEventCreate(&o.ev_stop));
+  const int rc = launch_fused(e, search_plan(e), o, s);
   hipError_t se = hipStreamSynchronize(s);
   float ms = 0.f;
-  hipError_t te = (rc == 0 && se == hipSuccess) ? hipEventElapsedTime(&ms, e->ev_start, e->ev_stop) : hipErrorUnknown;
-  hipEventDestroy(e->ev_start); hipEventDestroy(e->ev_stop);
-  e->ev_start = e->ev_stop = nullptr;
+  hipError_t te = (rc == 0 && se == hipSuccess) ? hipEventElapsedTime(&ms, o.ev_start, o.ev_stop) : hipErrorUnknown;
+  hipEventDestroy(o.ev_start); hipEventDestroy(o.ev_stop);
   if (rc) return -1;
   if (se != hipSuccess || te != hipSuccess) return fail("mz_search_timed: %s", hipGetErrorString(se != hipSuccess ? se : te));
   *ms_out = ms;
@@ -1488,9 +1370,9 @@ int mz_search_phase_profile(mz_engine *e, int num_simulations, unsigned long lon
   unsigned long long *buf = nullptr;
   HIPCHECK(hipMalloc((void **)&buf, n * 8));
   HIPCHECK(hipMemsetAsync(buf, 0, n * 8, s));
-  e->prof_buf = buf;
-  int rc = launch_fused(e, num_simulations, 0, s);
-  e->prof_buf = nullptr;
+  SearchOpts o = {num_simulations};
+  o.prof = buf;
+  int rc = launch_fused(e, search_plan(e), o, s);
   if (rc) { hipFree(buf); return -1; }
   HIPCHECK(hipStreamSynchronize(s));
   std::vector<unsigned long long> h(n);
@@ -1551,11 +1433,8 @@ int mz_tree_pair_timed(mz_engine *e, const float *value, const float *reward, co
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   for (auto &x : ev) HIPCHECK(hipEventCreate(&x));
   const bool pending = e->selection_valid;      // (the root's own first descent: mz_root_prepare leaves it selected)
-  e->ev_start = ev[0]; e->ev_stop = ev[1];
-  if (!pending) TREE_LAUNCH(k_tree_select, s, e->tv);
-  e->ev_start = ev[2]; e->ev_stop = ev[3];
-  TREE_LAUNCH(k_tree_expand_backup, s, e->tv, value, reward, logits);
-  e->ev_start = e->ev_stop = nullptr;
+  if (!pending) TREE_LAUNCH_EV(k_tree_select, s, ev[0], ev[1], e->tv);
+  TREE_LAUNCH_EV(k_tree_expand_backup, s, ev[2], ev[3], e->tv, value, reward, logits);
   hipError_t le = hipGetLastError(), se = hipStreamSynchronize(s);
   int rc = 0;
   if (le != hipSuccess || se != hipSuccess) rc = fail("mz_tree_pair_timed: %s", hipGetErrorString(le != hipSuccess ? le : se));

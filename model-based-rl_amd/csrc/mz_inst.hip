@@ -1,5 +1,5 @@
 // mz_inst.hip -- one translation unit per search-kernel shape: compiled with -DMZ_INST_F=KS1,JTP,G (k_search_fused) or
-// -DMZ_INST_H=G (k_search_h2), it defines that shape's instantiations (mz_kernels.inc); mz_engine.hip launches them.
+// -DMZ_INST_H=G (k_search_h2), it defines every variant of that shape (mz_kernels.inc); mz_engine.hip launches them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mz_engine.h"
@@ -14,13 +14,15 @@
 #include "mz_fused_h2.hip.h"
 #include "mz_kernels.inc"
 
+#define MZ_KF(S, ...) template __global__ void k_search_fused<MZ_UNPACK S, __VA_ARGS__> MZ_KARGS;
+#define MZ_KH(S, ...) template __global__ void k_search_h2<MZ_UNPACK S, __VA_ARGS__> MZ_KARGS;
 #if defined(MZ_INST_F)
-MZ_APPLY(MZ_INST_FUSED, , MZ_INST_F)
-#ifdef MZ_INST_GAME      // (the <15, 1, 16> unit) whole moves of the device TicTacToe environment
-template __global__ void k_search_fused<15, 1, 16, 2, false, false, true, true> MZ_KARGS;
+MZ_VARIANTS_FUSED(MZ_KF, (MZ_INST_F))
+#ifdef MZ_INST_GAME      // (the unit of MZ_GAME_SHAPE) whole moves of the device TicTacToe environment
+MZ_GAME_VARIANT(MZ_KF)
 #endif
 #elif defined(MZ_INST_H)
-MZ_APPLY(MZ_INST_H2, , MZ_INST_H)
+MZ_VARIANTS_H2(MZ_KH, (MZ_INST_H))
 #else
 #error "compile with -DMZ_INST_F=KS1,JTP,G or -DMZ_INST_H=G"
 #endif

@@ -71,7 +71,7 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
 // observe, initial inference on that observation, Dirichlet draw over the legal actions (or the host's draw), root
 // expansion + first descent, the two-player search kernel, end of move with the real env.step -- all on the stream, no
 // host round trip; up to 16 moves per hipGraph like every other configuration.
-static int launch_move_game(mz_engine *e, hipStream_t s) {
+static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
   hipLaunchKernelGGL(k_ttt_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
@@ -79,31 +79,26 @@ static int launch_move_game(mz_engine *e, hipStream_t s) {
   if (!e->draws_noise)
     hipLaunchKernelGGL(k_dirichlet, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, (const uint8_t *)sp.legal,
                        e->cfg.root_dirichlet_alpha, e->cfg.seed, 0ull, (const unsigned long long *)sp.movecnt, sp.env_offset);
-  {
-    hipEvent_t a = e->ev_start, b = e->ev_stop;      // (a timed run clocks the search kernel's dispatch, not the root's)
-    e->ev_start = e->ev_stop = nullptr;
-    TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, (const double *)e->tv.noise,
-                e->cfg.root_exploration_fraction, 1);
-    e->ev_start = a; e->ev_stop = b;
-  }
-  if (launch_search(e, e->sims, true, 0, s)) return -1;
+  // (a timed run clocks the search kernel's dispatch, not the root's)
+  TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, (const double *)e->tv.noise,
+              e->cfg.root_exploration_fraction, 1);
+  if (launch_search(e, o, true, s)) return -1;
   hipLaunchKernelGGL(k_ttt_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
   HIPCHECK(hipGetLastError());
   return 0;
 }
 
-static int launch_move(mz_engine *e, hipStream_t s) {
+// o: the move's search (all simulations; mz_selfplay_steps_timed adds events around its dispatch)
+static int launch_move(mz_engine *e, SearchOpts o, hipStream_t s) {
   SelfplayState &sp = e->sp;
   const int B = e->B, O = e->O, A = e->A;
-  if (sp.env_kind) return launch_move_game(e, s);
+  if (sp.env_kind) return launch_move_game(e, o, s);
   // observation + initial inference + root expansion with Dirichlet noise + first descent: one launch
   if (launch_root(e, nullptr, true, s)) return -1;
   // search; the fused kernel also finalizes the move (action, visit distribution, env step, record) in its tail
   const bool fused = fused_usable(e);
-  e->fuse_record = fused;
-  const int rc = launch_search(e, e->sims, true, 0, s);
-  e->fuse_record = false;
-  if (rc) return -1;
+  o.record = fused;
+  if (launch_search(e, o, true, s)) return -1;
   if (!fused)
     hipLaunchKernelGGL(k_env_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, O, A, e->cfg.seed);
   HIPCHECK(hipGetLastError());
@@ -310,7 +305,7 @@ static int selfplay_order_behind_drain(mz_engine *e, int moves, hipStream_t s) {
   return 0;
 }
 
-static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, bool direct);
+static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, float *direct);
 
 // mz_selfplay_steps_into without touching the kernels (k_search_fused's register allocation is tuned to the last scratch byte:
 // a slot argument cost it 1 % of the headline): the kernels keep computing slot = move % ring_moves, and the host hands them a
@@ -329,7 +324,7 @@ static void selfplay_point_ring_at(mz_engine *e, float *dst, unsigned long long 
 int mz_selfplay_steps(mz_engine *e, int moves, void *stream) {
   if (!e) return fail("mz_selfplay_steps: null engine");
   MZ_ENTER(e);
-  return selfplay_steps_impl(e, moves, stream, false);
+  return selfplay_steps_impl(e, moves, stream, nullptr);
 }
 
 // The moves' records straight into the caller's pinned buffer: host_records [moves][B][rec_floats] is page-locked host
@@ -354,16 +349,15 @@ int mz_selfplay_steps_into(mz_engine *e, int moves, float *host_records, void *s
   if (sp.noise_log) return fail("mz_selfplay_steps_into: the Dirichlet log is indexed by ring slot (mz_selfplay_steps + mz_selfplay_drain)");
   float *ring = sp.ring;
   const int ring_moves = sp.ring_moves;
-  e->direct_records = (float *)dev;
-  const int rc = selfplay_steps_impl(e, moves, stream, true);
-  e->direct_records = nullptr;
+  const int rc = selfplay_steps_impl(e, moves, stream, (float *)dev);
   sp.ring = ring; sp.ring_moves = ring_moves;
   if (rc) return rc;
   sp.drained = sp.moves_host;
   return 0;
 }
 
-static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, bool direct) {
+// direct: device mapping of the caller's pinned record buffer (mz_selfplay_steps_into), or null (the device ring)
+static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, float *direct) {
   if (!e->sp.ready) return fail("mz_selfplay_steps: call mz_selfplay_reset first");
   if (!e->weights_set) return fail("mz_selfplay_steps: weights not set (call mz_set_weights)");
   SelfplayState &sp = e->sp;
@@ -384,22 +378,21 @@ static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, bool direc
   } partial{sp};
   // up to MZ_GRAPH_MOVES moves go out as ONE graph launch (one graph per distinct count, built on first use):
   // back-to-back nodes inside a graph start without a gap, between graph launches the GPU idles ~9 us
-  const bool persist = selfplay_persist_ok(e);
+  const bool persist = search_plan(e).persist;
   for (int left = moves; left > 0; partial.launched = moves - left) {
     const int k = left < MZ_GRAPH_MOVES ? left : MZ_GRAPH_MOVES;
-    if (direct) selfplay_point_ring_at(e, e->direct_records + (size_t)(moves - left) * e->B * sp.rec_floats,
+    if (direct) selfplay_point_ring_at(e, direct + (size_t)(moves - left) * e->B * sp.rec_floats,
                                        sp.moves_host + (unsigned long long)(moves - left), k);
     if (persist) {      // k whole moves inside one launch of the search kernel: no root kernel, no graph
-      e->persist_moves = k;
-      const int rc = launch_search(e, e->sims, true, 0, s);
-      e->persist_moves = 0;
-      if (rc) return -1;
+      SearchOpts o = {e->sims};
+      o.moves = k;
+      if (launch_search(e, o, true, s)) return -1;
       left -= k;
       continue;
     }
     if (direct) {       // (no graph: a captured one holds the device ring's address)
       for (int i = 0; i < k; ++i)
-        if (launch_move(e, s)) return -1;
+        if (launch_move(e, {e->sims}, s)) return -1;
       left -= k;
       continue;
     }
@@ -407,7 +400,7 @@ static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, bool direc
       hipGraph_t g = nullptr;
       HIPCHECK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
       int rc = 0;
-      for (int i = 0; i < k && !rc; ++i) rc = launch_move(e, e->cap_stream);
+      for (int i = 0; i < k && !rc; ++i) rc = launch_move(e, {e->sims}, e->cap_stream);
       hipError_t ce = hipStreamEndCapture(e->cap_stream, &g);
       if (rc || ce != hipSuccess) return fail("mz_selfplay_steps: graph capture failed");
       HIPCHECK(hipGraphInstantiate(&e->move_graph[k], g, nullptr, nullptr, 0));
@@ -417,7 +410,7 @@ static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, bool direc
       HIPCHECK(hipGraphLaunch(e->move_graph[k], s));
     } else {
       for (int i = 0; i < k; ++i)
-        if (launch_move(e, s)) return -1;
+        if (launch_move(e, {e->sims}, s)) return -1;
     }
     left -= k;
   }
@@ -431,7 +424,7 @@ static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, bool direc
 
 int mz_selfplay_moves_per_launch(const mz_engine *e) {
   if (!e) return -1;
-  return selfplay_persist_ok(e) ? MZ_GRAPH_MOVES : 0;
+  return search_plan(e).persist ? MZ_GRAPH_MOVES : 0;
 }
 int mz_selfplay_rec_floats(const mz_engine *e) { return e ? (e->sp.t ? e->sp.rec_floats : e->O + e->A + MZ_REC_EXTRA) : -1; }
 int mz_selfplay_ring_moves(const mz_engine *e) { return (e && e->sp.t) ? e->sp.ring_moves : -1; }
@@ -448,22 +441,23 @@ int mz_selfplay_steps_timed(mz_engine *e, int k, float *ms_out, void *stream) {
   if (selfplay_order_behind_drain(e, k, s)) return -1;
   // whole moves inside the launch (HEAD): one dispatch of up to MZ_GRAPH_MOVES moves, every move of it reported as
   // its share of the dispatch's duration
-  const bool persist = selfplay_persist_ok(e);
+  const bool persist = search_plan(e).persist;
   const int nl = persist ? (k + MZ_GRAPH_MOVES - 1) / MZ_GRAPH_MOVES : k;
   std::vector<hipEvent_t> ev(2 * (size_t)nl, nullptr);
   for (auto &x : ev) HIPCHECK(hipEventCreate(&x));
   int rc = 0;
   for (int i = 0; i < nl && !rc; ++i) {        // eager launches, back to back, no synchronisation in between
-    e->ev_start = ev[2 * i]; e->ev_stop = ev[2 * i + 1];
     if (persist) {
-      e->persist_moves = (k - i * MZ_GRAPH_MOVES) < MZ_GRAPH_MOVES ? (k - i * MZ_GRAPH_MOVES) : MZ_GRAPH_MOVES;
-      rc = launch_search(e, e->sims, true, 0, s);
-      e->persist_moves = 0;
+      SearchOpts o = {e->sims};
+      o.moves = (k - i * MZ_GRAPH_MOVES) < MZ_GRAPH_MOVES ? (k - i * MZ_GRAPH_MOVES) : MZ_GRAPH_MOVES;
+      o.ev_start = ev[2 * i]; o.ev_stop = ev[2 * i + 1];
+      rc = launch_search(e, o, true, s);
     } else {
-      rc = launch_move(e, s);
+      SearchOpts o = {e->sims};
+      o.ev_start = ev[2 * i]; o.ev_stop = ev[2 * i + 1];
+      rc = launch_move(e, o, s);
     }
   }
-  e->ev_start = e->ev_stop = nullptr;
   hipError_t se = hipStreamSynchronize(s);
   if (!rc && se == hipSuccess)
     for (int i = 0; i < nl; ++i) {
@@ -490,7 +484,7 @@ int mz_selfplay_phase_profile(mz_engine *e, int moves, double *cycles_out, void 
   if (!e || !cycles_out) return fail("mz_selfplay_phase_profile: null argument");
   if (!e->sp.ready) return fail("mz_selfplay_phase_profile: call mz_selfplay_reset first");
   if (!e->weights_set) return fail("mz_selfplay_phase_profile: weights not set (call mz_set_weights)");
-  if (!selfplay_persist_ok(e) || e->split_f16)
+  if (!search_plan(e).persist || e->split_f16)
     return fail("mz_selfplay_phase_profile: the self-play loop of this configuration does not run as whole moves in one launch of the exact-f32 kernel");
   if (moves < 1 || moves > MZ_GRAPH_MOVES ||
       (unsigned long long)moves > (unsigned long long)e->sp.ring_moves - (e->sp.moves_host - e->sp.drained))
@@ -501,11 +495,10 @@ int mz_selfplay_phase_profile(mz_engine *e, int moves, double *cycles_out, void 
   const size_t n = (size_t)(e->Bp / MZ_ROWS) * 4 * 8;
   unsigned long long *buf = nullptr;
   HIPCHECK(hipMalloc((void **)&buf, n * 8));
-  e->head_prof = buf;
-  e->persist_moves = moves;
-  const int rc = launch_search(e, e->sims, true, 0, s);
-  e->persist_moves = 0;
-  e->head_prof = nullptr;
+  SearchOpts o = {e->sims};
+  o.moves = moves;
+  o.prof = buf;
+  const int rc = launch_search(e, o, true, s);
   hipError_t se = hipStreamSynchronize(s);
   std::vector<unsigned long long> h(n);
   if (!rc && se == hipSuccess) se = hipMemcpy(h.data(), buf, n * 8, hipMemcpyDeviceToHost);
