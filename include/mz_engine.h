@@ -351,6 +351,15 @@ int mz_fcl_repack(mz_fcl *c, void *stream);
  *   or written with momentum 0), exp_avg_sq RMSprop's square_avg (SGD: not touched); the step counters advance as for Adam.
  *   Refuses an unknown kind, momentum < 0 and alpha outside [0, 1) (mz_last_error). */
 int mz_fcl_set_optimizer(mz_fcl *c, int kind, double momentum, double alpha);
+/* mz_fcl_set_scalar_loss: the loss family of the value and reward heads (utils.py:61-70, learners.py:182-206).  kind 0 = categorical
+ *   (the default: soft cross-entropy against the two-hot target), 1 = MSE (torch.nn.MSELoss), 2 = Huber (torch.nn.SmoothL1Loss,
+ *   beta 1), both reduction 'none': the reference's --no_support, where each of the two heads ends in ONE output trained against
+ *   the scalar target (transformed unless no_target_transform, never clamped) and the priority refresh is that raw output minus the
+ *   first value target.  The policy head stays categorical.  Kinds 1 and 2 need a handle created with value_support_min ==
+ *   value_support_max and reward_support_min == reward_support_max (one output per head); without this call such a handle is a
+ *   categorical one with one bin.  The kind holds for every later mz_fcl_step, mz_fcl_update and mz_fcl_run.  Refuses a null handle,
+ *   an unknown kind and kinds 1 / 2 on a handle with wider supports (mz_last_error). */
+int mz_fcl_set_scalar_loss(mz_fcl *c, int kind);
 int mz_fcl_step(mz_fcl *c, const float *obs, const void *actions, int actions_are_i32, const float *target_rewards, const float *target_values,
                 const float *target_policies, const void *is_weights, int weights_are_f64, double beta1, double beta2, double eps,
                 double weight_decay, double clip_grad, int adamw, int no_update, float *new_errors, double *loss_sums, void *stream);

@@ -170,6 +170,7 @@ SIGNATURES = {
     'mz_fcl_bind': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     'mz_fcl_repack': (_I, [_VP, _VP]),
     'mz_fcl_set_optimizer': (_I, [_VP, _I, _D, _D]),
+    'mz_fcl_set_scalar_loss': (_I, [_VP, _I]),
     'mz_fcl_step': (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _D, _D, _D, _D, _D, _I, _I, _VP, _VP, _VP]),
     'mz_fcl_update': (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _D, _D, _D, _D, _D, _I, _VP, _VP, C.POINTER(_I)]),
     'mz_fcl_errors': (_I, [_VP, _I, _VP]),

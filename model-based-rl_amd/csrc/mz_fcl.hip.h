@@ -66,6 +66,7 @@ struct FclView {
                                  // whose hidden state the units' d loss / d hidden belongs to): 3 = value, policy and the next position's reward unit; 2 at position K)
   unsigned *err;                 // [host, device-mapped] set to 1 where a unit's wait for its counter ran into its bound (never on a healthy box)
   float *steps; int nsteps;      // the optimiser's per-parameter step counters (torch keeps one per parameter), advanced by k_fcl_heads; nsteps = 0: not this step
+  int sloss;                     // scalar-loss kind of the value and reward heads (--no_support): 1 MSE, 2 Huber; read by the SC instantiations only
   unsigned long long *prof;      // development: s_memtime stamps of k_fcl_heads' phases (workgroup 0 of every head at position 1), else null
 };
 
@@ -328,7 +329,9 @@ __device__ __forceinline__ float fcl_max32(float x) {
 struct FclNothing { __device__ __forceinline__ void operator()() const {} };
 // requested: called once the unit's own first loads (biases, targets, fc1's weights, its inputs) are on their way -- k_fcl_fb's chain workgroups ask for
 // their backward pass's weights there (loads return in order: asked for in front of the unit, they held its first phase back 3 us)
-template <bool WAIT, bool SIGD = false, class F = FclNothing>
+// SC: the scalar-loss form (mz_fcl_set_scalar_loss; FclView::sloss: 1 MSE, 2 Huber) -- an instantiation of its own beside every categorical
+// one, so that the categorical kernels carry neither its branch nor its registers
+template <bool WAIT, bool SIGD = false, bool SC = false, class F = FclNothing>
 __device__ __forceinline__ void fcl_heads_body(const FclView &v, const int cb, const int p, const int hd, float *fcl_smem, F requested = F()) {
   float *X = fcl_smem, *A1 = X + 1024, *redf = A1 + 8192, *Y = redf + 8192, *S = Y + 1024, *PV = S + 1024;
   f32x4 *red = (f32x4 *)redf;
@@ -424,7 +427,32 @@ __device__ __forceinline__ void fcl_heads_body(const FclView &v, const int cb, c
   FCL_STAMP()      // 5: reduce + barrier
   // soft cross-entropy against the categorical target (utils.py:53-60; learners.py:186-203) and its gradient, 32 lanes per
   // sample, bins q and q + 32; the gradient of the weighted mean and the 1 / K hook (learners.py:205-212) ride in g
-  {
+  bool scalar_head = false;
+  if constexpr (SC) {
+    // --no_support (utils.py:61-70; learners.py:182-206): the value and reward heads end in ONE output y, trained against the (transformed,
+    // unclamped) scalar target with torch.nn.MSELoss / SmoothL1Loss (beta 1, comparison <), reduction 'none'; the policy head stays
+    // categorical.  Only element (0, n) of the gradient tile is not zero; the priority refresh is the RAW output against the untransformed
+    // first value target, as the reference has it
+    if (hd != 1) {
+      scalar_head = true;
+      const int n = n_s, q = q_s, row = row_s;
+      const float y = Y[fcl_at(0, n)], t = v.ntt ? ts : mzl_scalar_transform(ts), d = y - t;
+      float l = d * d, dl = 2.f * d;
+      if (v.sloss == 2) {
+        const bool quad = fabsf(d) < 1.f;
+        l = quad ? 0.5f * d * d : fabsf(d) - 0.5f;
+        dl = quad ? d : (d > 0.f ? 1.f : -1.f);
+      }
+      const float g = (float)(((1.0 / (double)v.K) / (double)v.bs) * wb);
+      S[fcl_at(q, n)] = q == 0 ? g * dl : 0.f;
+      S[fcl_at(q + 32, n)] = 0.f;
+      if (q == 0) {
+        v.lossb[hp * R + row] = l;
+        if (hd == 0 && p == 0) v.new_errors[row] = y - tv0;
+      }
+    }
+  }
+  if (!scalar_head) {
     const int n = n_s, q = q_s, row = row_s;
     const float x0 = in0 ? Y[fcl_at(q, n)] : -__builtin_inff(), x1 = in1 ? Y[fcl_at(q + 32, n)] : -__builtin_inff();
     if (hd != 1) {
@@ -504,6 +532,10 @@ __device__ __forceinline__ void fcl_heads_body(const FclView &v, const int cb, c
 __global__ __launch_bounds__(FCL_THREADS, 4) void k_fcl_heads(FclView v) {
   extern __shared__ __attribute__((aligned(16))) float fcl_smem[];
   fcl_heads_body<false>(v, blockIdx.x, blockIdx.y, blockIdx.z, fcl_smem);
+}
+__global__ __launch_bounds__(FCL_THREADS, 4) void k_fcl_heads_scalar(FclView v) {
+  extern __shared__ __attribute__((aligned(16))) float fcl_smem[];
+  fcl_heads_body<false, false, true>(v, blockIdx.x, blockIdx.y, blockIdx.z, fcl_smem);
 }
 
 // ------------------------------------------------------------------------------------------------ chain (4 samples per workgroup)
@@ -819,7 +851,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_fcl_chain_fwd4(FclView v) {
 // its weights, biases and targets in flight.  As two launches the heads started when the whole chain had ended, 272 units on 256 CUs
 // (a second round on 16 of them): 23.3 + 1.7 + 24.7 us; a unit never waits for anything but chain workgroups, which are resident
 // from the start of the launch: no deadlock however few units fit beside them.
-template <int KP>
+template <int KP, bool SC = false>
 __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fwd(FclView v, int nchain) {
   extern __shared__ __attribute__((aligned(16))) float fcl_smem[];
   if ((int)blockIdx.x < nchain) {
@@ -835,7 +867,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fwd(FclView v, int nchain) 
     const int r = u - (p - 1) * 3 * G;
     hd = r / G; cb = r - hd * G;
   }
-  fcl_heads_body<true>(v, cb, p, hd, fcl_smem);
+  fcl_heads_body<true, false, SC>(v, cb, p, hd, fcl_smem);
 }
 
 // WAITD: the chain workgroups of k_fcl_fb -- the backward pass follows the forward pass in the SAME workgroup, and the heads' d loss / d hidden
@@ -1440,7 +1472,7 @@ __device__ __forceinline__ void fcl_loss_block(const float *lossb, const void *w
 // (a chain workgroup that has finished its forward pass does not idle the ~13 us until its last position's units have finished: three of a
 // sample group's four chain workgroups run THOSE units themselves -- value, policy, reward of position K: no CU waits 17 us for them with
 // nothing to do -- and the fourth takes one of the other positions' units, which are handed out through a counter in position order)
-template <int KP, int OK = FCL_ADAM>
+template <int KP, int OK = FCL_ADAM, bool SC = false>
 __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fb(FclView v, int nchain, const FclJob *jobs, FclDw a) {
   extern __shared__ __attribute__((aligned(16))) float fcl_smem[];
   __shared__ int s_unit;
@@ -1480,7 +1512,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_fcl_fb(FclView v, int nchain, c
       if (u >= 2 * G) { u -= 2 * G; p = 1 + u / (3 * G); u -= (p - 1) * 3 * G; }
       hd = u / G; cb = u - hd * G;
     }
-    fcl_heads_body<true, true>(v, cb, p, hd, fcl_smem, preload);
+    fcl_heads_body<true, true, SC>(v, cb, p, hd, fcl_smem, preload);
   } else preload();
   if (v.prof && !chain && threadIdx.x == 0) atomicMax(v.prof + 65, (unsigned long long)__builtin_amdgcn_s_memrealtime());      // (the last unit's end)
   if (chain) {

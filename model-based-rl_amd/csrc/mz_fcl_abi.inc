@@ -30,6 +30,7 @@ struct mz_fcl {
   // mz_fcl_set_optimizer: FCL_ADAM (the default) / FCL_SGD / FCL_RMSPROP, momentum and RMSprop's alpha
   int opt_kind = FCL_ADAM;
   double opt_mom = 0.0, opt_alpha = 0.0;
+  int scalar_loss = 0;                     // mz_fcl_set_scalar_loss: 0 categorical (the default), 1 MSE, 2 Huber
   // mz_fcl_update: FCL_SLOTS pinned staging slots for a batch, its device copy, the new errors' way back
   char *stage_h[FCL_SLOTS] = {}, *stage_d = nullptr;
   size_t stage_bytes = 0, soff[6] = {0, 0, 0, 0, 0, 0};
@@ -283,7 +284,8 @@ int mz_fcl_create(int batch, int unroll_steps, int obs_dim, int action_space, in
       if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd_dw) != hipSuccess)
         return bail(fail("mz_fcl_create: %zu bytes of LDS per workgroup refused", c->lds_bwd_dw));
   }
-  if (hipFuncSetAttribute((const void *)k_fcl_heads, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess)
+  if (hipFuncSetAttribute((const void *)k_fcl_heads, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess ||
+      hipFuncSetAttribute((const void *)k_fcl_heads_scalar, hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess)
     return bail(fail("mz_fcl_create: %d bytes of LDS per workgroup refused", FCL_LDS_HEADS * 4));
   {
     // the fused forward launch: where the chain leaves at least half of the chip idle (batch <= 512 on 256 CUs: 107 against 115 us per
@@ -306,11 +308,17 @@ int mz_fcl_create(int batch, int unroll_steps, int obs_dim, int action_space, in
         hipHostGetDevicePointer((void **)&c->done_hd, c->done_h, 0) != hipSuccess || fcl_alloc(c, &c->done_ctr, (size_t)16))
       return bail(fail("mz_fcl_create: pinned completion words refused"));
     memset(c->done_h, 0, FCL_SLOTS * 64);
-    const void *fn[12] = {(const void *)k_fcl_fwd<56>, (const void *)k_fcl_fwd<64>, (const void *)k_fcl_fb<56, FCL_ADAM>, (const void *)k_fcl_fb<64, FCL_ADAM>,
+    const void *fn[24] = {(const void *)k_fcl_fwd<56>, (const void *)k_fcl_fwd<64>, (const void *)k_fcl_fb<56, FCL_ADAM>, (const void *)k_fcl_fb<64, FCL_ADAM>,
                           (const void *)k_fcl_fb<56, FCL_SGD>, (const void *)k_fcl_fb<64, FCL_SGD>, (const void *)k_fcl_fb<56, FCL_SGD | FCL_MOM>,
                           (const void *)k_fcl_fb<64, FCL_SGD | FCL_MOM>, (const void *)k_fcl_fb<56, FCL_RMSPROP>, (const void *)k_fcl_fb<64, FCL_RMSPROP>,
-                          (const void *)k_fcl_fb<56, FCL_RMSPROP | FCL_MOM>, (const void *)k_fcl_fb<64, FCL_RMSPROP | FCL_MOM>};
-    for (int i = 0; i < 12; ++i)
+                          (const void *)k_fcl_fb<56, FCL_RMSPROP | FCL_MOM>, (const void *)k_fcl_fb<64, FCL_RMSPROP | FCL_MOM>,
+                          // (their scalar-loss siblings: mz_fcl_set_scalar_loss)
+                          (const void *)k_fcl_fwd<56, true>, (const void *)k_fcl_fwd<64, true>, (const void *)k_fcl_fb<56, FCL_ADAM, true>,
+                          (const void *)k_fcl_fb<64, FCL_ADAM, true>, (const void *)k_fcl_fb<56, FCL_SGD, true>, (const void *)k_fcl_fb<64, FCL_SGD, true>,
+                          (const void *)k_fcl_fb<56, FCL_SGD | FCL_MOM, true>, (const void *)k_fcl_fb<64, FCL_SGD | FCL_MOM, true>,
+                          (const void *)k_fcl_fb<56, FCL_RMSPROP, true>, (const void *)k_fcl_fb<64, FCL_RMSPROP, true>,
+                          (const void *)k_fcl_fb<56, FCL_RMSPROP | FCL_MOM, true>, (const void *)k_fcl_fb<64, FCL_RMSPROP | FCL_MOM, true>};
+    for (int i = 0; i < 24; ++i)
       if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, FCL_LDS_HEADS * 4) != hipSuccess)
         return bail(fail("mz_fcl_create: %d bytes of LDS per workgroup refused", FCL_LDS_HEADS * 4));
   }
@@ -391,6 +399,17 @@ int mz_fcl_set_optimizer(mz_fcl *c, int kind, double momentum, double alpha) {
   return 0;
 }
 
+int mz_fcl_set_scalar_loss(mz_fcl *c, int kind) {
+  if (!c) return fail("mz_fcl_set_scalar_loss: null argument");
+  if (kind < 0 || kind > 2) return fail("mz_fcl_set_scalar_loss: unknown loss kind %d (0 categorical, 1 MSE, 2 Huber)", kind);
+  if (kind != 0 && (c->view.Sv != 1 || c->view.Sr != 1))
+    return fail("mz_fcl_set_scalar_loss: a scalar loss needs a handle created with one output per head (value_support_min == value_support_max, "
+                "reward_support_min == reward_support_max); this one has %d value and %d reward bins", c->view.Sv, c->view.Sr);
+  c->scalar_loss = kind;
+  fcl_drop_run_graphs(c);
+  return 0;
+}
+
 int mz_fcl_repack(mz_fcl *c, void *stream) {
   if (!c || !c->P) return fail("mz_fcl_repack: no parameters bound");
   FCL_ENTER(c);
@@ -439,6 +458,7 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
   const int K1 = c->K + 1;
   const bool clip = clip_grad > 0.0;
   v.steps = c->steps; v.nsteps = no_update ? 0 : c->nsteps;
+  v.sloss = c->scalar_loss;
   FclOpt o;
   o.beta1 = beta1; o.beta2 = beta2; o.eps = eps; o.wd = weight_decay; o.clip = (float)clip_grad;
   o.adamw = adamw ? 1 : 0; o.no_update = no_update ? 1 : 0;
@@ -457,22 +477,24 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
   const int nchain_jobs = c->njobs - c->njobs_heads;
   const int lds_dwa = FCL_DW_LDS(FCL_NW, 1, 4) > 3 * 256 * 8 ? FCL_DW_LDS(FCL_NW, 1, 4) : 3 * 256 * 8;
   // the launches, with the optimiser kind's instantiation of every kernel that updates weights
-  auto launches = [&](auto kind) {
+  // and, for a handle in scalar-loss mode, the scalar instantiation of every kernel that runs heads units
+  auto launches = [&](auto kind, auto scalar) {
   constexpr int OK = decltype(kind)::value;
+  constexpr bool SC = decltype(scalar)::value;
   if (c->fuse_fb) {
     // batch <= 256: TWO launches -- forward chain, heads and backward chain (k_fcl_fb); every weight-gradient job with Adam in its
     // workgroup, the LayerNorm parameters and the loss sums (k_fcl_dwa)
     const int units = (c->bs / 16) * (3 * c->K - 1);      // (position K's units run in the chain workgroups)
     const int inl = c->fb_jobs ? c->njobs_heads : 0;        // the heads' jobs inside k_fcl_fb (MZ_FCL_FB_JOBS=0: in the last launch, A/B)
-    if (v.tr.ks1 == 56) hipLaunchKernelGGL((k_fcl_fb<56, OK>), dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
-    else hipLaunchKernelGGL((k_fcl_fb<64, OK>), dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
+    if (v.tr.ks1 == 56) hipLaunchKernelGGL((k_fcl_fb<56, OK, SC>), dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
+    else hipLaunchKernelGGL((k_fcl_fb<64, OK, SC>), dim3(c->nwg + units + inl), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg, (const FclJob *)c->jobs, a);
     hipLaunchKernelGGL((k_fcl_dwa<10, 2, OK>), dim3(c->njobs - inl + (a.fuse ? 2 : 0)), dim3(FCL_THREADS), lds_dwa, s, (const FclJob *)c->jobs + inl, c->njobs - inl, a, a.fuse,
                        (const float *)c->lnpart, c->nln, c->L.ln_w, (const float *)v.lossb, is_weights, v.w_f64, c->bs, K1, loss_sums,
                        c->njobs_heads - inl, c->flags, v.nflags, c->done_ctr, dflag, seq);
   } else if (c->fuse_fwd) {
     const int units = (c->bs / 16) * (3 * K1 - 1);
-    if (v.tr.ks1 == 56) hipLaunchKernelGGL(k_fcl_fwd<56>, dim3(c->nwg + units), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg);
-    else hipLaunchKernelGGL(k_fcl_fwd<64>, dim3(c->nwg + units), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg);
+    if (v.tr.ks1 == 56) hipLaunchKernelGGL((k_fcl_fwd<56, SC>), dim3(c->nwg + units), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg);
+    else hipLaunchKernelGGL((k_fcl_fwd<64, SC>), dim3(c->nwg + units), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v, c->nwg);
   } else {
     const bool k56 = v.tr.ks1 == 56;
     if (c->G == 1) { if (k56) hipLaunchKernelGGL((k_fcl_chain_fwd4<56, 1>), dim3(c->nwg), dim3(FCL_THREADS), c->lds_bytes, s, v);
@@ -481,7 +503,7 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
                           else hipLaunchKernelGGL((k_fcl_chain_fwd4<64, 2>), dim3(c->nwg), dim3(FCL_THREADS), c->lds_bytes, s, v); }
     else { if (k56) hipLaunchKernelGGL((k_fcl_chain_fwd4<56, 4>), dim3(c->nwg), dim3(FCL_THREADS), c->lds_bytes, s, v);
            else hipLaunchKernelGGL((k_fcl_chain_fwd4<64, 4>), dim3(c->nwg), dim3(FCL_THREADS), c->lds_bytes, s, v); }
-    hipLaunchKernelGGL(k_fcl_heads, dim3(c->bs / 16, K1, 3), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v);
+    hipLaunchKernelGGL(SC ? k_fcl_heads_scalar : k_fcl_heads, dim3(c->bs / 16, K1, 3), dim3(FCL_THREADS), FCL_LDS_HEADS * 4, s, v);
   }
   if (c->fuse_fb) {
   } else if (c->S == 1) {
@@ -515,11 +537,15 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
   }
   };
   const bool mom = c->opt_mom != 0.0;
-  if (c->opt_kind == FCL_SGD && mom) launches(std::integral_constant<int, FCL_SGD | FCL_MOM>{});
-  else if (c->opt_kind == FCL_SGD) launches(std::integral_constant<int, FCL_SGD>{});
-  else if (c->opt_kind == FCL_RMSPROP && mom) launches(std::integral_constant<int, FCL_RMSPROP | FCL_MOM>{});
-  else if (c->opt_kind == FCL_RMSPROP) launches(std::integral_constant<int, FCL_RMSPROP>{});
-  else launches(std::integral_constant<int, FCL_ADAM>{});
+  auto by_loss = [&](auto kind) {
+    if (c->scalar_loss) launches(kind, std::true_type{});
+    else launches(kind, std::false_type{});
+  };
+  if (c->opt_kind == FCL_SGD && mom) by_loss(std::integral_constant<int, FCL_SGD | FCL_MOM>{});
+  else if (c->opt_kind == FCL_SGD) by_loss(std::integral_constant<int, FCL_SGD>{});
+  else if (c->opt_kind == FCL_RMSPROP && mom) by_loss(std::integral_constant<int, FCL_RMSPROP | FCL_MOM>{});
+  else if (c->opt_kind == FCL_RMSPROP) by_loss(std::integral_constant<int, FCL_RMSPROP>{});
+  else by_loss(std::integral_constant<int, FCL_ADAM>{});
   HIPCHECK(hipGetLastError());
   return 0;
 }

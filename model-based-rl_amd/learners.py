@@ -181,6 +181,7 @@ class _NativeFC(object):
   graph capture's restore) is noticed through the parameters' version counters and repacked (sync)."""
 
   ADAM, SGD, RMSPROP = 0, 1, 2          # mz_fcl_set_optimizer's kinds
+  SCALAR_LOSS = {'MSE': 1, 'Huber': 2}  # mz_fcl_set_scalar_loss's kinds under --no_support (0: categorical)
 
   @staticmethod
   def kind_of(optimizer):
@@ -203,7 +204,7 @@ class _NativeFC(object):
     cfg, net = learner.config, learner.network
     if learner.device.type != 'cuda' or not isinstance(net, FCNetwork) or getattr(cfg, 'no_native_learner', False):
       return False
-    if getattr(cfg, 'no_support', False):
+    if getattr(cfg, 'no_support', False) and getattr(cfg, 'scalar_loss', 'MSE') not in _NativeFC.SCALAR_LOSS:
       return False
     name = getattr(cfg, 'optimizer', 'AdamW')
     if name in ('AdamW', 'Adam'):
@@ -230,10 +231,15 @@ class _NativeFC(object):
     self.bs, self.K = host['obs'].shape[0], host['act'].shape[1]
     self.shape = {k: host[k].shape for k in _GraphedUpdate.ORDER}
     self.h = C.c_void_p()
+    # --no_support: one output per head (supports (0, 0)), trained with the scalar loss (utils.py:61-70)
+    no_support = bool(getattr(cfg, 'no_support', False))
+    sup = (0, 0, 0, 0) if no_support else (int(cfg.value_support_min), int(cfg.value_support_max), int(cfg.reward_support_min),
+                                           int(cfg.reward_support_max))
     with torch.cuda.device(dev):
-      _abi.check(self.lib.mz_fcl_create(self.bs, self.K, host['obs'].shape[1], net.action_space, int(cfg.value_support_min),
-                                        int(cfg.value_support_max), int(cfg.reward_support_min), int(cfg.reward_support_max),
+      _abi.check(self.lib.mz_fcl_create(self.bs, self.K, host['obs'].shape[1], net.action_space, sup[0], sup[1], sup[2], sup[3],
                                         int(bool(cfg.no_target_transform)), C.byref(self.h)), 'mz_fcl_create')
+    if no_support:
+      _abi.check(self.lib.mz_fcl_set_scalar_loss(self.h, self.SCALAR_LOSS[getattr(cfg, 'scalar_loss', 'MSE')]), 'mz_fcl_set_scalar_loss')
     g = opt.param_groups[0]
     mom = float(g.get('momentum', 0.0) or 0.0) if self.kind != self.ADAM else 0.0
     _abi.check(self.lib.mz_fcl_set_optimizer(self.h, self.kind, mom, float(g.get('alpha', 0.0)) if self.kind == self.RMSPROP else 0.0),
@@ -646,7 +652,7 @@ class Learner(Logger):
     # kernels on a CPU learner and with --no_hip_learner_ops
     self.hip_ops = self.device.type == 'cuda' and not getattr(config, 'no_hip_learner_ops', False)
     self._graph = None          # _GraphedUpdate, built from the first batch
-    self._native = None         # _NativeFC (FCNetwork, Adam / AdamW / SGD / RMSprop, categorical losses), built from the first batch
+    self._native = None         # _NativeFC (FCNetwork, Adam / AdamW / SGD / RMSprop, categorical or --no_support scalar losses), built from the first batch
     self._source = None         # _BatchSource while learn() runs
     self._pending = None        # (idxs, slot) of the update whose priority refresh has not reached the replay yet
     self.native_loop_updates = 0      # updates taken by mz_fcl_run (the loop body in native code)
@@ -1007,7 +1013,7 @@ class Learner(Logger):
     replay = getattr(self.replay_buffer, '_obj', self.replay_buffer)
     return (self.device.type == 'cuda' and (self.use_graph or self.native_only) and isinstance(self.network, FCNetwork) and hasattr(replay, '_h') and
             hasattr(replay, 'sample_batches_arrays') and not getattr(cfg, 'no_native_learner', False) and
-            not getattr(cfg, 'no_native_loop', False) and not getattr(cfg, 'no_support', False))
+            not getattr(cfg, 'no_native_loop', False))
 
   def _native_segment(self, cfg, last, log_every):
     """-> how many updates mz_fcl_run may take from here: up to the next step at which the loop does something in Python

@@ -4,7 +4,9 @@
 on the same GPU -- then the trained network's MCTS agent (temperature 0, no exploration noise) against a uniformly random
 opponent on the host's TicTacToe rules, 512 games as each side, next to the untrained network.
 
-  python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--out profiles/r03_tictactoe_learning.json]"""
+  python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
+                                       [--out profiles/r03_tictactoe_learning.json]
+--no_support adds the flag (scalar value / reward heads, MSE or Huber loss) to the recipe, for training and for the matches."""
 import argparse, json, os, sys, time, types
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,12 +14,12 @@ sys.path.insert(0, ROOT)
 LINES = np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8], [0, 3, 6], [1, 4, 7], [2, 5, 8], [0, 4, 8], [2, 4, 6]])
 
 
-def play_vs_random(weights, agent_side, games=512, sims=30, seed=0):
+def play_vs_random(weights, agent_side, games=512, sims=30, seed=0, no_support=False):
   """agent (MCTS, T = 0, no noise) vs a uniformly random opponent, `games` boards in lock-step through the stepwise ABI;
   returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second."""
   from model_based_rl_amd.engine import Engine
   rng = np.random.RandomState(seed)
-  eng = Engine(games, 9, 9, sims, two_players=True, known_bounds=(-1.0, 1.0), discount=1.0, seed=seed)
+  eng = Engine(games, 9, 9, sims, two_players=True, known_bounds=(-1.0, 1.0), discount=1.0, seed=seed, no_support=no_support)
   eng.set_weights(weights)
   board = np.zeros((games, 9), np.int64); turn = np.ones(games, np.int64); live = np.ones(games, bool)
   result = np.zeros(games, np.int64)          # +1 agent won, -1 agent lost, 0 draw
@@ -54,6 +56,8 @@ def main():
   ap.add_argument('--training_steps', type=int, default=3000)
   ap.add_argument('--num_envs', type=int, default=1024)
   ap.add_argument('--out', default=None)
+  ap.add_argument('--no_support', action='store_true')
+  ap.add_argument('--scalar_loss', default='MSE', choices=['MSE', 'Huber'])
   a = ap.parse_args()
   from model_based_rl_amd import train
   from model_based_rl_amd.config import make_config
@@ -61,9 +65,11 @@ def main():
   from model_based_rl_amd.engine import flatten_weights
   base = ['--environment', 'TicTacToe', '--two_players', '--architecture', 'FCNetwork', '--td_steps', '10', '--discount', '1',
           '--known_bounds', '-1', '1', '--num_simulations', '30', '--seed', '0', '--num_envs', str(a.num_envs)]
+  if a.no_support:
+    base += ['--no_support', '--scalar_loss', a.scalar_loss]
   torch.manual_seed(0)
   untrained = flatten_weights(get_network(make_config(base), torch.device('cpu')).state_dict())
-  before = {side: play_vs_random(untrained, side) for side in (1, -1)}
+  before = {side: play_vs_random(untrained, side, no_support=a.no_support) for side in (1, -1)}
   saves = os.path.join('/tmp', 'mz_ttt_learning_%d' % os.getpid())
   t0 = time.time()
   thr = train.main(base + ['--max_moves', '-1', '--training_steps', str(a.training_steps), '--stored_before_train', '20000',
@@ -75,7 +81,7 @@ def main():
   ck = sorted(glob.glob(os.path.join(saves, '**', 'saves', '*'), recursive=True), key=os.path.getmtime)[-1]
   state = torch.load(ck, map_location='cpu', weights_only=False)
   trained = flatten_weights(state['weights'])
-  after = {side: play_vs_random(trained, side) for side in (1, -1)}
+  after = {side: play_vs_random(trained, side, no_support=a.no_support) for side in (1, -1)}
   out = {'recipe': ' '.join(base), 'training_steps': int(state['training_step']), 'train_seconds': seconds,
          'selfplay_frames': thr['frames'], 'selfplay_games': thr['games'], 'learner': thr.get('learner'),
          'vs_random_512_games': {'untrained': {'agent_first (win, draw, loss)': before[1], 'agent_second': before[-1]},
