@@ -289,7 +289,15 @@ int mz_selfplay_set_moves(mz_engine *e, unsigned long long moves);
  * 1: TicTacToe with the reference's rules (custom_environments/tic_tac_toe.py:5-76: observation turn * board, legal =
  * empty cells, reward 1 for the winning move, done on a win or after nine moves, players alternate) entirely on the device;
  * needs obs_dim 9, action_space 9, two_players.  mz_selfplay_reset's episode_len / stagger are ignored (real games).
- * mz_selfplay_set_draws (game environments only): the Dirichlet draw (noise [dev][B][A] float64 at the legal positions,
+ * 2: CartPole (envs.CartPole, the definition of CartPole-v1 / -v0 here: float64 state (x, x_dot, theta, theta_dot), Euler
+ * step of 0.02 s with sin / cos as fixed polynomials so that host and device agree bit for bit, observation = the state as
+ * float32, reward 1 per step, done outside |x| <= 2.4, |theta| <= 12 degrees or when the step count reaches the time limit)
+ * entirely on the device; needs obs_dim 4, action_space 2 and a single player.  mz_selfplay_reset's episode_len is the time
+ * limit (500 / 200); every environment starts episode 0 at step 0 (stagger is ignored), episode k of environment i from the
+ * counter-RNG state mz_cartpole_reset_state(i, k) (mz_engine_debug.h).  With the exact-f32 kernel the moves run inside the
+ * whole-moves launch (the state lives in LDS across its moves); with split_f16 or MZ_NO_PERSIST as one launch per step of a
+ * move.  --norm_obs and byte observations (mz_selfplay_set_obs) are refused for it.
+ * mz_selfplay_set_draws (TicTacToe only): the Dirichlet draw (noise [dev][B][A] float64 at the legal positions,
  * mcts.py:59) and / or the uniform of select_action (uniform [dev][B] float64, config.py:77) of the following moves come
  * from the caller -- numpy's stream in the reference's order -- instead of the device RNG; NULL, NULL switches back. */
 int mz_selfplay_set_env(mz_engine *e, int kind);

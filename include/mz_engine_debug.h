@@ -108,6 +108,15 @@ int mz_selfplay_phase_profile(mz_engine *e, int moves, double *cycles_out, void 
 /* observation the synthetic env would emit for (env, episode, t): [host] out[obs_dim]; and reward */
 int mz_synth_obs(const mz_engine *e, int env, int episode, int t, float *out_obs, float *out_reward);
 
+/* The device CartPole environment (mz_selfplay_set_env kind 2).  mz_cartpole_reset_state: out [host][4] = the float64 state
+ * episode `episode` of (global) environment `env` starts from -- the counter RNG keyed (seed, env, episode), the same
+ * integer code on host and device, so a test can start a host envs.CartPole where the device started.
+ * mz_selfplay_env_state: out [host][B][4] = the environments' current states (synchronous).  mz_selfplay_set_env_state:
+ * state [host][4] replaces environment env's (after mz_selfplay_reset; synchronous): a test starts next to a threshold. */
+int mz_cartpole_reset_state(const mz_engine *e, int env, int episode, double *out);
+int mz_selfplay_env_state(mz_engine *e, double *out);
+int mz_selfplay_set_env_state(mz_engine *e, int env, const double *state);
+
 #ifdef __cplusplus
 }
 #endif

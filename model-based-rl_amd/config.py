@@ -150,9 +150,11 @@ def build_parser():
   return p
 
 
+CARTPOLE_TIME_LIMITS = {'CartPole-v1': 500, 'CartPole-v0': 200}      # (envs.CartPole.max_episode_steps)
 ENV_SHAPES = {   # (action_space, obs_space) of the environments the reference's README runs
     'TicTacToe': (9, (9,)), 'LunarLander-v2': (4, (8,)), 'Pong-ramNoFrameskip-v4': (6, (128,)),
     'Breakout-ramNoFrameskip-v4': (4, (128,)),
+    'CartPole-v1': (2, (4,)), 'CartPole-v0': (2, (4,)),      # envs.CartPole, on the device too (csrc/mz_selfplay.hip.h)
     # image observations of the Atari wrappers (wrappers.py:422-444: 96x96 uint8 frames) -- what MuZeroNetwork /
     # TinyNetwork take (SURVEY.md s7 on BASELINE configs[4]).  The channel count is NOT a property of the environment:
     # utils.py:27-35 builds the network with input_channels = stack_obs, doubled with --stack_actions (None below;
@@ -186,6 +188,8 @@ def make_config(argv=None, **overrides):
     cfg.action_space, cfg.obs_space = env_shapes(cfg)   # train.py:66-68 probes the env for these
   if not hasattr(cfg, 'obs_u8'):
     cfg.obs_u8 = obs_are_bytes(cfg)
+  if cfg.environment in CARTPOLE_TIME_LIMITS:      # gym's TimeLimit: the episode length is the environment's, not a flag
+    cfg.episode_length = cfg.max_episode_steps = CARTPOLE_TIME_LIMITS[cfg.environment]
   return cfg
 
 

@@ -512,8 +512,10 @@ __host__ __device__ inline size_t mz_fused_dyn_lds(int sims, int NN, int lt) {
 // Game.store_search_statistics, root error, Game.apply on the synthetic env and the experience record
 // (the stand-alone k_env_step_record does the same from the global pool).  Lane a stages child a's visit count
 // in LDS, lane 0 then runs the reference's sequential arithmetic (mz_sample_index) on the staged vector.
-// GAME: the environment is the device TicTacToe (mz_ttt_apply) instead of the synthetic one; the uniform may be the host's.
-template <int TL, int LT, bool GAME = false>
+// GAME 1: the environment is the device TicTacToe (mz_ttt_apply) instead of the synthetic one; the uniform may be the host's.
+// GAME 2: the device CartPole (mz_cartpole_apply) on the four float64 state words of envs[8..15]; the record's observation
+// is their float cast, read by lanes 0..3 before lane 0 steps them.
+template <int TL, int LT, int GAME = 0>
 __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const TreeMem<LT> &tm, const SelfplayState &sp,
                                                    int b, int lane, uint32_t legal, uint64_t seed, double *stage,
                                                    int O, int *envs = nullptr) {
@@ -532,7 +534,10 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
   const unsigned long long move = envs ? *(const unsigned long long *)envs : sp.movecnt[b];
   float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * t.B + b) * sp.rec_floats;
   const int OS = sp.obs_slots;       // float slots of the observation in the record (O, or ceil(O / 4) for packed bytes)
-  if (envs && O <= MZ_ENVW - 8 && sp.obs_u8 != 2) { if (lane < O) rec[lane] = ((const float *)envs)[8 + lane]; }
+  // (lanes 0..3 read the LDS words lane 0 overwrites further down, with no barrier between: the TL lanes of a tree share a
+  // wavefront and the read precedes the write in program order -- as for the synthetic environment's copy below)
+  if constexpr (GAME == 2) { if (lane < 4) rec[lane] = (float)((const double *)(envs + 8))[lane]; }
+  else if (envs && O <= MZ_ENVW - 8 && sp.obs_u8 != 2) { if (lane < O) rec[lane] = ((const float *)envs)[8 + lane]; }
   else for (int k = lane; k < OS; k += TL) rec[k] = mz_rec_obs_slot(sp, sp.obs + (size_t)b * O, O, k);
   if (lane < A) rec[OS + lane] = (float)(ok ? (double)c / (double)sumv : 0.0);
   if (lane == 0) {
@@ -543,12 +548,29 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
     const uint32_t env = (uint32_t)(sp.env_offset + b);
     const mz_u4 r = mz_philox(seed, env, (uint32_t)move, (uint32_t)(move >> 32), MZ_RNG_ACTION << 24);
     double u = mz_u01(r.x, r.y);
-    if constexpr (GAME) { if (sp.draw_uniform) u = sp.draw_uniform[b]; }
+    if constexpr (GAME == 1) { if (sp.draw_uniform) u = sp.draw_uniform[b]; }
     const int idx = mz_sample_index(d, n, envs ? *(const double *)(envs + 4) : sp.temp[b], u);
     const int action = acts[idx];
-    if constexpr (GAME) {
+    if constexpr (GAME == 1) {
       mz_ttt_apply(sp, b, action, rv, err, rec, A);
       sp.movecnt[b] = move + 1ull;
+      return;
+    }
+    if constexpr (GAME == 2) {
+      const int tt = envs[2], ep = envs[3];
+      double *ev = (double *)(envs + 8);
+      double st[4] = {ev[0], ev[1], ev[2], ev[3]};
+      const int done = mz_cartpole_apply(sp, b, action, rv, err, rec, A, st, tt, ep, seed);
+      for (int k = 0; k < 4; ++k) { ev[k] = st[k]; sp.cart[(size_t)b * 4 + k] = st[k]; }
+      if (done) {      // the next game starts: its temperature is evaluated now (actors.py:128-129)
+        const double tn = *sp.temp_next;
+        sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = tn;
+        envs[2] = 0; envs[3] = ep + 1; *(double *)(envs + 4) = tn;
+      } else {
+        sp.t[b] = tt + 1; envs[2] = tt + 1;
+      }
+      sp.movecnt[b] = move + 1ull;
+      *(unsigned long long *)envs = move + 1ull;
       return;
     }
     const int tt = envs ? envs[2] : sp.t[b], ep = envs ? envs[3] : sp.episode[b];
@@ -572,7 +594,7 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
 }
 
 // (mz_root.hip.h) the root of a move for the 16 rows of a workgroup
-template <int JTP, int G, bool SELFPLAY, bool GAME, class STAMPF>
+template <int JTP, int G, bool SELFPLAY, int GAME, class STAMPF>
 __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t, const float *obs_in,
                                              const f32x4 *istream, int nst0, const SelfplayState &sp, uint64_t seed,
                                              double alpha, double frac, float *smem, int tid, double *root_stage,
@@ -591,12 +613,15 @@ struct MzRootArgs {
 // root and search, and the resident weight steps are loaded once per launch instead of once per move.  The
 // workgroups drift apart freely: nothing is exchanged between them.
 // GAME (HEAD, two players): the moves are those of the device TicTacToe environment (mz_root_body<.., GAME>, mz_ttt_apply).
+// GAME && SP (HEAD, single player): those of the device CartPole environment (mz_cartpole_apply); its four float64 state
+// words live in words 8..15 of the workgroup's LDS environment rows across the moves of the launch.
 template <int KS1, int JTP, int G, int LT, bool PROF, bool SP, bool HEAD = false, bool GAME = false>
 __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, const f32x4 *wstream, int nsims,
                                                           int slot0, unsigned long long *prof, SelfplayState sp,
                                                           int record, uint64_t seed, MzRootArgs ra) {
   static_assert(!HEAD || (LT != 0 && !PROF), "HEAD: trees in LDS, no phase stamps");
-  static_assert(!GAME || (HEAD && !SP), "GAME: whole moves of a two-player game environment");
+  static_assert(!GAME || HEAD, "GAME: whole moves of a game environment (two players: TicTacToe, single player: CartPole)");
+  constexpr int GK = GAME ? (SP ? 2 : 1) : 0;      // the environment of a GAME launch
   using SC = FusedSched<KS1, JTP>;
   constexpr int NB = MZ_NB, NSTEPS = SC::NSTEPS, RS = SC::RS, NRING = SC::NRING;
   static_assert(RS <= SC::FC1, "resident steps must be fc1 steps of the dynamics stage");
@@ -661,13 +686,16 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
   }
 
   const int nmoves = HEAD ? ra.nmoves : 1;
-  constexpr bool ENVS = HEAD && !GAME;      // per-environment scalars of the synthetic env kept in LDS across the moves
+  constexpr bool ENVS = HEAD && GK != 1;    // per-environment scalars (synthetic env, CartPole) kept in LDS across the moves
   if constexpr (ENVS) {
     if (tid0 < 16 && b0 + tid0 < t.B) {
       const int b = b0 + tid0;
       *(unsigned long long *)(s_env + tid0 * MZ_ENVW) = sp.movecnt[b];
       s_env[tid0 * MZ_ENVW + 2] = sp.t[b]; s_env[tid0 * MZ_ENVW + 3] = sp.episode[b];
       *(double *)(s_env + tid0 * MZ_ENVW + 4) = sp.temp[b];
+      if constexpr (GK == 2) {
+        for (int k = 0; k < 4; ++k) ((double *)(s_env + tid0 * MZ_ENVW + 8))[k] = sp.cart[(size_t)b * 4 + k];
+      }
     }
   }
   // HEAD launches: cycles per phase of a move (s_memtime), accumulated over the launch when `prof` is given
@@ -689,7 +717,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
     // root's address arithmetic as invariants of the move loop and carries them through the simulations --
     // 413.5 vs 410.5 us per move, A/B on one box)
     if (ra.nst0 >= 0)
-    mz_root_body<JTP, G, true, GAME>(n, t, nullptr, ra.istream, ra.nst0, sp, seed, ra.alpha, ra.frac,
+    mz_root_body<JTP, G, true, GK>(n, t, nullptr, ra.istream, ra.nst0, sp, seed, ra.alpha, ra.frac,
                                (float *)(dyn_lds + (((t.sims + 2) * PBS * 8 + 15) & ~15)), tid_r, s_stage,
                                [&](int k) __attribute__((always_inline)) { HSTAMP(4 + k) }, ENVS ? s_env : nullptr);
     __syncthreads();
@@ -768,7 +796,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
         my_act[i] = best;
         tr[i].len = 2;
         tr[i].legal = (t.A >= 32) ? 0xFFFFFFFFu : ((1u << t.A) - 1u);
-        if constexpr (GAME) {         // the root's mover and legal moves (mz_root_body left them in the staging area)
+        if constexpr (GK == 1) {      // the root's mover and legal moves (mz_root_body left them in the staging area)
           tr[i].root_tp = (int)st[33];
           tr[i].tp = -tr[i].root_tp;                 // to_play at the leaf of the first descent (mcts.py:90-92)
           tr[i].legal = (uint32_t)st[34];
@@ -783,7 +811,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
           }
           for (int k = tl; k < have; k += TL) tm[i].X[k] = 0.0;
         } else {
-          for (int k = tl; k < have; k += TL) { tm[i].N[k] = 0; tm[i].E[k] = (k == 0) ? 0 : -1; tm[i].TP[k] = (GAME && k == 0) ? (int8_t)tr[i].root_tp : (int8_t)1; }
+          for (int k = tl; k < have; k += TL) { tm[i].N[k] = 0; tm[i].E[k] = (k == 0) ? 0 : -1; tm[i].TP[k] = (GK == 1 && k == 0) ? (int8_t)tr[i].root_tp : (int8_t)1; }
           if (tl == 0) { tm[i].W[0] = 0.0; tm[i].R[0] = 0.f; tm[i].X[0] = 0.0; }      // the root's expansion slot
         }
         for (int k = tl; k < have; k += TL) tm[i].P[k] = (k == 0) ? 0.0 : st[k - 1];
@@ -1188,7 +1216,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
 #pragma unroll
     for (int i = 0; i < NPASS; ++i) {
       const int mt = tid / TL + i * (256 / TL);
-      if (b0 + mt < t.B) mz_finalize_record<TL, LT, GAME>(t, tm[i], sp, b0 + mt, tl, tr[i].legal, seed, s_stage + mt * 96, n.O,
+      if (b0 + mt < t.B) mz_finalize_record<TL, LT, GK>(t, tm[i], sp, b0 + mt, tl, tr[i].legal, seed, s_stage + mt * 96, n.O,
                                                            ENVS ? s_env + mt * MZ_ENVW : nullptr);
     }
   }

@@ -21,6 +21,9 @@ MZ_VARIANTS_FUSED(MZ_KF, (MZ_INST_F))
 #ifdef MZ_INST_GAME      // (the unit of MZ_GAME_SHAPE) whole moves of the device TicTacToe environment
 MZ_GAME_VARIANT(MZ_KF)
 #endif
+#ifdef MZ_INST_CART      // (the unit of MZ_CART_SHAPE) whole moves of the device CartPole environment
+MZ_CART_VARIANT(MZ_KF)
+#endif
 #elif defined(MZ_INST_H)
 MZ_VARIANTS_H2(MZ_KH, (MZ_INST_H))
 #else

@@ -17,6 +17,8 @@
 #define MZ_H2_ROWS_MORE(X) X(13, 16)
 // whole moves of the device TicTacToe environment (two players, 9 actions): one more kernel of this shape's row
 #define MZ_GAME_SHAPE 15, 1, 16
+// whole moves of the device CartPole environment (single player, 2 actions): one more kernel of the A <= 4 row
+#define MZ_CART_SHAPE 14, 1, 4
 
 // ---- variants of a shape S, V(S, tree placement LT, phase stamps PROF, single player SP, whole moves HEAD)
 // trees in LDS (LT 1 whole, 2 compact): both kernels; HEAD needs LDS trees, no stamps, a single player
@@ -30,6 +32,9 @@
   MZ_VARIANTS_H2(V, S)
 // the game kernel: (S, LT, PROF, SP, HEAD, GAME)
 #define MZ_GAME_VARIANT(V) V((MZ_GAME_SHAPE), 2, false, false, true, true)
+// the single-player game kernel (GAME && SP): whole trees in LDS, the placement of 2 actions at every simulation count the
+// fused kernels take (16 trees of 1 + 63 * 2 nodes fit beside the root's working set)
+#define MZ_CART_VARIANT(V) V((MZ_CART_SHAPE), 1, false, true, true, true)
 
 #define MZ_UNPACK(...) __VA_ARGS__      // MZ_UNPACK S: a shape tuple (KS1, JTP, G) / (G) as leading template arguments
 
@@ -42,5 +47,5 @@
 #ifdef MZ_DEV_ONLY
 #define MZ_ALL_KERNELS MZ_FUSED_ROWS_DEV(MZ_KF_ROW) MZ_H2_ROWS_DEV(MZ_KH_ROW)
 #else
-#define MZ_ALL_KERNELS MZ_FUSED_ROWS(MZ_KF_ROW) MZ_GAME_VARIANT(MZ_KG) MZ_H2_ROWS(MZ_KH_ROW)
+#define MZ_ALL_KERNELS MZ_FUSED_ROWS(MZ_KF_ROW) MZ_GAME_VARIANT(MZ_KG) MZ_CART_VARIANT(MZ_KG) MZ_H2_ROWS(MZ_KH_ROW)
 #endif

@@ -12,6 +12,7 @@
 #define MZ_RNG_DIRICHLET 3u
 #define MZ_RNG_ACTION 4u
 #define MZ_RNG_EVAL 5u       // evaluation walk (mz_eval.hip.h): one uniform per applied action, counter (env, move, step)
+#define MZ_RNG_ENV 6u        // start state of a device environment's episode (mz_cartpole_reset_state): counter (env, episode, 0)
 
 struct mz_u4 { uint32_t x, y, z, w; };
 

@@ -39,7 +39,9 @@ __host__ __device__ inline int mz_root_nst0(int O) { return ((O + 1 + 3) / 4 + 1
 // the TicTacToe state (custom_environments/tic_tac_toe.py:24,50), the root is expanded over the legal moves for the player
 // to move (actors.py:141-142), the Dirichlet draw covers the legal actions only (mcts.py:58-59) or is the host's
 // (parity runs); root_stage additionally receives to_play (slot 33) and the legal mask (slot 34).
-template <int JTP, int G, bool SELFPLAY, bool GAME = false, class STAMPF>
+// GAME == 2: the device CartPole environment (single player, every action legal: the root's tree part is the synthetic
+// environment's); the observation is the float cast of the four float64 state words the launch keeps in envs[8..15].
+template <int JTP, int G, bool SELFPLAY, int GAME = 0, class STAMPF>
 __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t, const float *obs_in,
                                              const f32x4 *istream, int nst0, const SelfplayState &sp, uint64_t seed,
                                              double alpha, double frac, float *smem, int tid, double *root_stage,
@@ -118,7 +120,11 @@ __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t
       float v = 0.f;
       if (k < O) {
         if (b < t.B) {
-          if constexpr (GAME) {       // tic_tac_toe.py:24,50: observation = turn * board, np.float32 (actors.py:134)
+          if constexpr (GAME == 2) {  // envs.CartPole._obs: the state as np.float32
+            v = (float)((const double *)(envs + m * MZ_ENVW + 8))[k];
+            sp.obs[(size_t)b * O + k] = v;
+          } else
+          if constexpr (GAME == 1) {  // tic_tac_toe.py:24,50: observation = turn * board, np.float32 (actors.py:134)
             v = (float)((int)sp.turn[b] * (int)sp.board[(size_t)b * 9 + k]);
             sp.obs[(size_t)b * O + k] = v;
           } else
@@ -277,7 +283,7 @@ __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t
       if (b < t.B && tl < G) {
         const uint64_t move = envs ? (uint64_t)*(const unsigned long long *)(envs + mt * MZ_ENVW) : (uint64_t)sp.movecnt[b];
         double nz;
-        if constexpr (GAME) {
+        if constexpr (GAME == 1) {
           // legal_actions() = the empty cells (tic_tac_toe.py:27-28), game.to_play = env.turn
           const int to_play = (int)sp.turn[b];
           const bool ok = tl < A && sp.board[(size_t)b * 9 + (tl < 9 ? tl : 0)] == 0;
@@ -330,5 +336,5 @@ __global__ __launch_bounds__(256, 1) void k_root(NetView n, TreeView t, const fl
                                                   int nst0, SelfplayState sp, uint64_t seed, double alpha,
                                                   double frac) {
   __shared__ __attribute__((aligned(16))) float smem[MZ_ROOT_LDS_FLOATS];
-  mz_root_body<JTP, G, SELFPLAY, false>(n, t, obs_in, istream, nst0, sp, seed, alpha, frac, smem, (int)threadIdx.x, nullptr, MzNoStamp(), nullptr);
+  mz_root_body<JTP, G, SELFPLAY, 0>(n, t, obs_in, istream, nst0, sp, seed, alpha, frac, smem, (int)threadIdx.x, nullptr, MzNoStamp(), nullptr);
 }

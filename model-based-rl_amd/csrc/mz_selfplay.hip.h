@@ -27,11 +27,13 @@ struct SelfplayState {
   unsigned long long *movecnt;   // [B] moves completed by env b (all equal; per-env so that every thread reads and
                                  // advances only its own counter): keys the RNG and the ring slot
   // ---- a real game as the environment (mz_selfplay_set_env): TicTacToe, custom_environments/tic_tac_toe.py:5-76
-  int env_kind;          // 0 = synthetic fixed-length episodes (above), 1 = TicTacToe (two players, 9 cells, 9 actions)
+  int env_kind;          // 0 = synthetic fixed-length episodes (above), 1 = TicTacToe (two players, 9 cells, 9 actions),
+                         // 2 = CartPole (single player, 4 observations, 2 actions, episode_len = the time limit)
   int8_t *board;         // [B][9] env.board: 0 empty, +1 / -1 the two players' marks
   int8_t *turn;          // [B] env.turn == game.to_play: +1 or -1, the player about to move
   uint8_t *legal;        // [B][A] legal_actions() of the current position as a mask (actors.py:141)
   int8_t *to_play;       // [B] game.to_play of the current move (root.expand's to_play, actors.py:142)
+  double *cart;          // [Bp][4] CartPole: (x, x_dot, theta, theta_dot) of the current position, float64
   const double *draw_uniform;   // [B] or null: the uniform select_action consumes, given by the host (parity runs,
                                 // mz_selfplay_set_draws); null = the device RNG keyed (seed, env, move)
   int draws_noise;       // != 0: the Dirichlet draw of the coming moves is the one the host put into TreeView::noise
@@ -202,4 +204,111 @@ static __global__ void k_ttt_step_record(TreeView tv, SelfplayState sp, int B, i
   for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
   for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
   mz_ttt_apply(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A);
+}
+
+
+// ---- CartPole on the device (envs.CartPole is the definition; gym's CartPole-v1 / -v0 with its TimeLimit folded in).
+// sin / cos of the pole angle: fixed Taylor polynomials in z = theta * theta, Horner from the highest term down with plain
+// float64 multiplies and adds -- with -ffp-contract=off the host class, the host build of this function and the device run the
+// same IEEE operations, so trajectories agree bit for bit (libm's sin / cos differ between the sides in the last place,
+// and the pole grows a last-place difference by ~e^0.09 per step).
+__host__ __device__ inline double mz_cartpole_sin(double t) {
+  const double z = t * t;
+  double r = -1.0 / 1307674368000.0;
+  r = r * z + 1.0 / 6227020800.0;
+  r = r * z + -1.0 / 39916800.0;
+  r = r * z + 1.0 / 362880.0;
+  r = r * z + -1.0 / 5040.0;
+  r = r * z + 1.0 / 120.0;
+  r = r * z + -1.0 / 6.0;
+  r = r * z + 1.0;
+  return t * r;
+}
+__host__ __device__ inline double mz_cartpole_cos(double t) {
+  const double z = t * t;
+  double r = 1.0 / 20922789888000.0;
+  r = r * z + -1.0 / 87178291200.0;
+  r = r * z + 1.0 / 479001600.0;
+  r = r * z + -1.0 / 3628800.0;
+  r = r * z + 1.0 / 40320.0;
+  r = r * z + -1.0 / 720.0;
+  r = r * z + 1.0 / 24.0;
+  r = r * z + -1.0 / 2.0;
+  r = r * z + 1.0;
+  return r;
+}
+// env.step(action) on st = (x, x_dot, theta, theta_dot), in place, in the operation order of envs.CartPole.step; returns
+// whether the new state lies outside the thresholds (the time limit is the caller's: it owns the step counter).  The one
+// function every device form -- and the host side of the debug header -- calls.
+__host__ __device__ inline bool mz_cartpole_step(double *st, int action) {
+  const double g = 9.8, M = 1.1, m_pole = 0.1, l = 0.5, pml = 0.05, F = 10.0, tau = 0.02;
+  double x = st[0], x_dot = st[1], theta = st[2], theta_dot = st[3];
+  const double f = action == 1 ? F : -F;
+  const double c = mz_cartpole_cos(theta), s = mz_cartpole_sin(theta);
+  const double temp = (f + pml * theta_dot * theta_dot * s) / M;
+  const double tha = (g * s - c * temp) / (l * (4.0 / 3.0 - m_pole * c * c / M));
+  const double xa = temp - pml * tha * c / M;
+  x = x + tau * x_dot;
+  x_dot = x_dot + tau * xa;
+  theta = theta + tau * theta_dot;
+  theta_dot = theta_dot + tau * tha;
+  st[0] = x; st[1] = x_dot; st[2] = theta; st[3] = theta_dot;
+  const double th = 12 * 2 * 3.141592653589793 / 360;
+  return x < -2.4 || x > 2.4 || theta < -th || theta > th;
+}
+// env.reset() of episode `episode` of environment `env`: every component uniform in [-0.05, 0.05), from the counter RNG
+// -- integer-derived, identical on host and device, so the host can name the start of every episode.
+__host__ __device__ inline void mz_cartpole_reset_state(uint64_t seed, uint32_t env, uint32_t episode, double *out) {
+  for (uint32_t j = 0; j < 2; ++j) {
+    const mz_u4 r = mz_philox(seed, env, episode, 0u, (MZ_RNG_ENV << 24) | j);
+    out[2 * j] = (mz_u01(r.x, r.y) - 0.5) * 0.1;
+    out[2 * j + 1] = (mz_u01(r.z, r.w) - 0.5) * 0.1;
+  }
+}
+
+// What Actor.play_game reads before a move: the observation = the state as float32; every action is legal, to_play = +1
+static __global__ void k_cartpole_observe(SelfplayState sp, int B, int A) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  for (int k = 0; k < 4; ++k) sp.obs[(size_t)b * 4 + k] = (float)sp.cart[(size_t)b * 4 + k];
+  for (int a = 0; a < A; ++a) sp.legal[(size_t)b * A + a] = 1;
+  sp.to_play[b] = 1;
+}
+
+// Game.apply on CartPole's env.step for environment b, by ONE lane, and the tail of its experience record.  st: the
+// environment's four doubles (global memory, or the LDS words of a whole-moves launch), stepped or reset in place;
+// tt / ep: its step counter and episode before the move.  Returns done; the caller stores the counters.
+__device__ __forceinline__ int mz_cartpole_apply(const SelfplayState &sp, int b, int action, double root_value, double error,
+                                                 float *rec, int A, double *st, int tt, int ep, uint64_t seed) {
+  const int O = 4;
+  const bool out = mz_cartpole_step(st, action);
+  const int done = (out || tt + 1 >= sp.episode_len) ? 1 : 0;      // termination, or gym's TimeLimit
+  mz_rec_put_double(rec + O + A + 0, root_value);
+  mz_rec_put_double(rec + O + A + 2, error);
+  rec[O + A + 4] = 1.f;
+  int32_t *ri = (int32_t *)(rec + O + A + 5);
+  ri[0] = action; ri[1] = done; ri[2] = tt; ri[3] = sp.env_offset + b; ri[4] = ep;
+  if (done) mz_cartpole_reset_state(seed, (uint32_t)(sp.env_offset + b), (uint32_t)(ep + 1), st);
+  return done;
+}
+
+// End of a move of the launch-per-step form: finalize the tree, write the record (pre-step observation), step the environment
+static __global__ void k_cartpole_step_record(TreeView tv, SelfplayState sp, int B, int A, uint64_t seed) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long move = sp.movecnt[b];
+  sp.movecnt[b] = move + 1ull;
+  mz_finalize_tree(tv, b, sp.temp, sp.draw_uniform, seed, move, sp.env_offset, sp.action, sp.child_visits, sp.root_value,
+                   sp.error, nullptr);
+  const int O = 4;
+  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
+  for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
+  for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
+  const int tt = sp.t[b], ep = sp.episode[b];
+  double st[4];
+  for (int k = 0; k < 4; ++k) st[k] = sp.cart[(size_t)b * 4 + k];
+  const int done = mz_cartpole_apply(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A, st, tt, ep, seed);
+  for (int k = 0; k < 4; ++k) sp.cart[(size_t)b * 4 + k] = st[k];
+  if (done) { sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next; }
+  else sp.t[b] = tt + 1;
 }

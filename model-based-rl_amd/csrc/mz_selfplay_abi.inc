@@ -46,6 +46,14 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
     HIPCHECK(hipMemsetAsync(sp.board, 0, (size_t)e->Bp * 9, s));
     HIPCHECK(hipMemsetAsync(sp.turn, 1, (size_t)e->Bp, s));
   }
+  if (sp.env_kind == 2) {      // CartPole: episode_len is the time limit; every environment starts episode 0 at step 0
+    std::vector<double> st((size_t)e->Bp * 4, 0.0);
+    for (int b = 0; b < e->B; ++b)
+      mz_cartpole_reset_state(e->cfg.seed, (uint32_t)(e->cfg.env_id_offset + b), 0u, st.data() + (size_t)b * 4);
+    HIPCHECK(hipMemsetAsync(sp.t, 0, (size_t)e->Bp * 4, s));
+    HIPCHECK(hipMemcpyAsync(sp.cart, st.data(), st.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
   HIPCHECK(hipMemsetAsync(sp.episode, 0, (size_t)e->Bp * 4, s));
   HIPCHECK(hipMemsetAsync(sp.movecnt, 0, (size_t)e->Bp * 8, s));
   std::vector<double> temp(e->Bp, temperature);
@@ -74,7 +82,9 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
 static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
-  hipLaunchKernelGGL(k_ttt_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
+  const bool cart = sp.env_kind == 2;
+  if (cart) hipLaunchKernelGGL(k_cartpole_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
+  else hipLaunchKernelGGL(k_ttt_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
   if (launch_root(e, sp.obs, false, s)) return -1;
   if (!e->draws_noise)
     hipLaunchKernelGGL(k_dirichlet, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, (const uint8_t *)sp.legal,
@@ -83,7 +93,8 @@ static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
   TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, (const double *)e->tv.noise,
               e->cfg.root_exploration_fraction, 1);
   if (launch_search(e, o, true, s)) return -1;
-  hipLaunchKernelGGL(k_ttt_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
+  if (cart) hipLaunchKernelGGL(k_cartpole_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
+  else hipLaunchKernelGGL(k_ttt_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -148,6 +159,8 @@ int mz_selfplay_set_obs(mz_engine *e, int uint8_obs, const float *obs_min, const
   SelfplayState &sp = e->sp;
   if (uint8_obs < 0 || uint8_obs > 2) return fail("mz_selfplay_set_obs: uint8_obs %d (0 float, 1 byte-valued, 2 byte-valued and packed in the record)", uint8_obs);
   if (uint8_obs == 2 && sp.env_kind) return fail("mz_selfplay_set_obs: packed byte observations are for the synthetic -ram- environments");
+  if (sp.env_kind == 2 && (uint8_obs || obs_min))
+    return fail("mz_selfplay_set_obs: the CartPole environment has neither byte observations nor --norm_obs");
   if (selfplay_alloc(e)) return -1;
   if (sp.moves_host != sp.drained) return fail("mz_selfplay_set_obs: drain the ring first (the record layout may change)");
   sp.obs_u8 = uint8_obs;
@@ -182,12 +195,17 @@ int mz_selfplay_export_trees(mz_engine *e, int keep) {
 
 // The environment of the self-play loop.  kind 0: the synthetic fixed-length episodes (default).  kind 1: TicTacToe with
 // the reference's rules (custom_environments/tic_tac_toe.py:5-76) -- needs obs_dim 9, action_space 9 and a two-player
-// engine; observations, legal moves, wins, draws and the alternating to_play all live on the device.  Call before
-// mz_selfplay_reset.
+// engine; observations, legal moves, wins, draws and the alternating to_play all live on the device.  kind 2: CartPole
+// (envs.CartPole: CartPole-v1 / -v0) -- needs obs_dim 4, action_space 2 and a single-player engine; the float64 state,
+// termination and the time limit (mz_selfplay_reset's episode_len) live on the device.  Call before mz_selfplay_reset.
 int mz_selfplay_set_env(mz_engine *e, int kind) {
   if (!e) return fail("mz_selfplay_set_env: null engine");
   MZ_ENTER(e);
-  if (kind != 0 && kind != 1) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe)", kind);
+  if (kind < 0 || kind > 2) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole)", kind);
+  if (kind == 2 && (e->O != 4 || e->A != 2 || e->cfg.two_players))
+    return fail("mz_selfplay_set_env: CartPole needs obs_dim 4, action_space 2 and a single player (got %d, %d, two_players %d)", e->O, e->A, e->cfg.two_players);
+  if (kind == 2 && (e->sp.obs_u8 || e->sp.obs_min))
+    return fail("mz_selfplay_set_env: the CartPole environment has neither byte observations nor --norm_obs");
   if (kind == 1 && (e->O != 9 || e->A != 9 || !e->cfg.two_players))
     return fail("mz_selfplay_set_env: TicTacToe needs obs_dim 9, action_space 9 and two_players (got %d, %d, %d)", e->O, e->A, e->cfg.two_players);
   if (selfplay_alloc(e)) return -1;
@@ -198,6 +216,10 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
         dmalloc(e, &sp.legal, (size_t)e->Bp * e->A) || dmalloc(e, &sp.to_play, (size_t)e->Bp) ||
         dmalloc(e, &e->draw_uniform, (size_t)e->Bp))
       return -1;
+  }
+  if (kind == 2 && !sp.cart) {
+    if (dmalloc(e, &sp.cart, (size_t)e->Bp * 4)) return -1;
+    if (!sp.legal && (dmalloc(e, &sp.legal, (size_t)e->Bp * e->A) || dmalloc(e, &sp.to_play, (size_t)e->Bp))) return -1;
   }
   sp.env_kind = kind;
   sp.ready = false;                // the environment state is (re)made by mz_selfplay_reset
@@ -212,7 +234,7 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
 int mz_selfplay_set_draws(mz_engine *e, const double *noise, const double *uniform, void *stream) {
   if (!e) return fail("mz_selfplay_set_draws: null engine");
   MZ_ENTER(e);
-  if (!e->sp.env_kind) return fail("mz_selfplay_set_draws: only for a game environment (mz_selfplay_set_env)");
+  if (e->sp.env_kind != 1) return fail("mz_selfplay_set_draws: only for the TicTacToe environment (mz_selfplay_set_env)");
   hipStream_t s = (hipStream_t)stream;
   if (noise) HIPCHECK(hipMemcpyAsync(e->tv.noise, noise, (size_t)e->B * e->A * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (uniform) HIPCHECK(hipMemcpyAsync(e->draw_uniform, uniform, (size_t)e->B * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -554,6 +576,30 @@ int mz_selfplay_drain(mz_engine *e, float *out, int max_moves, int *n_moves, voi
   }
   sp.drained += n;
   *n_moves = n;
+  return 0;
+}
+
+// ---- the CartPole environment's state (include/mz_engine_debug.h)
+int mz_cartpole_reset_state(const mz_engine *e, int env, int episode, double *out) {
+  if (!e || !out) return fail("mz_cartpole_reset_state: null argument");
+  mz_cartpole_reset_state(e->cfg.seed, (uint32_t)env, (uint32_t)episode, out);
+  return 0;
+}
+int mz_selfplay_env_state(mz_engine *e, double *out) {
+  if (!e || !out) return fail("mz_selfplay_env_state: null argument");
+  MZ_ENTER(e);
+  if (e->sp.env_kind != 2 || !e->sp.ready) return fail("mz_selfplay_env_state: the CartPole environment is not set up (mz_selfplay_set_env, mz_selfplay_reset)");
+  HIPCHECK(hipDeviceSynchronize());
+  HIPCHECK(hipMemcpy(out, e->sp.cart, (size_t)e->B * 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+int mz_selfplay_set_env_state(mz_engine *e, int env, const double *state) {
+  if (!e || !state) return fail("mz_selfplay_set_env_state: null argument");
+  MZ_ENTER(e);
+  if (e->sp.env_kind != 2 || !e->sp.ready) return fail("mz_selfplay_set_env_state: the CartPole environment is not set up (mz_selfplay_set_env, mz_selfplay_reset)");
+  if (env < 0 || env >= e->B) return fail("mz_selfplay_set_env_state: environment %d outside [0, %d)", env, e->B);
+  HIPCHECK(hipDeviceSynchronize());
+  HIPCHECK(hipMemcpy(e->sp.cart + (size_t)env * 4, state, 4 * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -459,10 +459,11 @@ class Engine(object):
     self.obs_packed = bool(packed)
     self.rec_floats = self.lib.mz_selfplay_rec_floats(self._h)
 
-  ENVS = {'synthetic': 0, 'tictactoe': 1}
+  ENVS = {'synthetic': 0, 'tictactoe': 1, 'cartpole': 2}
 
   def selfplay_set_env(self, kind):
-    """'synthetic' (default) or 'tictactoe' (the reference's custom_environments/tic_tac_toe.py on the device); before selfplay_reset"""
+    """'synthetic' (default), 'tictactoe' (the reference's custom_environments/tic_tac_toe.py on the device) or 'cartpole'
+    (envs.CartPole on the device; selfplay_reset's episode_len is its time limit); before selfplay_reset"""
     _abi.check(self.lib.mz_selfplay_set_env(self._h, self.ENVS[kind] if isinstance(kind, str) else int(kind)), 'mz_selfplay_set_env')
 
   def selfplay_set_draws(self, noise=None, uniform=None):
@@ -558,6 +559,24 @@ class Engine(object):
     _abi.check(self.lib.mz_selfplay_drain(self._h, C.c_void_p(out.data_ptr()), max_moves, C.byref(n), stream),
                'mz_selfplay_drain')
     return out, n.value
+
+  def cartpole_reset_state(self, env, episode):
+    """float64 state [4] episode `episode` of (global) environment `env` of the device CartPole starts from"""
+    out = np.zeros(4, np.float64)
+    _abi.check(self.lib.mz_cartpole_reset_state(self._h, int(env), int(episode), out.ctypes.data_as(C.c_void_p)),
+               'mz_cartpole_reset_state')
+    return out
+
+  def selfplay_env_state(self):
+    """[B, 4] float64: the current states of the device CartPole environments (synchronous)"""
+    out = np.zeros((self.B, 4), np.float64)
+    _abi.check(self.lib.mz_selfplay_env_state(self._h, out.ctypes.data_as(C.c_void_p)), 'mz_selfplay_env_state')
+    return out
+
+  def selfplay_set_env_state(self, env, state):
+    """replace the state of device CartPole environment `env` (tests: a start next to a threshold); after selfplay_reset"""
+    st = np.ascontiguousarray(state, np.float64).reshape(4)
+    _abi.check(self.lib.mz_selfplay_set_env_state(self._h, int(env), st.ctypes.data_as(C.c_void_p)), 'mz_selfplay_set_env_state')
 
   def synth_obs(self, env, episode, t):
     obs = np.zeros(self.O, np.float32)

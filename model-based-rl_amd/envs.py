@@ -1,10 +1,14 @@
 """Environments that exist without gym.  TicTacToe follows the reference's custom environment
 (custom_environments/tic_tac_toe.py:5-76: gym-0.x API, observation = turn * board, reward 1 for the
-winning move, draw after nine moves).  Every other reference environment (Box2D, ALE) is unavailable on
-both boxes; its SHAPE is served by the on-device synthetic env (csrc/mz_selfplay.hip.h)."""
+winning move, draw after nine moves).  CartPole is the classic-control task the reference reaches through gym.make
+('CartPole-v1' / 'CartPole-v0'); gym is not installed, so the class below IS its definition and the device environment
+(csrc/mz_selfplay.hip.h, mz_cartpole_step) follows it bit for bit.  Every other reference environment (Box2D, ALE) is
+unavailable; its SHAPE is served by the on-device synthetic env (csrc/mz_selfplay.hip.h)."""
 from types import SimpleNamespace
 
 import numpy as np
+
+from .config import CARTPOLE_TIME_LIMITS
 
 _LINES = np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8], [0, 3, 6], [1, 4, 7], [2, 5, 8], [0, 4, 8], [2, 4, 6]])
 
@@ -44,8 +48,92 @@ class TicTacToe(object):
     return self.turn * self.board.copy(), int(won), done, {'result': result}
 
 
+# sin / cos of the pole angle as fixed Taylor polynomials in z = theta * theta, Horner from the highest term down with plain
+# float64 multiplies and adds: the device runs the very same IEEE operations (csrc/mz_selfplay.hip.h), where its libm and
+# the host's differ in the last place -- and the pole, an unstable system, grows such a difference by ~e^0.09 per step.
+# Within 1.2e-16 of math.sin / math.cos on [-0.8, 0.8]; the state is reset before |theta| passes 0.27.
+_SIN_C = (1.0, -1.0 / 6.0, 1.0 / 120.0, -1.0 / 5040.0, 1.0 / 362880.0, -1.0 / 39916800.0, 1.0 / 6227020800.0,
+          -1.0 / 1307674368000.0)
+_COS_C = (1.0, -1.0 / 2.0, 1.0 / 24.0, -1.0 / 720.0, 1.0 / 40320.0, -1.0 / 3628800.0, 1.0 / 479001600.0,
+          -1.0 / 87178291200.0, 1.0 / 20922789888000.0)
+
+
+def sin_p(t):
+  t = float(t)
+  z = t * t
+  r = _SIN_C[7]
+  for k in range(6, -1, -1):
+    r = r * z + _SIN_C[k]
+  return t * r
+
+
+def cos_p(t):
+  t = float(t)
+  z = t * t
+  r = _COS_C[8]
+  for k in range(7, -1, -1):
+    r = r * z + _COS_C[k]
+  return r
+
+
+class CartPole(object):
+  """Cart and pole of Barto, Sutton & Anderson with gym's constants, Euler integration, reward 1 per step, termination
+  at |x| > 2.4 or |theta| > 12 degrees, and gym's TimeLimit folded in (done at max_episode_steps; the reference does
+  not tell truncation from termination, game.py:87-91).  gym-0.x API.  The state is four Python floats (float64)."""
+  GRAVITY, MASS_CART, MASS_POLE, TOTAL_MASS = 9.8, 1.0, 0.1, 1.1
+  LENGTH, POLEMASS_LENGTH, FORCE_MAG, TAU = 0.5, 0.05, 10.0, 0.02
+  THETA_THRESHOLD = 12 * 2 * 3.141592653589793 / 360
+  X_THRESHOLD = 2.4
+
+  def __init__(self, max_episode_steps=500):
+    self.action_space = SimpleNamespace(n=2)
+    self.observation_space = np.zeros(4, dtype=np.float32)
+    self.max_episode_steps = int(max_episode_steps)
+    self.rng = np.random.RandomState()
+    self.reset()
+
+  def seed(self, seed):
+    self.rng = np.random.RandomState(seed)
+
+  def set_state(self, state4):
+    self.state = tuple(float(v) for v in state4)
+
+  def _obs(self):
+    return np.array(self.state, dtype=np.float32)
+
+  def reset(self):
+    self.state = tuple(float(v) for v in self.rng.uniform(-0.05, 0.05, size=4))
+    self._elapsed_steps = 0
+    return self._obs()
+
+  def legal_actions(self):
+    return range(2)
+
+  def step(self, action):
+    x, x_dot, theta, theta_dot = self.state
+    g, M, m_pole, l, pml, tau = self.GRAVITY, self.TOTAL_MASS, self.MASS_POLE, self.LENGTH, self.POLEMASS_LENGTH, self.TAU
+    f = self.FORCE_MAG if int(action) == 1 else -self.FORCE_MAG
+    c, s = cos_p(theta), sin_p(theta)
+    temp = (f + pml * theta_dot * theta_dot * s) / M
+    tha = (g * s - c * temp) / (l * (4.0 / 3.0 - m_pole * c * c / M))
+    xa = temp - pml * tha * c / M
+    x = x + tau * x_dot
+    x_dot = x_dot + tau * xa
+    theta = theta + tau * theta_dot
+    theta_dot = theta_dot + tau * tha
+    self.state = (x, x_dot, theta, theta_dot)
+    th = self.THETA_THRESHOLD
+    done = bool(x < -self.X_THRESHOLD or x > self.X_THRESHOLD or theta < -th or theta > th)
+    self._elapsed_steps += 1
+    if self._elapsed_steps >= self.max_episode_steps:
+      done = True
+    return self._obs(), 1.0, done, {}
+
+
 def get_environment(config):
   if config.environment == 'TicTacToe':
     return TicTacToe()
+  if config.environment in CARTPOLE_TIME_LIMITS:
+    return CartPole(CARTPOLE_TIME_LIMITS[config.environment])
   raise NotImplementedError('%s needs gym/ALE/Box2D, which are not installed; the GPU actor serves its shape with '
                             'the synthetic on-device environment' % config.environment)
