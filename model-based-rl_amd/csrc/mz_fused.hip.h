@@ -14,7 +14,10 @@
 // buffer index is a compile-time constant; the stream is padded to a multiple of NB steps per simulation so the
 // ring position is the same at the top of every simulation and the prefetch runs across simulation boundaries,
 // barriers and the tree phase.  Every instruction in the MFMA stream costs issue time (the f32 "matrix core" IS
-// the vector ALU), so a streamed step carries exactly five besides its MFMAs: four loads and one counted wait.
+// the vector ALU), so a streamed step carries exactly five besides its MFMAs: one counted wait for its own pieces in
+// front, then its four prefetch loads one behind each group of four MFMAs -- in the fc1 steps as in the fc2 steps.  (Four
+// loads and the wait bunched in front of the 16 MFMAs, the fc1 steps' earlier form, cost ~36 cycles more per step: A/B
+// on one box -1.34 % per move on the LunarLander shapes, profiles/stream_placement_ab.txt.)
 // Output rows that would fill a 16-row tile with padding (rows 48..49 of the hidden state, the policy head of a
 // 4-action game) run on v_mfma_f32_4x4x1_16b_f32 instead (mz_mfma4_*).
 // (Measured dead ends, kept out: LDS-DMA (global_load_lds) rings filled by the MFMA waves themselves -- each 1-KiB
@@ -916,10 +919,14 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
       constexpr int s = decltype(S_)::value;
       // streamed steps: prefetch ring step r + NB - 1 (cyclic: the tail of a simulation prefetches the head of
       // the next); resident steps issue no loads
-      // fc2 steps: the compiler's hazard recogniser wants one instruction between two groups of four MFMAs that
-      // accumulate into the same four tiles and fills the slot with s_nop 0 (three per step) -- so those steps issue
-      // their four prefetch loads one per slot instead of up front (SPREAD), and wait for their own pieces first
+      // SPREAD (every step that has MFMAs; the padding steps only prefetch): the step waits for its own pieces first and
+      // issues its four prefetch loads one behind each group of four MFMAs.  vmcnt(4 (NB - 2)): the NB - 2
+      // steps requested after this one's may be outstanding, its own prefetch is not out yet.
+#ifndef MZ_FC1_LOADS_UPFRONT
+      constexpr bool SPREAD = s < E_P2;
+#else      // (development switch, A/B builds: the streamed fc1 steps issue four loads and one wait in front of their 16 MFMAs)
       constexpr bool SPREAD = (s >= E_FC1 && s < E_FC2) || (s >= E_P1 && s < E_P2);
+#endif
       constexpr int pf_r = s >= RS ? s - RS : 0;
       constexpr int pf_ps = (pf_r + NB - 1) % NRING, pf_pb = (pf_r + NB - 1) % NB;
       if constexpr (s >= RS) {
@@ -981,6 +988,10 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
             mz_mfma_v(acc[4 * tg + 1], Bf[cb][tg][1], x);
             mz_mfma_v(acc[4 * tg + 2], Bf[cb][tg][2], x);
             mz_mfma_v(acc[4 * tg + 3], Bf[cb][tg][3], x);
+          }
+          if constexpr (s >= RS && SPREAD) {
+            Bf[pf_pb][tg] = MZ_WLOAD(pf_ps, tg);
+            __builtin_amdgcn_sched_barrier(0);
           }
         }
         if constexpr (s == E_FC1 - 1 || s == E_P1 - 1) {

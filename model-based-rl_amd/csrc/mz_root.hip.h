@@ -10,6 +10,10 @@
 // residency and the ring is only 4 deep.  The first stage (O+1 -> 512) has a run-time length (obs_dim is not a
 // template parameter): a double-buffered loop over steps of two k-steps x 8 tiles, the observation tile chunked
 // through LDS 256 columns at a time; the rest (512 -> 50, LayerNorm, 51 -> 2x512, 512 -> 31 | A) is unrolled.
+// The loads here are ordinary global loads, four at the head of a step, waited for by the compiler.  (Measured out: the
+// search loop's form -- buffer resource, one load behind each group of four MFMAs, one counted wait per step, SrcC = 0
+// chain starts.  It shortens k_root, but in the whole-moves kernel this body shares its register allocation with the
+// simulation loop, which came out 22 instructions longer: +1.1 % per move, profiles/stream_placement_ab.txt.)
 #pragma once
 #include "mz_fused.hip.h"
 #include "mz_selfplay.hip.h"
