@@ -297,6 +297,13 @@ int mz_selfplay_set_moves(mz_engine *e, unsigned long long moves);
  * counter-RNG state mz_cartpole_reset_state(i, k) (mz_engine_debug.h).  With the exact-f32 kernel the moves run inside the
  * whole-moves launch (the state lives in LDS across its moves); with split_f16 or MZ_NO_PERSIST as one launch per step of a
  * move.  --norm_obs and byte observations (mz_selfplay_set_obs) are refused for it.
+ * 3: Connect Four (envs.ConnectFour, the definition here: 6 rows of 7 columns, cell 7 * row + col with row 0 at the bottom,
+ * an action is a column and the stone lands on its lowest empty cell, observation turn * board, legal = the columns whose
+ * top cell is empty, reward 1 for the move that makes a line of four, done on such a line or a full board, players
+ * alternate) entirely on the device; needs obs_dim 42, action_space 7, two_players.  mz_selfplay_reset's episode_len /
+ * stagger are ignored (real games).  With the exact-f32 kernel and 1..48 simulations the moves run inside the whole-moves
+ * launch; otherwise, with split_f16 or MZ_NO_PERSIST as one launch per step of a move.  --norm_obs, byte observations and
+ * packed records (mz_selfplay_set_obs) are refused for it.
  * mz_selfplay_set_draws (TicTacToe only): the Dirichlet draw (noise [dev][B][A] float64 at the legal positions,
  * mcts.py:59) and / or the uniform of select_action (uniform [dev][B] float64, config.py:77) of the following moves come
  * from the caller -- numpy's stream in the reference's order -- instead of the device RNG; NULL, NULL switches back. */

@@ -117,6 +117,14 @@ int mz_cartpole_reset_state(const mz_engine *e, int env, int episode, double *ou
 int mz_selfplay_env_state(mz_engine *e, double *out);
 int mz_selfplay_set_env_state(mz_engine *e, int env, const double *state);
 
+/* The device Connect Four environment (mz_selfplay_set_env kind 3; any other kind is refused).  mz_selfplay_board_state:
+ * out [host][B][44] int8 = per environment the 42 cells (7 * row + col, row 0 at the bottom), the turn and the step
+ * (synchronous).  mz_selfplay_set_board_state: cells42 [host][42] and turn replace environment env's position (after
+ * mz_selfplay_reset; synchronous); its step becomes the number of stones.  The position need not be reachable, but it
+ * needs a column that is not full. */
+int mz_selfplay_board_state(mz_engine *e, int8_t *out);
+int mz_selfplay_set_board_state(mz_engine *e, int env, const int8_t *cells42, int turn);
+
 #ifdef __cplusplus
 }
 #endif

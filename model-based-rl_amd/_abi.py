@@ -33,11 +33,13 @@ def translation_units(extra=()):
     return [ints(r) for body in bodies for r in re.findall(r'X\(([^)]*)\)', body)]
   game = ints(re.search(r'^#define MZ_GAME_SHAPE (.*)$', text, re.M).group(1))
   cart = ints(re.search(r'^#define MZ_CART_SHAPE (.*)$', text, re.M).group(1))
+  c4 = ints(re.search(r'^#define MZ_C4_SHAPE (.*)$', text, re.M).group(1))
   units = [('mz_engine', 'mz_engine.hip', [])]
   for _, ks1, jtp, g in rows('MZ_FUSED_ROWS'):
     units.append(('mz_inst_f_%d_%d_%d' % (ks1, jtp, g), 'mz_inst.hip', ['-DMZ_INST_F=%d,%d,%d' % (ks1, jtp, g)] +
                   (['-DMZ_INST_GAME=1'] if (ks1, jtp, g) == game else []) +
-                  (['-DMZ_INST_CART=1'] if (ks1, jtp, g) == cart else [])))
+                  (['-DMZ_INST_CART=1'] if (ks1, jtp, g) == cart else []) +
+                  (['-DMZ_INST_C4=1'] if (ks1, jtp, g) == c4 else [])))
   for _, g in rows('MZ_H2_ROWS'):
     units.append(('mz_inst_h_%d' % g, 'mz_inst.hip', ['-DMZ_INST_H=%d' % g]))
   return units
@@ -194,6 +196,8 @@ SIGNATURES = {
     'mz_cartpole_reset_state': (_I, [_VP, _I, _I, _VP]),
     'mz_selfplay_env_state': (_I, [_VP, _VP]),
     'mz_selfplay_set_env_state': (_I, [_VP, _I, _VP]),
+    'mz_selfplay_board_state': (_I, [_VP, _VP]),
+    'mz_selfplay_set_board_state': (_I, [_VP, _I, _VP, _I]),
 }
 
 

@@ -161,8 +161,8 @@ class Actor(Logger):
     self.num_envs = int(getattr(config, 'num_envs', 1))
     # TicTacToe: the reference's environment object on the host for parity runs (numpy's global stream) and single games;
     # a pool of games runs the same rules on the device (mz_selfplay_set_env, csrc/mz_selfplay.hip.h)
-    # CartPole likewise: envs.CartPole on the host, the same dynamics bit for bit on the device for a pool
-    self.host_env = (config.environment == 'TicTacToe' or config.environment in CARTPOLE_TIME_LIMITS) and (bool(getattr(config, 'parity_rng', False)) or self.num_envs == 1)
+    # CartPole likewise: envs.CartPole on the host, the same dynamics bit for bit on the device for a pool; and ConnectFour
+    self.host_env = (config.environment in ('TicTacToe', 'ConnectFour') or config.environment in CARTPOLE_TIME_LIMITS) and (bool(getattr(config, 'parity_rng', False)) or self.num_envs == 1)
     # FCNetwork: the engine's own fused HIP kernels.  Any other architecture (MuZeroNetwork / TinyNetwork): the torch
     # network stays in the loop behind the batched external-inference path (actors.py:45-47 is network-agnostic)
     self.torch_net = getattr(config, 'architecture', 'FCNetwork') != 'FCNetwork'
@@ -404,6 +404,8 @@ class Actor(Logger):
                              packed=ram and bool(getattr(cfg, 'obs_u8', False)))      # (bytes in the records: a replay with obs_u8)
       if cfg.environment == 'TicTacToe':
         eng.selfplay_set_env('tictactoe')
+      if cfg.environment == 'ConnectFour':             # (refuses a single player and --norm_obs: the engine's sentence surfaces)
+        eng.selfplay_set_env('connect_four')
       if cfg.environment in CARTPOLE_TIME_LIMITS:      # (refuses --norm_obs: not built for this environment)
         eng.selfplay_set_env('cartpole')
       # (CartPole: the episode length is the environment's time limit, whatever --episode_length says)

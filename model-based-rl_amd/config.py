@@ -155,6 +155,7 @@ ENV_SHAPES = {   # (action_space, obs_space) of the environments the reference's
     'TicTacToe': (9, (9,)), 'LunarLander-v2': (4, (8,)), 'Pong-ramNoFrameskip-v4': (6, (128,)),
     'Breakout-ramNoFrameskip-v4': (4, (128,)),
     'CartPole-v1': (2, (4,)), 'CartPole-v0': (2, (4,)),      # envs.CartPole, on the device too (csrc/mz_selfplay.hip.h)
+    'ConnectFour': (7, (42,)),                                # envs.ConnectFour, likewise (two players)
     # image observations of the Atari wrappers (wrappers.py:422-444: 96x96 uint8 frames) -- what MuZeroNetwork /
     # TinyNetwork take (SURVEY.md s7 on BASELINE configs[4]).  The channel count is NOT a property of the environment:
     # utils.py:27-35 builds the network with input_channels = stack_obs, doubled with --stack_actions (None below;

@@ -734,7 +734,7 @@ struct SearchPlan {
   int lt;                        // its tree placement: 1 whole trees in LDS, 2 compact, 0 global pool
   bool sp;                       // its single-player instantiation
   size_t lds_static, dyn, dyn_head;   // bytes: static LDS, dynamic LDS of a plain launch / of a whole-moves (HEAD) launch
-  bool game;                     // whole moves are those of a device game environment (the game kernels: TicTacToe, CartPole)
+  int game;                      // != 0: whole moves are those of this device game environment (its kind; the game kernels)
   bool persist;                  // the self-play loop runs as whole moves inside one launch
 };
 static SearchPlan search_plan(const mz_engine *e) {
@@ -756,13 +756,14 @@ static SearchPlan search_plan(const mz_engine *e) {
   p.dyn = mz_fused_dyn_lds(e->sims, e->NN, p.lt);
   p.dyn_head = fused_head_dyn_lds(e->sims, e->NN, p.lt);
   p.kind = fused_usable(e) && !e->root_hidden_external ? p.fkind : 0;
-  p.game = e->sp.env_kind != 0;
+  p.game = e->sp.env_kind;
   // whole moves: LDS trees and a HEAD kernel -- single player on the synthetic environment, or the device TicTacToe
   // environment on the exact-f32 game kernel (host-given uniforms / draws work there too), or the device CartPole
-  // environment on the single-player game kernel; a game environment without such an instantiation for its shape and
+  // environment on the single-player game kernel, or the device Connect Four environment on its two game kernels (whole
+  // trees, compact placement); a game environment without such an instantiation for its shape and
   // placement, or with split_f16, plays in the launch-per-step form (launch_move_game)
   p.persist = e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
-              (p.game ? !e->split_f16 && !!e->cfg.two_players == (e->sp.env_kind == 1) &&
+              (p.game ? !e->split_f16 && !!e->cfg.two_players == (p.game != 2) &&
                             find_kernel(1, *p.shape, p.lt, false, p.sp, true, true) != nullptr
                       : p.sp && !e->sp.env_kind);
   return p;
@@ -780,7 +781,7 @@ struct SearchOpts {
 
 static int launch_fused(mz_engine *e, const SearchPlan &p, const SearchOpts &o, hipStream_t s) {
   const bool head = o.moves > 0;
-  const void *fn = find_kernel(p.fkind, *p.shape, p.lt, !head && o.prof, p.sp, head, head && p.game);
+  const void *fn = find_kernel(p.fkind, *p.shape, p.lt, !head && o.prof, p.sp, head, head && p.game != 0);
   if (!fn) {
 #ifdef MZ_DEV_ONLY      // kernel development: only the two bench shapes are instantiated
     if (!find_kernel(p.fkind, *p.shape, p.lt, false, p.sp, false, false))

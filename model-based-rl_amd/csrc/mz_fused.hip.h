@@ -518,6 +518,7 @@ __host__ __device__ inline size_t mz_fused_dyn_lds(int sims, int NN, int lt) {
 // GAME 1: the environment is the device TicTacToe (mz_ttt_apply) instead of the synthetic one; the uniform may be the host's.
 // GAME 2: the device CartPole (mz_cartpole_apply) on the four float64 state words of envs[8..15]; the record's observation
 // is their float cast, read by lanes 0..3 before lane 0 steps them.
+// GAME 3: the device Connect Four (mz_c4_apply), kind 1's sequence on the global board; the uniform is the device's.
 template <int TL, int LT, int GAME = 0>
 __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const TreeMem<LT> &tm, const SelfplayState &sp,
                                                    int b, int lane, uint32_t legal, uint64_t seed, double *stage,
@@ -556,6 +557,11 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
     const int action = acts[idx];
     if constexpr (GAME == 1) {
       mz_ttt_apply(sp, b, action, rv, err, rec, A);
+      sp.movecnt[b] = move + 1ull;
+      return;
+    }
+    if constexpr (GAME == 3) {
+      mz_c4_apply(sp, b, action, rv, err, rec, A);
       sp.movecnt[b] = move + 1ull;
       return;
     }
@@ -615,16 +621,26 @@ struct MzRootArgs {
 // occupy), all simulations, then the end of the move -- so a move costs no kernel launch, no grid-wide drain between
 // root and search, and the resident weight steps are loaded once per launch instead of once per move.  The
 // workgroups drift apart freely: nothing is exchanged between them.
-// GAME (HEAD, two players): the moves are those of the device TicTacToe environment (mz_root_body<.., GAME>, mz_ttt_apply).
-// GAME && SP (HEAD, single player): those of the device CartPole environment (mz_cartpole_apply); its four float64 state
-// words live in words 8..15 of the workgroup's LDS environment rows across the moves of the launch.
+// GAME (HEAD only): the moves are those of a device game environment; its kind (SelfplayState::env_kind) is GK below.
+// 1 (two players): the device TicTacToe environment (mz_root_body<.., GK>, mz_ttt_apply).
+// 2 (single player): the device CartPole environment (mz_cartpole_apply); its four float64 state words live in words 8..15
+// of the workgroup's LDS environment rows across the moves of the launch.
+// 3 (two players): the device Connect Four environment (mz_c4_apply): kind 1's two-player branches, its own observation,
+// legal mask and rules; like kind 1 it keeps board, turn, step and episode in global memory, current after every move.
+// The kernel's template list stays as it is -- every compiled kernel keeps its symbol, which the profiles and
+// tests/test_abi.py name -- so the kind is decoded from what the game kernels differ in: the players, and between the two
+// board games the lane group of their action counts (9 actions: G 16; 7 actions: G 8; mz_selfplay_set_env holds each
+// environment to its shape).  mz_root_body and mz_finalize_record take the kind itself.
+constexpr int mz_game_kind(bool game, bool sp, int g) { return !game ? 0 : sp ? 2 : g == 8 ? 3 : 1; }
 template <int KS1, int JTP, int G, int LT, bool PROF, bool SP, bool HEAD = false, bool GAME = false>
 __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, const f32x4 *wstream, int nsims,
                                                           int slot0, unsigned long long *prof, SelfplayState sp,
                                                           int record, uint64_t seed, MzRootArgs ra) {
   static_assert(!HEAD || (LT != 0 && !PROF), "HEAD: trees in LDS, no phase stamps");
-  static_assert(!GAME || HEAD, "GAME: whole moves of a game environment (two players: TicTacToe, single player: CartPole)");
-  constexpr int GK = GAME ? (SP ? 2 : 1) : 0;      // the environment of a GAME launch
+  static_assert(!GAME || HEAD, "GAME: whole moves of a game environment");
+  constexpr int GK = mz_game_kind(GAME, SP, G);    // the environment of a GAME launch
+  static_assert(GK != 1 || G == 16, "TicTacToe: 9 actions");
+  constexpr bool GK2P = GK == 1 || GK == 3;        // ... is a two-player board game: mover and legal moves come from the root
   using SC = FusedSched<KS1, JTP>;
   constexpr int NB = MZ_NB, NSTEPS = SC::NSTEPS, RS = SC::RS, NRING = SC::NRING;
   static_assert(RS <= SC::FC1, "resident steps must be fc1 steps of the dynamics stage");
@@ -689,7 +705,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
   }
 
   const int nmoves = HEAD ? ra.nmoves : 1;
-  constexpr bool ENVS = HEAD && GK != 1;    // per-environment scalars (synthetic env, CartPole) kept in LDS across the moves
+  constexpr bool ENVS = HEAD && !GK2P;      // per-environment scalars (synthetic env, CartPole) kept in LDS across the moves
   if constexpr (ENVS) {
     if (tid0 < 16 && b0 + tid0 < t.B) {
       const int b = b0 + tid0;
@@ -799,7 +815,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
         my_act[i] = best;
         tr[i].len = 2;
         tr[i].legal = (t.A >= 32) ? 0xFFFFFFFFu : ((1u << t.A) - 1u);
-        if constexpr (GK == 1) {      // the root's mover and legal moves (mz_root_body left them in the staging area)
+        if constexpr (GK2P) {         // the root's mover and legal moves (mz_root_body left them in the staging area)
           tr[i].root_tp = (int)st[33];
           tr[i].tp = -tr[i].root_tp;                 // to_play at the leaf of the first descent (mcts.py:90-92)
           tr[i].legal = (uint32_t)st[34];
@@ -813,8 +829,9 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
             tm[i].N[k] = 0; tm[i].W[k] = 0.0; tm[i].R[k] = 0.f; tm[i].E[k] = (k == 0) ? 0 : -1; tm[i].TP[k] = 1;
           }
           for (int k = tl; k < have; k += TL) tm[i].X[k] = 0.0;
+          if constexpr (GK2P) { if (tl == 0) tm[i].TP[0] = (int8_t)tr[i].root_tp; }      // (lane 0 wrote node 0 above)
         } else {
-          for (int k = tl; k < have; k += TL) { tm[i].N[k] = 0; tm[i].E[k] = (k == 0) ? 0 : -1; tm[i].TP[k] = (GK == 1 && k == 0) ? (int8_t)tr[i].root_tp : (int8_t)1; }
+          for (int k = tl; k < have; k += TL) { tm[i].N[k] = 0; tm[i].E[k] = (k == 0) ? 0 : -1; tm[i].TP[k] = (GK2P && k == 0) ? (int8_t)tr[i].root_tp : (int8_t)1; }
           if (tl == 0) { tm[i].W[0] = 0.0; tm[i].R[0] = 0.f; tm[i].X[0] = 0.0; }      // the root's expansion slot
         }
         for (int k = tl; k < have; k += TL) tm[i].P[k] = (k == 0) ? 0.0 : st[k - 1];

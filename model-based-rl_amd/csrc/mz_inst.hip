@@ -24,6 +24,9 @@ MZ_GAME_VARIANT(MZ_KF)
 #ifdef MZ_INST_CART      // (the unit of MZ_CART_SHAPE) whole moves of the device CartPole environment
 MZ_CART_VARIANT(MZ_KF)
 #endif
+#ifdef MZ_INST_C4        // (the unit of MZ_C4_SHAPE) whole moves of the device Connect Four environment
+MZ_C4_VARIANTS(MZ_KF)
+#endif
 #elif defined(MZ_INST_H)
 MZ_VARIANTS_H2(MZ_KH, (MZ_INST_H))
 #else

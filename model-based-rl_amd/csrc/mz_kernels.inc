@@ -19,6 +19,8 @@
 #define MZ_GAME_SHAPE 15, 1, 16
 // whole moves of the device CartPole environment (single player, 2 actions): one more kernel of the A <= 4 row
 #define MZ_CART_SHAPE 14, 1, 4
+// whole moves of the device Connect Four environment (two players, 7 actions): two more kernels of the A <= 8 row
+#define MZ_C4_SHAPE 15, 1, 8
 
 // ---- variants of a shape S, V(S, tree placement LT, phase stamps PROF, single player SP, whole moves HEAD)
 // trees in LDS (LT 1 whole, 2 compact): both kernels; HEAD needs LDS trees, no stamps, a single player
@@ -30,11 +32,17 @@
 #define MZ_VARIANTS_FUSED(V, S)                                                                                     \
   V(S, 0, false, false, false) V(S, 0, false, true, false) V(S, 0, true, false, false) V(S, 0, true, true, false) \
   MZ_VARIANTS_H2(V, S)
-// the game kernel: (S, LT, PROF, SP, HEAD, GAME)
+// the game kernels: (S, LT, PROF, SP, HEAD, GAME); which environment a game kernel plays follows from SP and the shape
+// (mz_game_kind, mz_fused.hip.h).  TicTacToe:
 #define MZ_GAME_VARIANT(V) V((MZ_GAME_SHAPE), 2, false, false, true, true)
-// the single-player game kernel (GAME && SP): whole trees in LDS, the placement of 2 actions at every simulation count the
+// the single-player game kernel (CartPole): whole trees in LDS, the placement of 2 actions at every simulation count the
 // fused kernels take (16 trees of 1 + 63 * 2 nodes fit beside the root's working set)
 #define MZ_CART_VARIANT(V) V((MZ_CART_SHAPE), 1, false, true, true, true)
+// Connect Four, trees of NN = 1 + (sims + 1) * 7 nodes beside 53,760 bytes of static LDS (mz_fused_dyn_lds): whole trees in
+// LDS (LT 1) up to 24 simulations (106,304 bytes of dynamic LDS; 25: 110,512 > 110,080), the compact placement (LT 2) from 25
+// to 48 (107,616 bytes; 49: 110,200) -- the default 30 among them; both boundaries confirmed through mz_search_kernel_info /
+// mz_selfplay_moves_per_launch.  Other simulation counts play launch-per-step
+#define MZ_C4_VARIANTS(V) V((MZ_C4_SHAPE), 1, false, false, true, true) V((MZ_C4_SHAPE), 2, false, false, true, true)
 
 #define MZ_UNPACK(...) __VA_ARGS__      // MZ_UNPACK S: a shape tuple (KS1, JTP, G) / (G) as leading template arguments
 
@@ -47,5 +55,5 @@
 #ifdef MZ_DEV_ONLY
 #define MZ_ALL_KERNELS MZ_FUSED_ROWS_DEV(MZ_KF_ROW) MZ_H2_ROWS_DEV(MZ_KH_ROW)
 #else
-#define MZ_ALL_KERNELS MZ_FUSED_ROWS(MZ_KF_ROW) MZ_GAME_VARIANT(MZ_KG) MZ_CART_VARIANT(MZ_KG) MZ_H2_ROWS(MZ_KH_ROW)
+#define MZ_ALL_KERNELS MZ_FUSED_ROWS(MZ_KF_ROW) MZ_GAME_VARIANT(MZ_KG) MZ_CART_VARIANT(MZ_KG) MZ_C4_VARIANTS(MZ_KG) MZ_H2_ROWS(MZ_KH_ROW)
 #endif

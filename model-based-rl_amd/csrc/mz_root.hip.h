@@ -45,6 +45,8 @@ __host__ __device__ inline int mz_root_nst0(int O) { return ((O + 1 + 3) / 4 + 1
 // (parity runs); root_stage additionally receives to_play (slot 33) and the legal mask (slot 34).
 // GAME == 2: the device CartPole environment (single player, every action legal: the root's tree part is the synthetic
 // environment's); the observation is the float cast of the four float64 state words the launch keeps in envs[8..15].
+// GAME == 3: the device Connect Four environment: kind 1's two-player branches on its own observation (mz_c4_obs_cell) and
+// legal mask (mz_c4_view: the columns whose top cell is empty); the draw is always the device's.
 template <int JTP, int G, bool SELFPLAY, int GAME = 0, class STAMPF>
 __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t, const float *obs_in,
                                              const f32x4 *istream, int nst0, const SelfplayState &sp, uint64_t seed,
@@ -126,6 +128,10 @@ __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t
         if (b < t.B) {
           if constexpr (GAME == 2) {  // envs.CartPole._obs: the state as np.float32
             v = (float)((const double *)(envs + m * MZ_ENVW + 8))[k];
+            sp.obs[(size_t)b * O + k] = v;
+          } else
+          if constexpr (GAME == 3) {  // envs.ConnectFour.step: observation = turn * board, np.float32
+            v = mz_c4_obs_cell(sp.board + (size_t)b * 42, (int)sp.turn[b], k);
             sp.obs[(size_t)b * O + k] = v;
           } else
           if constexpr (GAME == 1) {  // tic_tac_toe.py:24,50: observation = turn * board, np.float32 (actors.py:134)
@@ -287,6 +293,21 @@ __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t
       if (b < t.B && tl < G) {
         const uint64_t move = envs ? (uint64_t)*(const unsigned long long *)(envs + mt * MZ_ENVW) : (uint64_t)sp.movecnt[b];
         double nz;
+        if constexpr (GAME == 3) {
+          // legal_actions() = the columns that are not full, game.to_play = env.turn
+          int to_play;
+          const uint32_t mask = mz_c4_view(sp.board + (size_t)b * 42, (int)sp.turn[b], nullptr, &to_play);
+          const bool ok = tl < A && ((mask >> tl) & 1u);
+          const double gam = ok ? mz_gamma(alpha, seed, (uint32_t)(sp.env_offset + b), move, (uint32_t)tl) : 0.0;
+          double sum = 0.0;
+          for (int a = 0; a < A; ++a) sum += __shfl(gam, a, G);
+          nz = ok ? (sum > 0.0 ? gam / sum : 1.0 / (double)__popc(mask)) : 0.0;
+          if (tl < A) t.noise[(size_t)b * A + tl] = nz;
+          __threadfence_block();
+          mz_tree_root<G, true>(t, b, tl, to_play, mask, s_lg + mt * 32, t.noise + (size_t)b * A, frac,
+                                root_stage ? root_stage + mt * 96 : nullptr);
+          if (tl == 0 && root_stage) { root_stage[mt * 96 + 33] = (double)to_play; root_stage[mt * 96 + 34] = (double)mask; }
+        } else
         if constexpr (GAME == 1) {
           // legal_actions() = the empty cells (tic_tac_toe.py:27-28), game.to_play = env.turn
           const int to_play = (int)sp.turn[b];

@@ -28,8 +28,9 @@ struct SelfplayState {
                                  // advances only its own counter): keys the RNG and the ring slot
   // ---- a real game as the environment (mz_selfplay_set_env): TicTacToe, custom_environments/tic_tac_toe.py:5-76
   int env_kind;          // 0 = synthetic fixed-length episodes (above), 1 = TicTacToe (two players, 9 cells, 9 actions),
-                         // 2 = CartPole (single player, 4 observations, 2 actions, episode_len = the time limit)
-  int8_t *board;         // [B][9] env.board: 0 empty, +1 / -1 the two players' marks
+                         // 2 = CartPole (single player, 4 observations, 2 actions, episode_len = the time limit),
+                         // 3 = Connect Four (two players, 42 cells, 7 actions)
+  int8_t *board;         // [B][9] env.board: 0 empty, +1 / -1 the two players' marks (Connect Four: [B][42], cell 7 * row + col)
   int8_t *turn;          // [B] env.turn == game.to_play: +1 or -1, the player about to move
   uint8_t *legal;        // [B][A] legal_actions() of the current position as a mask (actors.py:141)
   int8_t *to_play;       // [B] game.to_play of the current move (root.expand's to_play, actors.py:142)
@@ -311,4 +312,88 @@ static __global__ void k_cartpole_step_record(TreeView tv, SelfplayState sp, int
   for (int k = 0; k < 4; ++k) sp.cart[(size_t)b * 4 + k] = st[k];
   if (done) { sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next; }
   else sp.t[b] = tt + 1;
+}
+
+
+// ---- Connect Four on the device (envs.ConnectFour is the definition: 6 rows of 7 columns, cell 7 * row + col, row 0 at the
+// bottom; TicTacToe's conventions otherwise).  The rules are integer operations on the 42 int8 cells, so host and device
+// agree by construction; the two functions below are all the device forms know of the game.
+// env.step(col) for the mover `turn` on bd[42], the column not full (the search only offers legal columns): the stone lands
+// on the lowest empty cell; *won = a line of at least four of the mover's stones passes through it (vertical, horizontal,
+// the two diagonals); returns done = won or no empty cell left (a full board = a full top row).
+__host__ __device__ inline bool mz_c4_step(int8_t *bd, int turn, int col, bool *won) {
+  int row = 0;
+  while (row < 5 && bd[7 * row + col] != 0) ++row;
+  bd[7 * row + col] = (int8_t)turn;
+  const int dr[4] = {1, 0, 1, 1}, dc[4] = {0, 1, 1, -1};
+  bool w = false;
+  for (int d = 0; d < 4; ++d) {
+    int n = 0;
+    for (int sg = -1; sg <= 1; sg += 2) {
+      int r = row + sg * dr[d], c = col + sg * dc[d];
+      while (r >= 0 && r < 6 && c >= 0 && c < 7 && bd[7 * r + c] == turn) { ++n; r += sg * dr[d]; c += sg * dc[d]; }
+    }
+    w = w || n >= 3;
+  }
+  *won = w;
+  bool full = true;
+  for (int c = 0; c < 7; ++c) full = full && bd[35 + c] != 0;
+  return w || full;
+}
+// What Actor.play_game reads before a move: legal_actions() as a mask (the columns whose top cell is empty) and
+// game.to_play = env.turn; obs (optional) [42] = turn * board as float32, cell k of it is mz_c4_obs_cell
+__host__ __device__ inline float mz_c4_obs_cell(const int8_t *bd, int turn, int k) { return (float)(turn * (int)bd[k]); }
+__host__ __device__ inline uint32_t mz_c4_view(const int8_t *bd, int turn, float *obs, int *to_play) {
+  uint32_t mask = 0;
+  for (int c = 0; c < 7; ++c) mask |= (bd[35 + c] == 0 ? 1u : 0u) << c;
+  if (obs) for (int k = 0; k < 42; ++k) obs[k] = mz_c4_obs_cell(bd, turn, k);
+  *to_play = turn;
+  return mask;
+}
+
+static __global__ void k_c4_observe(SelfplayState sp, int B, int A) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int to_play;
+  const uint32_t mask = mz_c4_view(sp.board + (size_t)b * 42, (int)sp.turn[b], sp.obs + (size_t)b * 42, &to_play);
+  for (int a = 0; a < A; ++a) sp.legal[(size_t)b * A + a] = (uint8_t)((mask >> a) & 1u);
+  sp.to_play[b] = (int8_t)to_play;
+}
+
+// Game.apply on env.step for environment b, by ONE lane, and the tail of its experience record -- TicTacToe's sequence
+// (mz_ttt_apply) on Connect Four's rules: on done the board is cleared, the turn is +1, the step 0, the episode advances
+// and the next game's temperature is evaluated.
+__device__ __forceinline__ void mz_c4_apply(const SelfplayState &sp, int b, int action, double root_value, double error,
+                                            float *rec, int A) {
+  const int O = 42;
+  const int turn = sp.turn[b], t = sp.t[b], ep = sp.episode[b];
+  int8_t *bd = sp.board + (size_t)b * 42;
+  bool won;
+  const int done = mz_c4_step(bd, turn, action, &won) ? 1 : 0;
+  mz_rec_put_double(rec + O + A + 0, root_value);
+  mz_rec_put_double(rec + O + A + 2, error);
+  rec[O + A + 4] = won ? 1.f : 0.f;
+  int32_t *ri = (int32_t *)(rec + O + A + 5);
+  ri[0] = action; ri[1] = done | (turn < 0 ? 2 : 0); ri[2] = t; ri[3] = sp.env_offset + b; ri[4] = ep;
+  if (done) {
+    for (int k = 0; k < 42; ++k) bd[k] = 0;
+    sp.turn[b] = 1; sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next;
+  } else {
+    sp.turn[b] = (int8_t)(-turn); sp.t[b] = t + 1;
+  }
+}
+
+// End of a move of the launch-per-step form: finalize the tree, write the record (pre-step observation), step the game
+static __global__ void k_c4_step_record(TreeView tv, SelfplayState sp, int B, int A, uint64_t seed) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long move = sp.movecnt[b];
+  sp.movecnt[b] = move + 1ull;
+  mz_finalize_tree(tv, b, sp.temp, nullptr, seed, move, sp.env_offset, sp.action, sp.child_visits, sp.root_value,
+                   sp.error, nullptr);
+  const int O = 42;
+  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
+  for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
+  for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
+  mz_c4_apply(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A);
 }

@@ -46,6 +46,12 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
     HIPCHECK(hipMemsetAsync(sp.board, 0, (size_t)e->Bp * 9, s));
     HIPCHECK(hipMemsetAsync(sp.turn, 1, (size_t)e->Bp, s));
   }
+  if (sp.env_kind == 3) {      // Connect Four: env.reset() everywhere; a game ends on a line of four or a full board
+    sp.episode_len = 42;
+    HIPCHECK(hipMemsetAsync(sp.t, 0, (size_t)e->Bp * 4, s));
+    HIPCHECK(hipMemsetAsync(sp.board, 0, (size_t)e->Bp * 42, s));
+    HIPCHECK(hipMemsetAsync(sp.turn, 1, (size_t)e->Bp, s));
+  }
   if (sp.env_kind == 2) {      // CartPole: episode_len is the time limit; every environment starts episode 0 at step 0
     std::vector<double> st((size_t)e->Bp * 4, 0.0);
     for (int b = 0; b < e->B; ++b)
@@ -82,8 +88,9 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
 static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
-  const bool cart = sp.env_kind == 2;
+  const bool cart = sp.env_kind == 2, c4 = sp.env_kind == 3;
   if (cart) hipLaunchKernelGGL(k_cartpole_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
+  else if (c4) hipLaunchKernelGGL(k_c4_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
   else hipLaunchKernelGGL(k_ttt_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
   if (launch_root(e, sp.obs, false, s)) return -1;
   if (!e->draws_noise)
@@ -94,6 +101,7 @@ static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
               e->cfg.root_exploration_fraction, 1);
   if (launch_search(e, o, true, s)) return -1;
   if (cart) hipLaunchKernelGGL(k_cartpole_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
+  else if (c4) hipLaunchKernelGGL(k_c4_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
   else hipLaunchKernelGGL(k_ttt_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
   HIPCHECK(hipGetLastError());
   return 0;
@@ -161,6 +169,8 @@ int mz_selfplay_set_obs(mz_engine *e, int uint8_obs, const float *obs_min, const
   if (uint8_obs == 2 && sp.env_kind) return fail("mz_selfplay_set_obs: packed byte observations are for the synthetic -ram- environments");
   if (sp.env_kind == 2 && (uint8_obs || obs_min))
     return fail("mz_selfplay_set_obs: the CartPole environment has neither byte observations nor --norm_obs");
+  if (sp.env_kind == 3 && (uint8_obs || obs_min))
+    return fail("mz_selfplay_set_obs: the Connect Four environment has neither byte observations nor --norm_obs");
   if (selfplay_alloc(e)) return -1;
   if (sp.moves_host != sp.drained) return fail("mz_selfplay_set_obs: drain the ring first (the record layout may change)");
   sp.obs_u8 = uint8_obs;
@@ -197,11 +207,19 @@ int mz_selfplay_export_trees(mz_engine *e, int keep) {
 // the reference's rules (custom_environments/tic_tac_toe.py:5-76) -- needs obs_dim 9, action_space 9 and a two-player
 // engine; observations, legal moves, wins, draws and the alternating to_play all live on the device.  kind 2: CartPole
 // (envs.CartPole: CartPole-v1 / -v0) -- needs obs_dim 4, action_space 2 and a single-player engine; the float64 state,
-// termination and the time limit (mz_selfplay_reset's episode_len) live on the device.  Call before mz_selfplay_reset.
+// termination and the time limit (mz_selfplay_reset's episode_len) live on the device.  kind 3: Connect Four
+// (envs.ConnectFour) -- needs obs_dim 42, action_space 7 and a two-player engine; board, turn, full columns, lines of four
+// and draws live on the device.  Call before mz_selfplay_reset.
 int mz_selfplay_set_env(mz_engine *e, int kind) {
   if (!e) return fail("mz_selfplay_set_env: null engine");
   MZ_ENTER(e);
-  if (kind < 0 || kind > 2) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole)", kind);
+  if (kind < 0 || kind > 3) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole, 3 Connect Four)", kind);
+  if (kind == 3 && (e->O != 42 || e->A != 7 || !e->cfg.two_players))
+    return fail("mz_selfplay_set_env: Connect Four needs obs_dim 42, action_space 7 and two_players (got %d, %d, %d)", e->O, e->A, e->cfg.two_players);
+  if (kind == 3 && e->sp.obs_u8 == 2)
+    return fail("mz_selfplay_set_env: packed byte observations are for the synthetic -ram- environments");
+  if (kind == 3 && (e->sp.obs_u8 || e->sp.obs_min))
+    return fail("mz_selfplay_set_env: the Connect Four environment has neither byte observations nor --norm_obs");
   if (kind == 2 && (e->O != 4 || e->A != 2 || e->cfg.two_players))
     return fail("mz_selfplay_set_env: CartPole needs obs_dim 4, action_space 2 and a single player (got %d, %d, two_players %d)", e->O, e->A, e->cfg.two_players);
   if (kind == 2 && (e->sp.obs_u8 || e->sp.obs_min))
@@ -211,8 +229,8 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
   if (selfplay_alloc(e)) return -1;
   HIPCHECK(hipDeviceSynchronize());
   SelfplayState &sp = e->sp;
-  if (kind == 1 && !sp.board) {
-    if (dmalloc(e, &sp.board, (size_t)e->Bp * 9) || dmalloc(e, &sp.turn, (size_t)e->Bp) ||
+  if ((kind == 1 || kind == 3) && !sp.board) {      // (the two board games differ in obs_dim: an engine plays one of them)
+    if (dmalloc(e, &sp.board, (size_t)e->Bp * (kind == 3 ? 42 : 9)) || dmalloc(e, &sp.turn, (size_t)e->Bp) ||
         dmalloc(e, &sp.legal, (size_t)e->Bp * e->A) || dmalloc(e, &sp.to_play, (size_t)e->Bp) ||
         dmalloc(e, &e->draw_uniform, (size_t)e->Bp))
       return -1;
@@ -600,6 +618,47 @@ int mz_selfplay_set_env_state(mz_engine *e, int env, const double *state) {
   if (env < 0 || env >= e->B) return fail("mz_selfplay_set_env_state: environment %d outside [0, %d)", env, e->B);
   HIPCHECK(hipDeviceSynchronize());
   HIPCHECK(hipMemcpy(e->sp.cart + (size_t)env * 4, state, 4 * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// ---- the Connect Four environment's state (include/mz_engine_debug.h)
+int mz_selfplay_board_state(mz_engine *e, int8_t *out) {
+  if (!e || !out) return fail("mz_selfplay_board_state: null argument");
+  MZ_ENTER(e);
+  if (e->sp.env_kind != 3 || !e->sp.ready) return fail("mz_selfplay_board_state: the Connect Four environment is not set up (mz_selfplay_set_env, mz_selfplay_reset)");
+  HIPCHECK(hipDeviceSynchronize());
+  const size_t B = (size_t)e->B;
+  std::vector<int8_t> bd(B * 42), turn(B);
+  std::vector<int32_t> t(B);
+  HIPCHECK(hipMemcpy(bd.data(), e->sp.board, B * 42, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(turn.data(), e->sp.turn, B, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(t.data(), e->sp.t, B * 4, hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < B; ++b) {
+    for (int k = 0; k < 42; ++k) out[b * 44 + k] = bd[b * 42 + k];
+    out[b * 44 + 42] = turn[b];
+    out[b * 44 + 43] = (int8_t)t[b];
+  }
+  return 0;
+}
+int mz_selfplay_set_board_state(mz_engine *e, int env, const int8_t *cells42, int turn) {
+  if (!e || !cells42) return fail("mz_selfplay_set_board_state: null argument");
+  MZ_ENTER(e);
+  if (e->sp.env_kind != 3 || !e->sp.ready) return fail("mz_selfplay_set_board_state: the Connect Four environment is not set up (mz_selfplay_set_env, mz_selfplay_reset)");
+  if (env < 0 || env >= e->B) return fail("mz_selfplay_set_board_state: environment %d outside [0, %d)", env, e->B);
+  if (turn != 1 && turn != -1) return fail("mz_selfplay_set_board_state: turn %d (+1 or -1)", turn);
+  int32_t stones = 0;
+  bool open = false;
+  for (int k = 0; k < 42; ++k) {
+    if (cells42[k] < -1 || cells42[k] > 1) return fail("mz_selfplay_set_board_state: cell %d holds %d (0, +1 or -1)", k, (int)cells42[k]);
+    stones += cells42[k] != 0;
+    open = open || (k >= 35 && cells42[k] == 0);
+  }
+  if (!open) return fail("mz_selfplay_set_board_state: every column is full, the position has no move");
+  const int8_t tn = (int8_t)turn;
+  HIPCHECK(hipDeviceSynchronize());
+  HIPCHECK(hipMemcpy(e->sp.board + (size_t)env * 42, cells42, 42, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(e->sp.turn + env, &tn, 1, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(e->sp.t + env, &stones, 4, hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -459,11 +459,12 @@ class Engine(object):
     self.obs_packed = bool(packed)
     self.rec_floats = self.lib.mz_selfplay_rec_floats(self._h)
 
-  ENVS = {'synthetic': 0, 'tictactoe': 1, 'cartpole': 2}
+  ENVS = {'synthetic': 0, 'tictactoe': 1, 'cartpole': 2, 'connect_four': 3}
 
   def selfplay_set_env(self, kind):
-    """'synthetic' (default), 'tictactoe' (the reference's custom_environments/tic_tac_toe.py on the device) or 'cartpole'
-    (envs.CartPole on the device; selfplay_reset's episode_len is its time limit); before selfplay_reset"""
+    """'synthetic' (default), 'tictactoe' (the reference's custom_environments/tic_tac_toe.py on the device), 'cartpole'
+    (envs.CartPole on the device; selfplay_reset's episode_len is its time limit) or 'connect_four' (envs.ConnectFour on
+    the device); before selfplay_reset"""
     _abi.check(self.lib.mz_selfplay_set_env(self._h, self.ENVS[kind] if isinstance(kind, str) else int(kind)), 'mz_selfplay_set_env')
 
   def selfplay_set_draws(self, noise=None, uniform=None):
@@ -577,6 +578,18 @@ class Engine(object):
     """replace the state of device CartPole environment `env` (tests: a start next to a threshold); after selfplay_reset"""
     st = np.ascontiguousarray(state, np.float64).reshape(4)
     _abi.check(self.lib.mz_selfplay_set_env_state(self._h, int(env), st.ctypes.data_as(C.c_void_p)), 'mz_selfplay_set_env_state')
+
+  def selfplay_board_state(self):
+    """[B, 44] int8: 42 cells, turn and step of every device Connect Four environment (synchronous)"""
+    out = np.zeros((self.B, 44), np.int8)
+    _abi.check(self.lib.mz_selfplay_board_state(self._h, out.ctypes.data_as(C.c_void_p)), 'mz_selfplay_board_state')
+    return out
+
+  def selfplay_set_board_state(self, env, board, turn):
+    """place a position into device Connect Four environment `env` (its step = the number of stones); after selfplay_reset"""
+    bd = np.ascontiguousarray(board, np.int8).reshape(42)
+    _abi.check(self.lib.mz_selfplay_set_board_state(self._h, int(env), bd.ctypes.data_as(C.c_void_p), int(turn)),
+               'mz_selfplay_set_board_state')
 
   def synth_obs(self, env, episode, t):
     obs = np.zeros(self.O, np.float32)

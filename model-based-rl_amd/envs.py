@@ -3,7 +3,9 @@
 winning move, draw after nine moves).  CartPole is the classic-control task the reference reaches through gym.make
 ('CartPole-v1' / 'CartPole-v0'); gym is not installed, so the class below IS its definition and the device environment
 (csrc/mz_selfplay.hip.h, mz_cartpole_step) follows it bit for bit.  Every other reference environment (Box2D, ALE) is
-unavailable; its SHAPE is served by the on-device synthetic env (csrc/mz_selfplay.hip.h)."""
+unavailable; its SHAPE is served by the on-device synthetic env (csrc/mz_selfplay.hip.h).  ConnectFour is not among the
+reference's environments: the class below is its definition, a second two-player board game next to TicTacToe with the
+same conventions, and the device environment (csrc/mz_selfplay.hip.h, mz_c4_step) follows it move for move."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -46,6 +48,61 @@ class TicTacToe(object):
     self._elapsed_steps += 1
     self.turn = -self.turn
     return self.turn * self.board.copy(), int(won), done, {'result': result}
+
+
+class ConnectFour(object):
+  """Connect Four on the standard board of 6 rows and 7 columns, with TicTacToe's conventions (gym-0.x API, observation =
+  turn * board for the player about to move, reward 1 to the mover for the winning move).  board[7 * row + col], row 0 at
+  the bottom: 0 empty, +1 / -1 the two players' stones.  An action is a column; the stone lands on its lowest empty cell."""
+  ROWS, COLS = 6, 7
+  _DIRECTIONS = ((1, 0), (0, 1), (1, 1), (1, -1))      # (d row, d col): vertical, horizontal, rising and falling diagonal
+
+  def __init__(self):
+    self.action_space = SimpleNamespace(n=7)
+    self.observation_space = np.zeros(42, dtype=np.int32)
+    self.reset()
+
+  def seed(self, seed):
+    return
+
+  def reset(self):
+    self.board = np.zeros(42, dtype=np.int32)
+    self.turn = 1
+    self._elapsed_steps = 0
+    return self.board.copy()
+
+  def set_position(self, board42, turn):
+    """place a position (it need not be reachable): the step count is the number of stones"""
+    self.board = np.array(board42, dtype=np.int32).reshape(42).copy()
+    self.turn = int(turn)
+    self._elapsed_steps = int(np.count_nonzero(self.board))
+
+  def legal_actions(self):
+    return np.flatnonzero(self.board[35:42] == 0)
+
+  def _run(self, row, col, drow, dcol):
+    """stones of the mover's colour next to (row, col) along (drow, dcol), not counting (row, col) itself"""
+    n, r, c = 0, row + drow, col + dcol
+    while 0 <= r < 6 and 0 <= c < 7 and self.board[7 * r + c] == self.turn:
+      n, r, c = n + 1, r + drow, c + dcol
+    return n
+
+  def step(self, action):
+    col = int(action)
+    if not 0 <= col < 7 or self.board[35 + col] != 0:
+      raise ValueError('column %d is full or does not exist' % col)
+    row = int(np.flatnonzero(self.board[col::7] == 0)[0])
+    self.board[7 * row + col] = self.turn
+    won = any(self._run(row, col, dr, dc) + self._run(row, col, -dr, -dc) >= 3 for dr, dc in self._DIRECTIONS)
+    done = won or not np.any(self.board == 0)
+    result = None
+    if won:
+      result = 'player 1 wins' if self.turn == 1 else 'player 2 wins'
+    elif done:
+      result = 'draw'
+    self._elapsed_steps += 1
+    self.turn = -self.turn
+    return self.turn * self.board.copy(), int(won), bool(done), {'result': result}
 
 
 # sin / cos of the pole angle as fixed Taylor polynomials in z = theta * theta, Horner from the highest term down with plain
@@ -133,6 +190,8 @@ class CartPole(object):
 def get_environment(config):
   if config.environment == 'TicTacToe':
     return TicTacToe()
+  if config.environment == 'ConnectFour':
+    return ConnectFour()
   if config.environment in CARTPOLE_TIME_LIMITS:
     return CartPole(CARTPOLE_TIME_LIMITS[config.environment])
   raise NotImplementedError('%s needs gym/ALE/Box2D, which are not installed; the GPU actor serves its shape with '
