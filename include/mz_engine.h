@@ -234,6 +234,52 @@ int mz_eval_walk(mz_engine *e, int max_actions, const double *temperature, const
 int mz_eval_lookahead(mz_engine *e, int mode, int32_t *action, float *pred_reward, double *child_visits, float *row_reward,
                       float *row_value, void *stream);
 
+/* Evaluation games that live on the device from the first move to the last (Evaluator.play_game's loop, evaluate.py:242-385,
+ * for B games in lock-step): the host touches no game between moves.  One evaluation state per engine, separate from the
+ * self-play loop's.  Game b of the engine is the game with seed env_id_offset + b.
+ *
+ * mz_eval_env_reset: kind 1 TicTacToe, 2 CartPole, 3 Connect Four (the device rules of mz_selfplay_set_env; the engine must
+ * have that game's obs_dim / action_space / two_players).  max_steps: the game is cut when its step count reaches it
+ * (evaluate.py:372); time_limit: CartPole's TimeLimit (500 / 200), ignored otherwise; random_opp +1 / -1: that player's moves
+ * are the random opponent's (two players), 0: none; keep_history != 0: per-move logs are kept ([B][cap] per entry, cap =
+ * min(max_steps, the game's longest: 9 / 42 / time_limit), mz_eval_env_log_capacity).  Every game starts from env.reset();
+ * CartPole's start state is the counter RNG's mz_cartpole_reset_state(env_id_offset + b, episode 0).  Synchronous.
+ *
+ * mz_eval_env_set_draws (after reset, before the first move; parity runs): every draw given by the caller instead of the
+ * counter RNG, as [dev] arrays the caller keeps alive until the games are over; any may be NULL.  walk [B][walk_moves][walk_m]
+ * float64: the uniforms of mz_eval_walk (walk_m == max_actions); noise [B][noise_moves][A] float64: the Dirichlet draw of
+ * every move at the legal positions; opp [B][opp_n] int32: the random opponent's choices in the order it makes them, each
+ * an index into the legal actions of the move's root position; start_states [B][4] float64: CartPole's start states.
+ * Moves past the given ones draw zeros.
+ *
+ * mz_eval_env_moves: n whole moves enqueued on the stream, each: observe (state -> obs / legal / to_play; a finished game
+ * gets a zero observation, all actions legal, to_play +1) -> mz_initial_inference -> mz_root_prepare (noise_on: the given
+ * draw, or the device Dirichlet keyed by the move) -> mode 0: mz_search + mz_eval_walk (max_actions, temperature; device
+ * uniforms under MZ_RNG_EVAL keyed by the move) + mz_finalize, mode 1 / 2: mz_eval_lookahead (--only_prior / --only_value)
+ * -> apply (evaluate.py:331-374 on the device rules: the predicted value, root value and child visits once, then per
+ * walked action the predicted reward, the random opponent's replacement -- drawn from the legal list OF THE MOVE'S ROOT
+ * POSITION, the reference's stale list, index min(floor(u * n), n - 1) with u from the counter RNG under MZ_RNG_OPP keyed
+ * (seed, game's seed, move, step) -- the env step, the cut at done or max_steps with the sign flip of an opponent's last
+ * reward; then the lexicographic maximum of the search-depth lists).  No host synchronisation between the moves; one
+ * copy at the end returns the number of games still live in *live_out [host].  The first call sizes the walk's buffers
+ * and uploads the temperature, and so synchronises once more.  Connect Four takes max_actions == 1 only.
+ *
+ * mz_eval_env_results (synchronous, [host] arrays, any may be NULL): step [B] int32 (game length), n_moves [B] int32,
+ * acc [5][B] float64 (sum of rewards, of predicted rewards, of predicted values, of root values -- added in move order --
+ * and the mean of the lexicographic-maximum depth list), depth_max [B][num_simulations] int32 (that list; one entry with
+ * modes 1 / 2); the logs, kept with keep_history: per applied action [B][cap] actions int32 (the opponent's included),
+ * rewards float64, mover int8 (+1 / -1, doubled on the step env.step itself reported done), pred_rewards float32; per move [B][cap] pred_values float32, root_values float64,
+ * child_visits [B][cap][A] float64, n_actions int32, depths [B][cap][num_simulations] int32 (mode 0). */
+int mz_eval_env_reset(mz_engine *e, int kind, int max_steps, int time_limit, int random_opp, int keep_history, void *stream);
+int mz_eval_env_set_draws(mz_engine *e, const double *walk, int walk_moves, int walk_m, const double *noise, int noise_moves,
+                          const int32_t *opp, int opp_n, const double *start_states, void *stream);
+int mz_eval_env_moves(mz_engine *e, int n, int mode, int max_actions, double temperature, int noise_on, int *live_out,
+                      void *stream);
+int mz_eval_env_results(mz_engine *e, int32_t *step, int32_t *n_moves, double *acc, int32_t *depth_max, int32_t *actions,
+                        double *rewards, int8_t *mover, float *pred_rewards, float *pred_values, double *root_values,
+                        double *child_visits, int32_t *n_actions, int32_t *depths, void *stream);
+int mz_eval_env_log_capacity(const mz_engine *e);
+
 /* Raw tree dump (Node objects of mcts.py:28-45 in SoA form) to [host] arrays, synchronous.
  * Each per-node array is [B][NN]; minmax [B][2]; legal_mask [B] (bit a = root child a exists);
  * noise [B][A] (the Dirichlet draw last mixed in).  Any pointer may be NULL. */

@@ -196,7 +196,8 @@ def make_config(argv=None, **overrides):
 
 def get_evaluation_args(argv=None):
   """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
-  engine; default min(num_games, 4096)) and --out (a JSON summary).  Checkpoints are saves_dir + net for every pair."""
+  engine; default min(num_games, 4096)), --out (a JSON summary) and --device_env / --keep_history (the games on the device
+  environments, evaluate.py).  Checkpoints are saves_dir + net for every pair."""
   p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
   a = p.add_argument
   a('--seed', type=int, default=None)
@@ -226,6 +227,9 @@ def get_evaluation_args(argv=None):
   a('--verbose', action='store_true')
   a('--batch', type=int, default=None, help='games played in lock-step on one engine (default: min(num_games, 4096))')
   a('--out', type=str, default=None, help='write the summary of every configuration to this JSON file')
+  a('--device_env', action='store_true',
+    help='play the games on the device environments (TicTacToe, ConnectFour, CartPole-v0 / -v1): no host work between moves')
+  a('--keep_history', action='store_true', help='--device_env: keep the per-move lists of every game, not only its summary')
   args = p.parse_args(argv)
   if args.batch is None:
     args.batch = min(args.num_games, 4096)

@@ -31,6 +31,7 @@
 #include "mz_learner.hip.h"
 #include "mz_fcl.hip.h"
 #include "mz_eval.hip.h"
+#include "mz_eval_env.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
@@ -163,6 +164,10 @@ struct mz_engine {
   bool draws_noise = false, draws_set = false;
   std::vector<float> obs_norm_host;
   float *eval_rows = nullptr;       // mz_eval_lookahead's scratch [B*A][50 + A + 2] (hidden, logits, reward, value), first use
+  EvalState ev;                     // evaluation games on the device environments (mz_eval_env_*; mz_eval_env.hip.h)
+  unsigned long long ev_moves = 0;  // moves enqueued since mz_eval_env_reset: keys the device draws, indexes the given ones
+  double ev_temp = 0.0;             // the temperature es.temp holds
+  bool ev_temp_set = false;
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -939,6 +944,7 @@ int mz_create(const mz_config *cfg, mz_engine **out) {
     return fail("mz_create: stream creation failed");
   }
   memset(&e->sp, 0, sizeof e->sp);
+  memset(&e->ev, 0, sizeof e->ev);
   *out = e;
   return 0;
 }
@@ -1612,6 +1618,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 }
 
 #include "mz_selfplay_abi.inc"
+#include "mz_eval_abi.inc"
 #include "mz_fcl_abi.inc"
 
 }  // extern "C"

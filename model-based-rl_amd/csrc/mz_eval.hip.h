@@ -8,6 +8,8 @@
 //   k_eval_choose_value  --only_value's choice over those rows (evaluate.py:286-303), one thread per tree
 //   k_eval_choose_prior  --only_prior's choice over the root priors (evaluate.py:278-284), one thread per tree
 //
+// The games that live on the device environments (their state, k_eval_observe, k_eval_apply) are in mz_eval_env.hip.h.
+//
 // A lookahead move is two launches: rows then choice (--only_value), choice then one row per tree (--only_prior).  The rows
 // of one tree straddle 16-row workgroup tiles for A = 9 and 18, so the choice is a second per-tree kernel over the [B][A]
 // reward / value rows instead of a reduction inside the network kernel.

@@ -13,6 +13,7 @@
 #define MZ_RNG_ACTION 4u
 #define MZ_RNG_EVAL 5u       // evaluation walk (mz_eval.hip.h): one uniform per applied action, counter (env, move, step)
 #define MZ_RNG_ENV 6u        // start state of a device environment's episode (mz_cartpole_reset_state): counter (env, episode, 0)
+#define MZ_RNG_OPP 7u        // the random opponent of a device evaluation game (k_eval_apply): counter (env = the game's seed, move, step)
 
 struct mz_u4 { uint32_t x, y, z, w; };
 

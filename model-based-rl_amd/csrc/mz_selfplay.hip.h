@@ -163,6 +163,19 @@ static __global__ void k_ttt_observe(SelfplayState sp, int B, int A) {
   sp.to_play[b] = (int8_t)turn;
 }
 
+// env.step(action) (tic_tac_toe.py:30-51) for the mover `turn` on bd[9], t = the elapsed steps before this move: the mark
+// goes on the cell; *won = a line through it sums to 3 * turn; returns done = won or the ninth move (tic_tac_toe.py:37).
+// The one statement of the rules every device form calls.
+__host__ __device__ inline bool mz_ttt_step(int8_t *bd, int turn, int action, int t, bool *won) {
+  bd[action] = (int8_t)turn;
+  const int r0 = 3 * (action / 3), c0 = action % 3;
+  bool w = (bd[r0] + bd[r0 + 1] + bd[r0 + 2] == 3 * turn) || (bd[c0] + bd[c0 + 3] + bd[c0 + 6] == 3 * turn);
+  if (action % 4 == 0) w = w || (bd[0] + bd[4] + bd[8] == 3 * turn);
+  if (action == 2 || action == 4 || action == 6) w = w || (bd[2] + bd[4] + bd[6] == 3 * turn);
+  *won = w;
+  return w || t == 8;
+}
+
 // Game.apply (game.py:79-104) on env.step (tic_tac_toe.py:30-51) for environment b, by ONE lane, and the tail of its
 // experience record (root value, error, reward, action, flags with the mover, step, env id, episode).
 __device__ __forceinline__ void mz_ttt_apply(const SelfplayState &sp, int b, int action, double root_value, double error,
@@ -170,12 +183,8 @@ __device__ __forceinline__ void mz_ttt_apply(const SelfplayState &sp, int b, int
   const int O = 9;
   const int turn = sp.turn[b], t = sp.t[b], ep = sp.episode[b];
   int8_t *bd = sp.board + (size_t)b * 9;
-  bd[action] = (int8_t)turn;
-  const int r0 = 3 * (action / 3), c0 = action % 3;
-  bool won = (bd[r0] + bd[r0 + 1] + bd[r0 + 2] == 3 * turn) || (bd[c0] + bd[c0 + 3] + bd[c0 + 6] == 3 * turn);
-  if (action % 4 == 0) won = won || (bd[0] + bd[4] + bd[8] == 3 * turn);
-  if (action == 2 || action == 4 || action == 6) won = won || (bd[2] + bd[4] + bd[6] == 3 * turn);
-  const int done = (won || t == 8) ? 1 : 0;           // tic_tac_toe.py:37 (elapsed steps before this move)
+  bool won;
+  const int done = mz_ttt_step(bd, turn, action, t, &won) ? 1 : 0;
   mz_rec_put_double(rec + O + A + 0, root_value);
   mz_rec_put_double(rec + O + A + 2, error);
   rec[O + A + 4] = won ? 1.f : 0.f;

@@ -405,6 +405,63 @@ class Engine(object):
                'mz_eval_lookahead')
     return out
 
+  # ---- evaluation games on the device environments (mz_eval_env_*, include/mz_engine.h)
+  EVAL_ENVS = {'TicTacToe': 1, 'CartPole-v0': 2, 'CartPole-v1': 2, 'ConnectFour': 3}
+
+  def eval_env_reset(self, kind, max_steps, time_limit=0, random_opp=None, keep_history=False):
+    """mz_eval_env_reset: B evaluation games of `kind` (an EVAL_ENVS name or 1 / 2 / 3) at their start; game b has the seed
+    env_id_offset + b.  random_opp: +1 / -1 / None."""
+    k = self.EVAL_ENVS[kind] if isinstance(kind, str) else int(kind)
+    _abi.check(self.lib.mz_eval_env_reset(self._h, k, int(max_steps), int(time_limit), int(random_opp or 0),
+                                          int(bool(keep_history)), self.stream), 'mz_eval_env_reset')
+    self.eval_log_cap = int(self.lib.mz_eval_env_log_capacity(self._h))
+    self._eval_keep = bool(keep_history)
+    self._eval_draws = None
+
+  def eval_env_set_draws(self, walk=None, noise=None, opp=None, start_states=None):
+    """mz_eval_env_set_draws: walk [B, moves, M] float64, noise [B, moves, A] float64, opp [B, n] int32, start_states [B, 4]
+    float64 (CartPole); uploaded once, kept alive by this object until the next reset"""
+    dev = lambda x, dt: None if x is None else torch.as_tensor(np.ascontiguousarray(x)).to(self.device, dt).contiguous()
+    w, nz, op, st = dev(walk, torch.float64), dev(noise, torch.float64), dev(opp, torch.int32), dev(start_states, torch.float64)
+    for t, shape in ((w, (self.B, None, None)), (nz, (self.B, None, self.A)), (op, (self.B, None)), (st, (self.B, 4))):
+      if t is not None and (t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise ValueError('eval_env_set_draws: shape %s does not match %s' % (tuple(t.shape), shape))
+    self._eval_draws = (w, nz, op, st)
+    _abi.check(self.lib.mz_eval_env_set_draws(
+        self._h, _ptr(w), 0 if w is None else w.shape[1], 0 if w is None else w.shape[2], _ptr(nz),
+        0 if nz is None else nz.shape[1], _ptr(op), 0 if op is None else op.shape[1], _ptr(st), self.stream), 'mz_eval_env_set_draws')
+
+  def eval_env_moves(self, n, mode=0, max_actions=1, temperature=0.0, noise_on=False):
+    """mz_eval_env_moves: n whole moves enqueued back to back, one synchronisation at the end; returns the games still live.
+    mode: 0 search + walk, 'only_prior' / 1, 'only_value' / 2."""
+    m = self.EVAL_MODES[mode] if isinstance(mode, str) else int(mode)
+    live = C.c_int(0)
+    _abi.check(self.lib.mz_eval_env_moves(self._h, int(n), m, int(max_actions), float(temperature), int(bool(noise_on)),
+                                          C.byref(live), self.stream), 'mz_eval_env_moves')
+    return int(live.value)
+
+  def eval_env_results(self, logs=None):
+    """mz_eval_env_results -> dict of numpy arrays: step, n_moves [B], sum_reward, sum_pred_reward, sum_pred_value,
+    sum_root_value, depth_mean [B] float64, depth_max [B, sims]; with logs (default: whether they were kept) also actions,
+    rewards, mover, pred_rewards, pred_values, root_values, n_actions [B, cap], child_visits [B, cap, A], depths [B, cap, sims]"""
+    B, A, L, S = self.B, self.A, self.eval_log_cap, self.sims
+    logs = self._eval_keep if logs is None else bool(logs)
+    out = dict(step=np.zeros(B, np.int32), n_moves=np.zeros(B, np.int32), acc=np.zeros((5, B), np.float64),
+               depth_max=np.zeros((B, S), np.int32))
+    names = ['step', 'n_moves', 'acc', 'depth_max']
+    if logs:
+      out.update(actions=np.zeros((B, L), np.int32), rewards=np.zeros((B, L), np.float64), mover=np.zeros((B, L), np.int8),
+                 pred_rewards=np.zeros((B, L), np.float32), pred_values=np.zeros((B, L), np.float32),
+                 root_values=np.zeros((B, L), np.float64), child_visits=np.zeros((B, L, A), np.float64),
+                 n_actions=np.zeros((B, L), np.int32), depths=np.zeros((B, L, S), np.int32))
+      names += ['actions', 'rewards', 'mover', 'pred_rewards', 'pred_values', 'root_values', 'child_visits', 'n_actions', 'depths']
+    ptrs = [out[k].ctypes.data_as(C.c_void_p) for k in names] + [None] * (13 - len(names))
+    _abi.check(self.lib.mz_eval_env_results(self._h, *ptrs, self.stream), 'mz_eval_env_results')
+    acc = out.pop('acc')
+    for i, k in enumerate(('sum_reward', 'sum_pred_reward', 'sum_pred_value', 'sum_root_value', 'depth_mean')):
+      out[k] = acc[i]
+    return out
+
   def export_tree(self, hidden=False):
     B, NN, A = self.B, self.NN, self.A
     d = dict(N=np.zeros((B, NN), np.int32), W=np.zeros((B, NN)), P=np.zeros((B, NN)),

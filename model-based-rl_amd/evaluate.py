@@ -9,6 +9,11 @@ np.random.RandomState(seed_i + 3) -- the numpy stream set_all_seeds(seed_i) leav
 (select_action's uniforms) from the counter-based RNG keyed by seed_i, so a game's record does not depend on the batch it
 was played in.
 
+With --device_env the games themselves live on the device as well (Engine.eval_env_*: the device rules of TicTacToe,
+ConnectFour and CartPole): the host enqueues whole moves in chunks and synchronises once per chunk, every draw comes from
+the counter-based RNG keyed by the game's seed (or is given by the caller), and the games come back as DeviceGame records.
+The host-environment path is the default.
+
 FCNetwork checkpoints on host environments (envs.get_environment) only; the interactive tools of the reference (rendering,
 GIFs, plots, human play, MCTS PNG dumps) are refused.  One departure from the reference's output: its '[Game done]' line after
 every game (evaluate.py:376-379) is printed only with --verbose -- thousands of games are played per configuration here, and
@@ -22,11 +27,14 @@ import time
 import numpy as np
 import torch
 
-from .config import get_evaluation_args
+from .config import CARTPOLE_TIME_LIMITS, get_evaluation_args
 from .engine import Engine, flatten_weights
 from .envs import get_environment
+from .game import History
 
 MAX_BATCH = 4096
+MOVES_PER_SYNC = 8      # --device_env: whole moves enqueued per host synchronisation
+DEVICE_ENVS = ('TicTacToe', 'ConnectFour', 'CartPole-v0', 'CartPole-v1')
 
 REFUSED = (
     ('render', 'rendering is an interactive tool and is not part of this evaluator (no display on the GPU machines).'),
@@ -44,10 +52,47 @@ def refuse_unsupported(args_or_config):
       raise NotImplementedError('--%s: %s' % (name, why))
 
 
+def refuse_device_env(args_or_config):
+  """one sentence per configuration --device_env leaves out (NotImplementedError); nothing to refuse without the flag"""
+  c = args_or_config
+  if not getattr(c, 'device_env', False):
+    return
+  env = getattr(c, 'environment', None)
+  if env is not None and env not in DEVICE_ENVS:
+    raise NotImplementedError('--device_env: %s has no device form; the device environments are %s.' % (env, ', '.join(DEVICE_ENVS)))
+  if getattr(c, 'norm_obs', False):
+    raise NotImplementedError('--device_env: --norm_obs is not applied by the device environments; use the host path.')
+  m = getattr(c, 'apply_mcts_actions', 1)
+  if env == 'ConnectFour' and any(int(x) != 1 for x in (m if isinstance(m, (list, tuple)) else [m])):
+    raise NotImplementedError('--device_env: ConnectFour takes --apply_mcts_actions 1 only; below the root the walk offers full '
+                              'columns, which the host class refuses and a device game cannot.')
+
+
+class DeviceGame(object):
+  """A finished game of the device-environment path: what the summary and the CLI read, from the device's accumulators.
+  With keep_history also the per-move lists under the host path's names (history.actions / rewards / to_play / dones /
+  steps / child_visits / root_values, pred_values, pred_rewards, search_depths) and n_actions."""
+  terminal = True
+  history = None
+
+  def __init__(self, step, ret, pred_return, pred_value, mcts_value, search_depth):
+    self.step, self.ret, self.pred_return = int(step), float(ret), float(pred_return)
+    self.pred_value, self.mcts_value, self.search_depth = float(pred_value), float(mcts_value), float(search_depth)
+
+
+def game_return(game):
+  return game.ret if isinstance(game, DeviceGame) else sum(game.history.rewards)
+
+
 class SummaryTools(object):
 
   def summary(self, games):
     """the six (mean, std) pairs print_summary prints (evaluate.py:79-104), as a dict"""
+    if games and isinstance(games[0], DeviceGame):
+      cols = (('length', 'step'), ('return', 'ret'), ('pred_return', 'pred_return'), ('pred_value', 'pred_value'),
+              ('mcts_value', 'mcts_value'), ('search_depth', 'search_depth'))
+      return {key: [float(np.mean([getattr(g, f) for g in games])), float(np.std([getattr(g, f) for g in games]))]
+              for key, f in cols}
     lengths = [game.step for game in games]
     returns = [sum(game.history.rewards) for game in games]
     pred_returns = [sum(game.pred_rewards) for game in games]
@@ -83,12 +128,15 @@ class Evaluator(SummaryTools):
       raise NotImplementedError('the evaluator runs FCNetwork checkpoints only (%s has no batched evaluation path here)'
                                 % self.config.architecture)
     refuse_unsupported(self.config)
+    refuse_device_env(self.config)
     if not torch.cuda.is_available():
       raise RuntimeError('the evaluator needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
     self.device = torch.device(device if device is not None else 'cuda')
     self.batch = int(getattr(self.config, 'batch', None) or MAX_BATCH)
     self.weights = None
     self.host_seconds = 0.0
+    self.device_seconds = 0.0      # --device_env: wall time inside Engine.eval_env_moves, and the synchronisations it made
+    self.device_syncs = 0
     if getattr(self.config, 'norm_obs', False):
       self.obs_min = np.array(self.config.obs_range[::2], dtype=np.float32)
       self.obs_max = np.array(self.config.obs_range[1::2], dtype=np.float32)
@@ -103,11 +151,21 @@ class Evaluator(SummaryTools):
     return self.play_games(1, None if seed is None else [seed], environments=[environment],
                            draws=None if draws is None else [draws])[0]
 
-  def play_games(self, num_games, seeds=None, environments=None, draws=None):
+  def play_games(self, num_games, seeds=None, environments=None, draws=None, device_env=False, keep_history=False,
+                 start_states=None):
     """num_games games, up to self.batch of them in lock-step per engine.  seeds: one per game, consecutive (seed + i); None
     draws a base seed.  draws (parity runs): per game a dict of recorded draws -- 'walk' [moves][M] uniforms, 'noise' [moves][A]
-    Dirichlet draws at the legal positions, 'opp' the random opponent's choices (indices into the legal actions)."""
+    Dirichlet draws at the legal positions, 'opp' the random opponent's choices (indices into the legal actions).
+    device_env (or config.device_env): the games live on the device environments and come back as DeviceGame records, with
+    keep_history (or config.keep_history) carrying the per-move lists; start_states [num_games][4]: CartPole's start states
+    instead of the counter RNG's (device path only)."""
     assert self.weights is not None, '.load_network() needs to be called before playing.'
+    device_env = bool(device_env or getattr(self.config, 'device_env', False))
+    keep_history = bool(keep_history or getattr(self.config, 'keep_history', False))
+    if device_env and environments is not None:
+      raise ValueError('play_games: a device-environment run builds no host environment')
+    if start_states is not None and not device_env:
+      raise ValueError('play_games: start_states are the device path\'s; give the host path environments that hold them')
     if seeds is None:
       base = int(np.random.randint(0, 2 ** 30))
       seeds = list(range(base, base + num_games))
@@ -117,8 +175,74 @@ class Evaluator(SummaryTools):
     games = []
     for lo in range(0, num_games, self.batch):
       hi = min(num_games, lo + self.batch)
+      if device_env:
+        games += self._play_batch_device(seeds[lo:hi], None if draws is None else draws[lo:hi],
+                                         None if start_states is None else start_states[lo:hi], keep_history)
+        continue
       envs = environments[lo:hi] if environments is not None else [get_environment(self.config) for _ in range(lo, hi)]
       games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
+    return games
+
+  def _play_batch_device(self, seeds, draws, start_states, keep_history):
+    """_play_batch with the games on the device environments: whole moves are enqueued MOVES_PER_SYNC at a time
+    (Engine.eval_env_moves: observe, initial inference, root, search + walk or lookahead, finalize, apply), and the host
+    only reads the number of games still live after each chunk"""
+    cfg = self.config
+    refuse_device_env(_with(cfg, device_env=True))
+    B, A = len(seeds), int(cfg.action_space)
+    only_prior, only_value = bool(getattr(cfg, 'only_prior', 0)), bool(getattr(cfg, 'only_value', 0))
+    mode = 1 if only_prior else 2 if only_value else 0
+    noise_on = bool(getattr(cfg, 'use_exploration_noise', 0))
+    two = bool(cfg.two_players)
+    M = int(getattr(cfg, 'apply_mcts_actions', 1))
+    if M <= 0:
+      M = int(cfg.num_simulations) + 1
+    T = float(getattr(cfg, 'temperature', 0) or 0)
+    t_batch = time.perf_counter()
+    # the device RNG's key: (engine seed 0, env id = the game's seed, move, step)
+    eng = Engine.from_config(cfg, B, device=self.device, seed=0, env_id_offset=seeds[0])
+    eng.set_weights(self.weights)
+    eng.eval_env_reset(cfg.environment, int(cfg.max_steps), CARTPOLE_TIME_LIMITS.get(cfg.environment, 0),
+                       getattr(cfg, 'random_opp', None) if two else None, keep_history)
+    if draws is not None or start_states is not None:
+      eng.eval_env_set_draws(**_pack_draws(draws, B, A, M, mode, noise_on, start_states))
+    live, moves, t_dev = B, 0, 0.0
+    while live > 0 and moves < eng.eval_log_cap:      # (every move applies at least one action: at most cap moves)
+      n = min(MOVES_PER_SYNC, eng.eval_log_cap - moves)
+      t0 = time.perf_counter()
+      live = eng.eval_env_moves(n, mode, M, T, noise_on)
+      t_dev += time.perf_counter() - t0
+      self.device_syncs += 1
+      moves += n
+    r = eng.eval_env_results()
+    eng.close()
+    games = []
+    for i in range(B):
+      nm = max(int(r['n_moves'][i]), 1)
+      g = DeviceGame(r['step'][i], r['sum_reward'][i], r['sum_pred_reward'][i], r['sum_pred_value'][i] / nm,
+                     r['sum_root_value'][i] / nm, r['depth_mean'][i])
+      g.seed = seeds[i]
+      if keep_history:
+        n, k = g.step, int(r['n_moves'][i])
+        h = g.history = History()
+        h.actions = [int(x) for x in r['actions'][i, :n]]
+        h.rewards = [float(x) for x in r['rewards'][i, :n]]
+        h.to_play = [int(np.sign(x)) for x in r['mover'][i, :n]]
+        h.steps = list(range(n))
+        h.dones = [abs(int(x)) == 2 for x in r['mover'][i, :n]]      # (env.step's done: not the cut at max_steps)
+        h.child_visits = [[float(x) for x in row] for row in r['child_visits'][i, :k]]
+        h.root_values = [float(x) for x in r['root_values'][i, :k]]
+        g.pred_values = [float(x) for x in r['pred_values'][i, :k]]
+        g.pred_rewards = [float(x) for x in r['pred_rewards'][i, :n]]
+        g.n_actions = [int(x) for x in r['n_actions'][i, :k]]
+        g.search_depths = [[0] if only_prior else [1] if only_value else [int(x) for x in row] for row in r['depths'][i, :k]]
+      if getattr(cfg, 'verbose', False):
+        msg = "\033[92m[Game done]\033[0m --> "
+        msg += "length: {:.1f}, return: {:.1f}, pred return: {:.1f}, pred value: {:.1f}, mcts value: {:.1f}"
+        print(msg.format(g.step, g.ret, g.pred_return, g.pred_value, g.mcts_value))
+      games.append(g)
+    self.device_seconds += t_dev
+    self.host_seconds += time.perf_counter() - t_batch - t_dev
     return games
 
   def _play_batch(self, envs, seeds, draws):
@@ -235,6 +359,45 @@ class Evaluator(SummaryTools):
     return games
 
 
+def _with(cfg, **kv):
+  """a shallow copy of a config with some attributes set"""
+  c = copy.copy(cfg)
+  for k, v in kv.items():
+    setattr(c, k, v)
+  return c
+
+
+def _pack_draws(draws, B, A, M, mode, noise_on, start_states):
+  """the per-game draw dicts of play_games as the dense arrays Engine.eval_env_set_draws uploads: walk [B][moves][M], noise
+  [B][moves][A], opp [B][n], each padded with zeros past a game's own draws"""
+  out = dict(start_states=None if start_states is None else np.ascontiguousarray(start_states, np.float64).reshape(B, 4))
+  if draws is None:
+    return out
+  if mode == 0 and any('walk' in d for d in draws):
+    mv = max(1, max(len(d['walk']) for d in draws))
+    walk = np.zeros((B, mv, M), np.float64)
+    for i, d in enumerate(draws):
+      for m, w in enumerate(d['walk']):
+        w = np.asarray(w, np.float64).reshape(-1)[:M]
+        walk[i, m, :len(w)] = w
+    out['walk'] = walk
+  if noise_on and any('noise' in d for d in draws):
+    mv = max(1, max(len(d['noise']) for d in draws))
+    noise = np.zeros((B, mv, A), np.float64)
+    for i, d in enumerate(draws):
+      for m, nz in enumerate(d['noise']):
+        noise[i, m] = np.asarray(nz, np.float64)
+    out['noise'] = noise
+  if any(len(d.get('opp', ())) for d in draws):
+    n = max(len(d.get('opp', ())) for d in draws)
+    opp = np.zeros((B, n), np.int32)
+    for i, d in enumerate(draws):
+      o = np.asarray(d.get('opp', ()), np.int32).reshape(-1)
+      opp[i, :len(o)] = o
+    out['opp'] = opp
+  return out
+
+
 def get_label(state, detailed=False, path_idx=None):
   label_parts = ['net:{}'.format(state['training_step'])]
   if detailed:
@@ -289,6 +452,8 @@ def state_generator(args):
                     c.use_gpu = True
                     c.verbose = args.verbose
                     c.batch = args.batch
+                    c.device_env = args.device_env
+                    c.keep_history = args.keep_history
                     yield state
 
 
@@ -301,6 +466,7 @@ def run(evaluator, seed=None):
 def main(argv=None):
   args = get_evaluation_args(argv)
   refuse_unsupported(args)
+  refuse_device_env(args)
   evaluators = [Evaluator(state) for state in state_generator(args)]
   print("\n\033[92mStarting a {} episode evaluation of {} configurations\033[0m...".format(args.num_games, len(evaluators)))
   seeds = list(range(args.seed, args.num_games + args.seed)) if args.seed is not None else None
@@ -315,7 +481,7 @@ def main(argv=None):
     s['label'] = evaluator.config.label
     s['num_games'] = len(games)
     if evaluator.config.two_players and args.random_opp is not None:
-      returns = np.array([sum(g.history.rewards) for g in games])
+      returns = np.array([game_return(g) for g in games])
       s['wins'], s['draws'], s['losses'] = int((returns > 0).sum()), int((returns == 0).sum()), int((returns < 0).sum())
       print("Against a random opponent (the agent moves {}): wins {} draws {} losses {}\n".format(
           'second' if args.random_opp == 1 else 'first', s['wins'], s['draws'], s['losses']))

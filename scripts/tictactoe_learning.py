@@ -5,7 +5,9 @@ on the same GPU -- then the trained network's MCTS agent (temperature 0, no expl
 opponent on the host's TicTacToe rules, 512 games as each side, next to the untrained network.
 
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
-                                       [--out profiles/r03_tictactoe_learning.json]
+                                       [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
+--environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
+evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --no_support adds the flag (scalar value / reward heads, MSE or Huber loss) to the recipe, for training and for the matches."""
 import argparse, json, os, sys, time, types
 import numpy as np, torch
@@ -51,8 +53,25 @@ def play_vs_random(weights, agent_side, games=512, sims=30, seed=0, no_support=F
   return int((result == 1).sum()), int((result == 0).sum()), int((result == -1).sum())
 
 
+def play_vs_random_device(config, weights, agent_side, games=512, seed=0):
+  """the same match through the evaluator's device-environment path (any environment with a device form); `weights` a
+  state_dict.  Returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second."""
+  import copy
+  from model_based_rl_amd.evaluate import Evaluator, game_return
+  cfg = copy.copy(config)
+  for k, v in dict(temperature=0, only_prior=0, only_value=0, use_exploration_noise=0, apply_mcts_actions=1,
+                   random_opp=-agent_side, human_opp=None, render=False, save_mcts=False, save_gif_as='', label='vs random',
+                   verbose=False, batch=games, device_env=True, keep_history=False).items():
+    setattr(cfg, k, v)
+  ev = Evaluator({'config': cfg, 'weights': weights, 'training_step': 0})
+  ev.load_network()
+  ret = np.array([game_return(g) for g in ev.play_games(games, list(range(seed, seed + games)))])
+  return int((ret > 0).sum()), int((ret == 0).sum()), int((ret < 0).sum())
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--environment', default='TicTacToe', choices=['TicTacToe', 'ConnectFour'])
   ap.add_argument('--training_steps', type=int, default=3000)
   ap.add_argument('--num_envs', type=int, default=1024)
   ap.add_argument('--out', default=None)
@@ -63,14 +82,18 @@ def main():
   from model_based_rl_amd.config import make_config
   from model_based_rl_amd.networks import get_network
   from model_based_rl_amd.engine import flatten_weights
-  base = ['--environment', 'TicTacToe', '--two_players', '--architecture', 'FCNetwork', '--td_steps', '10', '--discount', '1',
+  base = ['--environment', a.environment, '--two_players', '--architecture', 'FCNetwork', '--td_steps', '10', '--discount', '1',
           '--known_bounds', '-1', '1', '--num_simulations', '30', '--seed', '0', '--num_envs', str(a.num_envs)]
   if a.no_support:
     base += ['--no_support', '--scalar_loss', a.scalar_loss]
   torch.manual_seed(0)
-  untrained = flatten_weights(get_network(make_config(base), torch.device('cpu')).state_dict())
-  before = {side: play_vs_random(untrained, side, no_support=a.no_support) for side in (1, -1)}
-  saves = os.path.join('/tmp', 'mz_ttt_learning_%d' % os.getpid())
+  untrained_sd = get_network(make_config(base), torch.device('cpu')).state_dict()
+  if a.environment == 'TicTacToe':
+    match = lambda sd, side: play_vs_random(flatten_weights(sd), side, no_support=a.no_support)
+  else:
+    match = lambda sd, side: play_vs_random_device(make_config(base), sd, side)
+  before = {side: match(untrained_sd, side) for side in (1, -1)}
+  saves = os.path.join('/tmp', 'mz_%s_learning_%d' % ('ttt' if a.environment == 'TicTacToe' else 'c4', os.getpid()))
   t0 = time.time()
   thr = train.main(base + ['--max_moves', '-1', '--training_steps', str(a.training_steps), '--stored_before_train', '20000',
                            '--batch_size', '256', '--window_size', '200000', '--send_weights_frequency', '100',
@@ -80,8 +103,7 @@ def main():
   import glob
   ck = sorted(glob.glob(os.path.join(saves, '**', 'saves', '*'), recursive=True), key=os.path.getmtime)[-1]
   state = torch.load(ck, map_location='cpu', weights_only=False)
-  trained = flatten_weights(state['weights'])
-  after = {side: play_vs_random(trained, side, no_support=a.no_support) for side in (1, -1)}
+  after = {side: match(state['weights'], side) for side in (1, -1)}
   out = {'recipe': ' '.join(base), 'training_steps': int(state['training_step']), 'train_seconds': seconds,
          'selfplay_frames': thr['frames'], 'selfplay_games': thr['games'], 'learner': thr.get('learner'),
          'vs_random_512_games': {'untrained': {'agent_first (win, draw, loss)': before[1], 'agent_second': before[-1]},
