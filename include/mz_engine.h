@@ -280,6 +280,61 @@ int mz_eval_env_results(mz_engine *e, int32_t *step, int32_t *n_moves, double *a
                         double *child_visits, int32_t *n_actions, int32_t *depths, void *stream);
 int mz_eval_env_log_capacity(const mz_engine *e);
 
+/* A match between two networks on the device games: B games in lock-step, every ply searched by the mover's own network.
+ * Replaces the per-ply host loop a match driven from Python would need (two Evaluator._play_batch loops interleaved by
+ * hand: per ply one engine call sequence and one host environment step); the host touches no game between plies.
+ *
+ * mz_match_create: a handle over two existing engines, network 0 and network 1, each with its own weights, its own
+ * num_simulations and its own trees; the handle owns neither and is destroyed before them.  kind 1 TicTacToe or 3 Connect
+ * Four.  Refused: kind 2 (CartPole) and any single-player engine; engines that differ in device, num_envs, obs_dim,
+ * action_space, seed or env_id_offset.  Game b is the game with seed env_id_offset + b.  max_steps: a game is cut -- a draw
+ * -- when its ply count reaches it; keep_history != 0: per-ply logs are kept ([B][cap], cap = min(max_steps, 9 / 42),
+ * mz_match_log_capacity).
+ *
+ * mz_match_reset: every game back to the empty board, player +1 to move.  opening_plies in [0, max_steps): that many plies
+ * are applied with no inference before the first searched ply -- ply p of game b is the min(floor(u * n), n - 1)-th of the
+ * position's n legal actions, u from the counter RNG under MZ_RNG_OPEN keyed (engine seed, the game's seed, p, 0): the
+ * game's seed alone, so both seatings of a seed open alike.  A game that ends inside its opening is over, with its result.
+ * first_net 0 / 1: the network that moves at ply opening_plies; the other one moves next, and so on in turn.  Synchronous.
+ *
+ * mz_match_set_draws (after reset, before the first ply; parity runs): draws given by the caller instead of the counter
+ * RNG, [dev] arrays the caller keeps alive until the games are over; any may be NULL.  walk [B][walk_plies] float64: the
+ * uniform of mz_eval_walk; noise [B][noise_plies][A] float64: the Dirichlet draw at the legal positions -- both indexed by
+ * the ply, opening plies counted; opening [B][opening_n] int32: the opening plies as indices into the legal actions of
+ * their positions.  Plies past the given ones draw zeros.
+ *
+ * mz_match_plies: the opening (once), then n plies enqueued on the stream.  Ply p (opening plies counted) is network
+ * first_net's when (p - opening_plies) is even, else the other's, and runs on that network's engine: observe (state -> obs
+ * / legal / to_play; a finished game gets a zero observation, all actions legal, to_play +1) -> mz_initial_inference ->
+ * mz_root_prepare with move counter p (noise_on: the given draw, or the device Dirichlet keyed by p) -> mode 0: mz_search
+ * (the engine's num_simulations) + mz_eval_walk (one action, that side's temperature; device uniforms under MZ_RNG_EVAL
+ * keyed by p) + mz_finalize, mode 1 / 2: mz_eval_lookahead (only_prior / only_value) -> apply (the mover network's
+ * accumulators and logs, then exactly one action on the device rules).  mode, temperature, noise_on: [host] arrays of two,
+ * per network.  With opening_plies 0, a match of a network against itself enqueues what mz_eval_env_moves without a random
+ * opponent enqueues, with the same keys.  No host synchronisation between the plies; one 4-byte copy at the end returns
+ * the number of games still live in *live_out [host].
+ *
+ * mz_match_results (synchronous, [host] arrays, any may be NULL): result [B] int8 for player +1, the game's first mover
+ * (+1 win, 0 draw, -1 loss); length [B] int32; per network k = 0 / 1: n_searched [2][B] int32 (plies it searched), acc
+ * [2][4][B] float64 (sums, added in ply order, of its predicted rewards, predicted values and root values, and the mean of
+ * the lexicographic-maximum depth list), depth_max [2][B][S] int32 (that list; S = the larger num_simulations); the logs,
+ * kept with keep_history, per ply [B][cap]: actions int32, mover int8 (+1 / -1, doubled on the ply the rules reported
+ * done), net int8 (the network that moved, -1 on an opening ply), rewards float64, pred_rewards / pred_values float32,
+ * root_values float64, child_visits [B][cap][A] float64, depths [B][cap][S] int32 (the mover's num_simulations entries;
+ * [0] / [1] in modes 1 / 2).  The search entries of an opening ply are zero. */
+typedef struct mz_match mz_match;
+int mz_match_create(mz_engine *e0, mz_engine *e1, int kind, int max_steps, int keep_history, mz_match **out);
+int mz_match_destroy(mz_match *m);
+int mz_match_reset(mz_match *m, int first_net, int opening_plies, void *stream);
+int mz_match_set_draws(mz_match *m, const double *walk, int walk_plies, const double *noise, int noise_plies,
+                       const int32_t *opening, int opening_n, void *stream);
+int mz_match_plies(mz_match *m, int n, const int *mode, const double *temperature, const int *noise_on, int *live_out,
+                   void *stream);
+int mz_match_results(mz_match *m, int8_t *result, int32_t *length, int32_t *n_searched, double *acc, int32_t *depth_max,
+                     int32_t *actions, int8_t *mover, int8_t *net, double *rewards, float *pred_rewards, float *pred_values,
+                     double *root_values, double *child_visits, int32_t *depths, void *stream);
+int mz_match_log_capacity(const mz_match *m);
+
 /* Raw tree dump (Node objects of mcts.py:28-45 in SoA form) to [host] arrays, synchronous.
  * Each per-node array is [B][NN]; minmax [B][2]; legal_mask [B] (bit a = root child a exists);
  * noise [B][A] (the Dirichlet draw last mixed in).  Any pointer may be NULL. */

@@ -196,8 +196,9 @@ def make_config(argv=None, **overrides):
 
 def get_evaluation_args(argv=None):
   """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
-  engine; default min(num_games, 4096)), --out (a JSON summary) and --device_env / --keep_history (the games on the device
-  environments, evaluate.py).  Checkpoints are saves_dir + net for every pair."""
+  engine; default min(num_games, 4096)), --out (a JSON summary), --device_env / --keep_history (the games on the device
+  environments, evaluate.py) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
+  saves_dir + net for every pair."""
   p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
   a = p.add_argument
   a('--seed', type=int, default=None)
@@ -230,6 +231,12 @@ def get_evaluation_args(argv=None):
   a('--device_env', action='store_true',
     help='play the games on the device environments (TicTacToe, ConnectFour, CartPole-v0 / -v1): no host work between moves')
   a('--keep_history', action='store_true', help='--device_env: keep the per-move lists of every game, not only its summary')
+  a('--match', action='store_true',
+    help='play every pair of --nets against each other on the device games (TicTacToe, ConnectFour), every seed from both '
+         'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise then take one '
+         'value for both sides or two, one per side')
+  a('--opening_plies', type=int, default=0,
+    help='--match: uniform random legal plies before the first searched one, the same in both seatings of a seed')
   args = p.parse_args(argv)
   if args.batch is None:
     args.batch = min(args.num_games, 4096)

@@ -32,6 +32,7 @@
 #include "mz_fcl.hip.h"
 #include "mz_eval.hip.h"
 #include "mz_eval_env.hip.h"
+#include "mz_match.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
@@ -1619,6 +1620,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 
 #include "mz_selfplay_abi.inc"
 #include "mz_eval_abi.inc"
+#include "mz_match_abi.inc"
 #include "mz_fcl_abi.inc"
 
 }  // extern "C"

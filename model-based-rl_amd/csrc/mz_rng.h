@@ -14,6 +14,7 @@
 #define MZ_RNG_EVAL 5u       // evaluation walk (mz_eval.hip.h): one uniform per applied action, counter (env, move, step)
 #define MZ_RNG_ENV 6u        // start state of a device environment's episode (mz_cartpole_reset_state): counter (env, episode, 0)
 #define MZ_RNG_OPP 7u        // the random opponent of a device evaluation game (k_eval_apply): counter (env = the game's seed, move, step)
+#define MZ_RNG_OPEN 8u       // opening ply of a match (mz_match_open_game): counter (env = the game's seed, ply, 0)
 
 struct mz_u4 { uint32_t x, y, z, w; };
 

@@ -654,3 +654,93 @@ class Engine(object):
     _abi.check(self.lib.mz_synth_obs(self._h, env, episode, t, obs.ctypes.data_as(C.c_void_p), C.byref(r)),
                'mz_synth_obs')
     return obs, float(r.value)
+
+
+class Match(object):
+  """A match between two networks on the device games (mz_match_*, include/mz_engine.h): a handle over two Engines, network
+  0 and network 1, each with its own weights and num_simulations.  The engines must share device, num_envs, shapes, seed
+  and env_id_offset; the match holds them and is closed before them."""
+  KINDS = {'TicTacToe': 1, 'ConnectFour': 3}
+  MODES = {'search': 0, 'only_prior': 1, 'only_value': 2}
+
+  def __init__(self, engine0, engine1, kind, max_steps, keep_history=False):
+    self.engines = (engine0, engine1)
+    self.lib = engine0.lib
+    self.device = engine0.device
+    self.B, self.A = engine0.B, engine0.A
+    self.S = max(engine0.sims, engine1.sims)
+    self.keep = bool(keep_history)
+    k = self.KINDS.get(kind, 2 if str(kind).startswith('CartPole') else 0) if isinstance(kind, str) else int(kind)
+    h = C.c_void_p()
+    _abi.check(self.lib.mz_match_create(engine0._h, engine1._h, k, int(max_steps), int(self.keep), C.byref(h)), 'mz_match_create')
+    self._h = h
+    self.log_cap = int(self.lib.mz_match_log_capacity(self._h))
+    self._draws = None
+
+  def close(self):
+    if getattr(self, '_h', None):
+      self.lib.mz_match_destroy(self._h)
+      self._h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  @property
+  def stream(self):
+    return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+  def reset(self, first_net=0, opening_plies=0):
+    """mz_match_reset: every game at its start; network `first_net` moves at ply `opening_plies`, after the opening"""
+    _abi.check(self.lib.mz_match_reset(self._h, int(first_net), int(opening_plies), self.stream), 'mz_match_reset')
+    self._draws = None
+
+  def set_draws(self, walk=None, noise=None, opening=None):
+    """mz_match_set_draws: walk [B, plies] (or [B, plies, 1]) float64, noise [B, plies, A] float64 -- both indexed by the
+    ply, opening plies counted -- and opening [B, k] int32; uploaded once, kept alive by this object until the next reset"""
+    dev = lambda x, dt: None if x is None else torch.as_tensor(np.ascontiguousarray(x)).to(self.device, dt).contiguous()
+    w, nz, op = dev(walk, torch.float64), dev(noise, torch.float64), dev(opening, torch.int32)
+    if w is not None and w.dim() == 3 and w.shape[2] == 1:
+      w = w.reshape(w.shape[0], w.shape[1])
+    for t, shape in ((w, (self.B, None)), (nz, (self.B, None, self.A)), (op, (self.B, None))):
+      if t is not None and (t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise ValueError('Match.set_draws: shape %s does not match %s' % (tuple(t.shape), shape))
+    self._draws = (w, nz, op)
+    _abi.check(self.lib.mz_match_set_draws(self._h, _ptr(w), 0 if w is None else w.shape[1], _ptr(nz),
+                                           0 if nz is None else nz.shape[1], _ptr(op), 0 if op is None else op.shape[1],
+                                           self.stream), 'mz_match_set_draws')
+
+  def plies(self, n, modes=(0, 0), temperatures=(0.0, 0.0), noise_on=(False, False)):
+    """mz_match_plies: the opening (once) and n plies enqueued back to back, one synchronisation at the end; returns the
+    games still live.  modes / temperatures / noise_on: per network; a mode is 0 / 'search', 1 / 'only_prior', 2 / 'only_value'."""
+    md = (C.c_int * 2)(*[self.MODES[m] if isinstance(m, str) else int(m) for m in modes])
+    tp = (C.c_double * 2)(*[float(t) for t in temperatures])
+    nz = (C.c_int * 2)(*[int(bool(x)) for x in noise_on])
+    live = C.c_int(0)
+    _abi.check(self.lib.mz_match_plies(self._h, int(n), md, tp, nz, C.byref(live), self.stream), 'mz_match_plies')
+    return int(live.value)
+
+  def results(self, logs=None):
+    """mz_match_results -> dict of numpy arrays: result [B] int8 (for player +1, the first mover), length [B]; per network
+    n_searched [2, B], sum_pred_reward / sum_pred_value / sum_root_value / depth_mean [2, B] float64, depth_max [2, B, S];
+    with logs (default: whether they were kept), per ply: actions, mover, net, rewards, pred_rewards, pred_values,
+    root_values [B, cap], child_visits [B, cap, A], depths [B, cap, S]"""
+    B, A, L, S = self.B, self.A, self.log_cap, self.S
+    logs = self.keep if logs is None else bool(logs)
+    out = dict(result=np.zeros(B, np.int8), length=np.zeros(B, np.int32), n_searched=np.zeros((2, B), np.int32),
+               acc=np.zeros((2, 4, B), np.float64), depth_max=np.zeros((2, B, S), np.int32))
+    names = ['result', 'length', 'n_searched', 'acc', 'depth_max']
+    if logs:
+      out.update(actions=np.zeros((B, L), np.int32), mover=np.zeros((B, L), np.int8), net=np.zeros((B, L), np.int8),
+                 rewards=np.zeros((B, L), np.float64), pred_rewards=np.zeros((B, L), np.float32),
+                 pred_values=np.zeros((B, L), np.float32), root_values=np.zeros((B, L), np.float64),
+                 child_visits=np.zeros((B, L, A), np.float64), depths=np.zeros((B, L, S), np.int32))
+      names += ['actions', 'mover', 'net', 'rewards', 'pred_rewards', 'pred_values', 'root_values', 'child_visits', 'depths']
+    ptrs = [out[k].ctypes.data_as(C.c_void_p) for k in names] + [None] * (14 - len(names))
+    _abi.check(self.lib.mz_match_results(self._h, *ptrs, self.stream), 'mz_match_results')
+    acc = out.pop('acc')
+    for i, k in enumerate(('sum_pred_reward', 'sum_pred_value', 'sum_root_value', 'depth_mean')):
+      out[k] = acc[:, i]
+    return out

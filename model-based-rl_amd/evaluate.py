@@ -14,6 +14,9 @@ ConnectFour and CartPole): the host enqueues whole moves in chunks and synchroni
 the counter-based RNG keyed by the game's seed (or is given by the caller), and the games come back as DeviceGame records.
 The host-environment path is the default.
 
+With --match the nets play each other instead of being evaluated one by one (match.py): every pair of --nets, every seed
+from both seats, on the device games.
+
 FCNetwork checkpoints on host environments (envs.get_environment) only; the interactive tools of the reference (rendering,
 GIFs, plots, human play, MCTS PNG dumps) are refused.  One departure from the reference's output: its '[Game done]' line after
 every game (evaluate.py:376-379) is printed only with --verbose -- thousands of games are played per configuration here, and
@@ -465,6 +468,9 @@ def run(evaluator, seed=None):
 
 def main(argv=None):
   args = get_evaluation_args(argv)
+  if args.match:      # checkpoint against checkpoint (match.py); implies the device path
+    from . import match
+    return match.main(args)
   refuse_unsupported(args)
   refuse_device_env(args)
   evaluators = [Evaluator(state) for state in state_generator(args)]

@@ -101,13 +101,32 @@ def main():
                            '--run_tag', 'learn', '--save_state_frequency', str(a.training_steps), '--learner_log_frequency', '500'])
   seconds = time.time() - t0
   import glob
-  ck = sorted(glob.glob(os.path.join(saves, '**', 'saves', '*'), recursive=True), key=os.path.getmtime)[-1]
-  state = torch.load(ck, map_location='cpu', weights_only=False)
+  kept = sorted(glob.glob(os.path.join(saves, '**', 'saves', '*'), recursive=True), key=os.path.getmtime)
+  state = torch.load(kept[-1], map_location='cpu', weights_only=False)
   after = {side: match(state['weights'], side) for side in (1, -1)}
+  # the last checkpoint against the first kept one, from both seats (match.play_match); where the run kept a single
+  # checkpoint, against the untrained network
+  from model_based_rl_amd.match import play_match
+  if len(kept) > 1:
+    first = torch.load(kept[0], map_location='cpu', weights_only=False)
+    opponent = 'checkpoint %d' % int(first['training_step'])
+  else:
+    first, opponent = {'weights': untrained_sd, 'training_step': 0}, 'untrained network'
+
+  def side(st):
+    import copy
+    cfg = copy.copy(make_config(base))
+    for k, v in dict(temperature=0, only_prior=0, only_value=0, use_exploration_noise=0, apply_mcts_actions=1, random_opp=None,
+                     human_opp=None).items():
+      setattr(cfg, k, v)
+    return {'config': cfg, 'weights': st['weights'], 'training_step': st['training_step']}
+  _, vs_first = play_match(side(state), side(first), 256, list(range(256)), opening_plies=2, batch=256)
   out = {'recipe': ' '.join(base), 'training_steps': int(state['training_step']), 'train_seconds': seconds,
          'selfplay_frames': thr['frames'], 'selfplay_games': thr['games'], 'learner': thr.get('learner'),
          'vs_random_512_games': {'untrained': {'agent_first (win, draw, loss)': before[1], 'agent_second': before[-1]},
-                                 'trained': {'agent_first (win, draw, loss)': after[1], 'agent_second': after[-1]}}}
+                                 'trained': {'agent_first (win, draw, loss)': after[1], 'agent_second': after[-1]}},
+         'match_last_vs_first': dict(vs_first, a='checkpoint %d' % int(state['training_step']), b=opponent, seeds=256,
+                                     opening_plies=2)}
   print(json.dumps(out))
   if a.out:
     json.dump(out, open(a.out, 'w'), indent=1)
