@@ -335,6 +335,23 @@ int mz_match_results(mz_match *m, int8_t *result, int32_t *length, int32_t *n_se
                      double *root_values, double *child_visits, int32_t *depths, void *stream);
 int mz_match_log_capacity(const mz_match *m);
 
+/* MuZero Reanalyse: stored positions of the replay searched again under the engine's CURRENT weights.  rows_host [host, pinned]
+ * is [n_rows][rec_floats] record rows as mzr_reanalyse_pick (include/mz_replay.h) wrote them, rec_floats = obs_dim + action_space
+ * + MZ_REC_EXTRA; fresh_host [host, pinned] receives [n_rows][action_space + 2] floats per row: child_visits as float32 (the
+ * float32 of the float64 N[a] / sum N that mz_finalize returns, 0 at illegal actions), then the root's value, the float64 of
+ * mz_finalize, in two float slots -- what mzr_reanalyse_write takes.  Per chunk of num_envs rows the call enqueues: the rows'
+ * observation, to_play (bit 1 of the flags word) and legal actions read straight from the pinned rows; mz_initial_inference;
+ * mz_root_prepare WITHOUT exploration noise; mz_search(num_simulations); the store into fresh_host.  No host synchronisation
+ * between chunks, one at the end; the engine's self-play, evaluation and match states are untouched (a state of its own,
+ * allocated on the first call, which therefore synchronises).  Rows past n_rows in the last chunk are searched as empty
+ * positions and nothing is stored for them.
+ * kind, as in mz_selfplay_set_env, says how the legal actions follow from the observation: 0 synthetic and 2 CartPole: all;
+ * 1 TicTacToe: cell k iff obs[k] == 0; 3 Connect Four: column c iff obs[35 + c] == 0.
+ * Refused: weights not set; another rec_floats; kind outside 0..3 or not the engine's shape; n_rows < 0; num_simulations outside
+ * 1 .. the engine's; buffers that are not page-locked. */
+int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
+                 int num_simulations, void *stream);
+
 /* Raw tree dump (Node objects of mcts.py:28-45 in SoA form) to [host] arrays, synchronous.
  * Each per-node array is [B][NN]; minmax [B][2]; legal_mask [B] (bit a = root child a exists);
  * noise [B][A] (the Dirichlet draw last mixed in).  Any pointer may be NULL. */

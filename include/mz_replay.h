@@ -163,6 +163,29 @@ int mzr_sample_batches_full(mz_replay *r, const uint32_t *words, int n, int bs, 
                             float *target_values, float *target_policies, int64_t *idxs, double *is_weights, uint32_t *np_key,
                             int32_t *np_pos, double *beta_inout, int64_t *pads_out, uint32_t *py_key, int32_t *py_pos);
 
+/* Reanalyse: refresh the stored search statistics of history slices with a newer network.  mzr_sample_batch builds its targets at
+ * sampling time from the rows' child_visits and root_value, so rewriting those two fields in place is all a learner needs.
+ * mzr_reanalyse_pick walks the leaves in position order from a cursor kept in the handle (leaf 0 at first; it wraps at the tree's
+ *   current capacity) and copies every distinct slice with a payload -- consecutive leaves of one slice count once -- with ALL its n
+ *   rows, the ignored tail included (the value target of step s reads root_value of row s + td_steps), as stored ([n][rec_floats]) to
+ *   rows_out, one slice after another; slice_rows_out[i] = rows of slice i.  It stops when the next slice would not fit max_rows or
+ *   max_slices (the next call starts there), when the walk is back where this call started, or when the replay is empty.  Empty
+ *   leaves and slices without payload are skipped; a slice longer than max_rows is skipped and counted in info[0] (info may be NULL).
+ *   -> the number of rows (< 0: error); *n_slices, *ticket (0 when nothing was picked).  The picked slices stay alive and writable
+ *   until the ticket is written or released, whatever the window evicts meanwhile.  One ticket per handle: a second pick is refused
+ *   with -2 (every other error: -1), so that callers sharing the handle can tell "another pass is under way" from a failure.
+ *   A replay created with obs_u8 refuses.
+ * mzr_reanalyse_write: fresh [n_rows][A + 2] = child_visits[A] (float32), root_value (float64 in two float slots) -- the row's own
+ *   layout from the observation's end on -- for the ticket's rows in pick order.  Writes exactly these fields of exactly these rows
+ *   and releases the ticket; a slice that lost all its leaves since the pick is dropped unwritten.  Priorities, the stored error,
+ *   counters and everything else stay.  -> rows written (< 0: error; a wrong n_rows keeps the ticket); stats_out (may be NULL):
+ *   {rows written, sum |new - old root_value|, sum over rows of the L1 distance between old and new child_visits}.
+ * mzr_reanalyse_release drops the ticket without writing. */
+int64_t mzr_reanalyse_pick(mz_replay *r, int64_t max_rows, float *rows_out, int32_t *slice_rows_out, int64_t max_slices,
+                           int64_t *n_slices, uint64_t *ticket, int64_t *info);
+int64_t mzr_reanalyse_write(mz_replay *r, uint64_t ticket, const float *fresh, int64_t n_rows, double *stats_out);
+int mzr_reanalyse_release(mz_replay *r, uint64_t ticket);
+
 /* number of ingest threads of the handle (mzr_config.ingest_threads at creation; the setter re-creates the pool) */
 int mzr_set_ingest_threads(mz_replay *r, int threads);
 int mzr_ingest_threads(const mz_replay *r);

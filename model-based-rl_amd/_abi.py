@@ -11,8 +11,8 @@ import subprocess
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _SO = os.environ.get('MZ_HIP_LIB') or os.path.join(_CSRC, 'libmz_hip.so')      # (MZ_HIP_LIB: A/B runs of two builds on one box)
 _SOURCES = ['mz_engine.hip', 'mz_comm.inc', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_inst.hip', 'mz_kernels.inc', 'mz_common.h', 'mz_net.hip.h', 'mz_tree.hip.h', 'mz_rng.h', 'mz_eval.hip.h',
-            'mz_selfplay.hip.h', 'mz_selfplay_abi.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_fused.hip.h', 'mz_root.hip.h', 'mz_fused_h2.hip.h']
-_ENGINE_ONLY = ('mz_engine.hip', 'mz_comm.inc', 'mz_eval.hip.h', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_selfplay_abi.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc')      # included by mz_engine.hip alone
+            'mz_selfplay.hip.h', 'mz_selfplay_abi.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_fused.hip.h', 'mz_root.hip.h', 'mz_fused_h2.hip.h']
+_ENGINE_ONLY = ('mz_engine.hip', 'mz_comm.inc', 'mz_eval.hip.h', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_selfplay_abi.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc')      # included by mz_engine.hip alone
 _lib = None
 
 HIPCC_FLAGS = ['-O3', '--offload-arch=gfx950', '-ffp-contract=off', '-std=c++17', '-fPIC', '-Wno-unused-value',
@@ -162,6 +162,7 @@ SIGNATURES = {
     'mz_match_plies': (_I, [_VP, _I, C.POINTER(_I), C.POINTER(_D), C.POINTER(_I), C.POINTER(_I), _VP]),
     'mz_match_results': (_I, [_VP] * 16),
     'mz_match_log_capacity': (_I, [_VP]),
+    'mz_reanalyse': (_I, [_VP, _I, _VP, _I, _I, _VP, _I, _VP]),
     'mz_export_tree': (_I, [_VP] * 11),
     'mz_affine_relu': (_I, [_VP, _VP, _VP, _VP, _SZ, _I, _I, _VP]),
     'mz_nodes_per_tree': (_I, [_VP]),
@@ -286,6 +287,9 @@ REPLAY_SIGNATURES = {
     'mzr_priorities_f32': (_I, [_VP, _VP, _I64, _VP]),
     'mzr_update_errors_f32': (_I, [_VP, _VP, _VP, _I64]),
     'mzr_sample_batches_full': (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'mzr_reanalyse_pick': (_I64, [_VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP]),
+    'mzr_reanalyse_write': (_I64, [_VP, _U64, _VP, _I64, _VP]),
+    'mzr_reanalyse_release': (_I, [_VP, _U64]),
     'mzr_store_release_i64': (None, [_VP, _I64]),
     'mzr_load_acquire_i64': (_I64, [_VP]),
 }

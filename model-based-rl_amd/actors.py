@@ -212,6 +212,8 @@ class Actor(Logger):
     self._launched = False
     self.record_tap = None      # (tests: callable(records [n, B, rec] numpy view) on every chunk before it is ingested)
     self.last_run = {}
+    self.reanalyser = None      # reanalyse.Reanalyser of the device loop (--reanalyse_rows), made on its first pass
+    self.reanalyse_runs, self.reanalyse_skipped, self._reanalysed_at = 0, 0, 0
     self._turns = None
     if getattr(config, 'gpu_turns', False):      # --gpu_turns: an actor and a learner of this process share ONE GPU (gpu_turns.py)
       from . import gpu_turns
@@ -251,6 +253,8 @@ class Actor(Logger):
     weights, training_step = _call(self.storage, 'get_weights', self.games_played, self.actor_key)
     if training_step != self.training_step or force:
       self._set_weights(weights)
+      if getattr(self.config, 'reanalyse_rows', 0):
+        self._pulled_weights = weights      # (the set a Reanalyse pass after this pull searches with)
       self.training_step = training_step
       self.weight_pulls += 1
 
@@ -435,6 +439,7 @@ class Actor(Logger):
       self.experiences_collected += m * eng.B
       if (self.move_counter // sync_every) != ((self.move_counter - m) // sync_every):
         self.sync_weights()
+        self._maybe_reanalyse()
         # actors.py:128-129: the temperature of the schedule is evaluated at the start of every game; on the device the
         # new value reaches each environment at its next episode start (games in progress keep theirs)
         if self._temperature() != self._selfplay_temperature:
@@ -444,6 +449,43 @@ class Actor(Logger):
     self.last_run = {'moves': self.move_counter - moves0, 'seconds': time.perf_counter() - t0, 'chunk': chunk,
                      'weight_pulls': self.weight_pulls - pulls0}
     self.sync_weights(force=True)
+
+  def _maybe_reanalyse(self):
+    """--reanalyse_rows N: after a weight pull whose training step crossed a multiple of --reanalyse_every, N stored rows of the
+    replay are searched again under the just-pulled weights and their child_visits / root_value rewritten (reanalyse.py), in
+    this actor's turn on the device"""
+    cfg = self.config
+    rows = int(getattr(cfg, 'reanalyse_rows', 0) or 0)
+    if rows <= 0:
+      return None
+    every = max(1, int(getattr(cfg, 'reanalyse_every', None) or cfg.weight_sync_frequency))
+    if self.training_step // every == self._reanalysed_at // every:
+      return None
+    import contextlib
+    from .distributed import FlatWeights
+    from .reanalyse import Reanalyser
+    weights = getattr(self, '_pulled_weights', None)
+    if weights is None:
+      return None
+    self._reanalysed_at = self.training_step
+    if isinstance(weights, FlatWeights):      # (refused in train: --ranks above 1)
+      raise RuntimeError('--reanalyse_rows: broadcast weight buffers (multi-rank runs) are not reanalysed')
+    if self._pipe is not None:
+      self._pipe.join()      # every chunk played so far is in the replay before the pass walks it
+    turn = self._turns.turn(self.device) if self._turns is not None else contextlib.nullcontext()
+    with turn:      # (the reanalyser's own engine, kernels and pinned buffers are made in the turn too)
+      if self.reanalyser is None:
+        self.reanalyser = Reanalyser(cfg, self.replay_buffer, device=self.device)
+      self.reanalyser.set_weights(weights)
+      out = self.reanalyser.run(rows)
+    self.last_reanalyse = out
+    if out['busy']:      # another actor's pass holds the shared replay's one ticket: this pull's pass is left out
+      self.reanalyse_skipped += 1
+      return out
+    self.reanalyse_runs += 1
+    for tag in ('rows', 'slices', 'skipped_slices', 'seconds', 'mean_abs_value_change', 'mean_policy_l1'):
+      self.log_scalar(tag='reanalyse/' + tag, value=out[tag], i=self.training_step)
+    return out
 
   def _hand_over(self, buf, n):
     """one chunk of records, on the pipeline's worker thread: the games this actor finished (actors.py:94-99 counts one per

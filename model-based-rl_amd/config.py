@@ -145,6 +145,11 @@ def build_parser():
   a('--split_f16', action='store_true',
     help='FCNetwork GEMMs of the search as float16 high/low splits on the f16 matrix pipe (float32-level accuracy, not '
          'bit-identical to the exact-float32 default; include/mz_engine.h mz_config.split_f16)')
+  a('--reanalyse_rows', type=int, default=0,
+    help='MuZero Reanalyse: stored replay rows searched again under the just-pulled weights per pass, their child_visits and '
+         'root_value rewritten in place (reanalyse.py); 0: off')
+  a('--reanalyse_every', type=int, default=None,
+    help='learner steps between Reanalyse passes (default: --weight_sync_frequency); a pass follows the first weight pull past each multiple')
   a('--parity_rng', action='store_true',
     help="draw Dirichlet noise / action samples from numpy's global stream in the reference's order")
   return p

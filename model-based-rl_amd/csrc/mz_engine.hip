@@ -33,6 +33,7 @@
 #include "mz_eval.hip.h"
 #include "mz_eval_env.hip.h"
 #include "mz_match.hip.h"
+#include "mz_reanalyse.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
@@ -169,6 +170,7 @@ struct mz_engine {
   unsigned long long ev_moves = 0;  // moves enqueued since mz_eval_env_reset: keys the device draws, indexes the given ones
   double ev_temp = 0.0;             // the temperature es.temp holds
   bool ev_temp_set = false;
+  ReanalyseState ra = {};           // Reanalyse of stored replay rows (mz_reanalyse; mz_reanalyse.hip.h), allocated on first use
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -1621,6 +1623,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 #include "mz_selfplay_abi.inc"
 #include "mz_eval_abi.inc"
 #include "mz_match_abi.inc"
+#include "mz_reanalyse_abi.inc"
 #include "mz_fcl_abi.inc"
 
 }  // extern "C"

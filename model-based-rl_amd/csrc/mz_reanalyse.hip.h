@@ -1,0 +1,75 @@
+// mz_reanalyse.hip.h -- MuZero Reanalyse on the device (mz_reanalyse, mz_reanalyse_abi.inc): stored positions of the replay are
+// searched again under the current weights, B rows at a time, and only what the replay needs comes back (gfx950; included by
+// mz_engine.hip, -ffp-contract=off):
+//
+//   k_reanalyse_observe  from a chunk of record rows in PINNED HOST memory (the layout of mz_selfplay_drain / mzr_reanalyse_pick)
+//                        to the engine's obs / legal / to_play inputs, one thread per observation element
+//   k_reanalyse_store    from the searched trees to the rows' fresh statistics in pinned host memory: child_visits[A] as float32,
+//                        then the root's value as a float64 in two float slots -- the record's own layout from the observation's
+//                        end on --, one thread per output float; the arithmetic is mz_finalize_tree's (mz_root_visit_sum /
+//                        mz_root_visit_share / mz_root_mean_value, mz_tree.hip.h), not restated
+//
+// Between the two run mz_initial_inference, mz_root_prepare (no noise) and mz_search, unchanged.
+#pragma once
+#include "mz_common.h"
+#include "mz_selfplay.hip.h"
+
+// Separate from SelfplayState / EvalState / MatchState: self-play, evaluation and matches on the same engine are untouched.
+struct ReanalyseState {
+  float *obs;            // [Bp][O]
+  uint8_t *legal;        // [B][A]
+  int8_t *to_play;       // [B]
+};
+
+// The legal actions of a stored position, from its observation alone, as a bit mask; kind as in mz_selfplay_set_env:
+//   0 synthetic, 2 CartPole: every action;
+//   1 TicTacToe: the observation is to_play * board, cell k is free iff obs[k] == 0;
+//   3 Connect Four: the observation is turn * board, column c is open iff its top cell obs[35 + c] == 0 (mz_c4_view on it).
+__host__ __device__ inline uint32_t mz_reanalyse_legal_mask(int kind, const float *obs, int A) {
+  uint32_t mask = 0;
+  if (kind == 1) {
+    for (int k = 0; k < 9; ++k) mask |= (obs[k] == 0.f ? 1u : 0u) << k;
+  } else if (kind == 3) {
+    for (int c = 0; c < 7; ++c) mask |= (obs[35 + c] == 0.f ? 1u : 0u) << c;
+  } else {
+    mask = A >= 32 ? 0xFFFFFFFFu : ((1u << A) - 1u);
+  }
+  return mask;
+}
+
+// rows: the chunk's first row, [n][R] with R = O + A + MZR_REC_EXTRA; the flags word is the int32 at float slot O + A + 6 (bit 1:
+// to_play == -1).  One thread per (row, observation element): neighbouring threads read neighbouring floats of the host row;
+// the row's first thread also derives legal / to_play.  Rows b >= n of the chunk get what k_eval_observe feeds a finished game:
+// a zero observation, every action legal, to_play +1.
+static __global__ void k_reanalyse_observe(ReanalyseState rs, const float *rows, int n, int R, int kind, int B, int O, int A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * O) return;
+  const int b = i / O, k = i - b * O;
+  const bool real = b < n;
+  const float *row = rows + (size_t)(real ? b : 0) * R;      // (never dereferenced for a row past n)
+  rs.obs[i] = real ? row[k] : 0.f;
+  if (k != 0) return;
+  uint8_t *legal = rs.legal + (size_t)b * A;
+  const uint32_t mask = real ? mz_reanalyse_legal_mask(kind, row, A) : 0xFFFFFFFFu;
+  for (int a = 0; a < A; ++a) legal[a] = (uint8_t)((mask >> a) & 1u);
+  const int32_t flags = real ? ((const int32_t *)(row + O + A + 5))[1] : 0;
+  rs.to_play[b] = (flags & 2) ? (int8_t)-1 : (int8_t)1;
+}
+
+// fresh: the chunk's first row, [n][A + 2]; nothing is stored for b >= n.  One thread per (row, float slot): slots 0..A-1 the
+// visit shares, slots A and A + 1 the low and the high half of the root value's float64 (a row of A + 2 floats is 4-byte
+// aligned only).  Plain vector stores.
+static __global__ void k_reanalyse_store(TreeView t, float *fresh, int n) {
+  const int A = t.A, F = A + 2;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = i / F, j = i - b * F;
+  if (b >= t.B || b >= n) return;
+  const size_t o = mz_slab(t, b);
+  if (j < A) {
+    const uint32_t legal = t.legal[b];
+    fresh[i] = (float)mz_root_visit_share(t, o, legal, j, mz_root_visit_sum(t, o, legal));
+  } else {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(mz_root_mean_value(t, o));
+    ((uint32_t *)fresh)[i] = j == A ? (uint32_t)bits : (uint32_t)(bits >> 32);
+  }
+}

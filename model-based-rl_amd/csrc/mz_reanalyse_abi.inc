@@ -1,0 +1,65 @@
+// mz_reanalyse_abi.inc -- C ABI of MuZero Reanalyse on the device (included inside extern "C" of mz_engine.hip; kernels and
+// state: mz_reanalyse.hip.h).  Stored rows of the replay (mzr_reanalyse_pick, include/mz_replay.h) are searched again under the
+// engine's current weights, chunk by chunk, and the fresh child_visits / root_value come back in the layout mzr_reanalyse_write
+// takes.  Like mz_eval_env_moves / mz_match_plies: whole chunks are enqueued, the host touches nothing in between.
+
+static int reanalyse_shape(const mz_engine *e, int kind, const char **why) {
+  const bool two = e->cfg.two_players != 0;
+  if (kind == 1 && (e->O != 9 || e->A != 9 || !two)) { *why = "TicTacToe needs obs_dim 9, action_space 9, two_players"; return -1; }
+  if (kind == 2 && (e->O != 4 || e->A != 2 || two)) { *why = "CartPole needs obs_dim 4, action_space 2, a single player"; return -1; }
+  if (kind == 3 && (e->O != 42 || e->A != 7 || !two)) { *why = "Connect Four needs obs_dim 42, action_space 7, two_players"; return -1; }
+  return 0;
+}
+
+int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
+                 int num_simulations, void *stream) {
+  if (!e) return fail("mz_reanalyse: null engine");
+  MZ_ENTER(e);
+  if (!e->weights_set) return fail("mz_reanalyse: weights not set (call mz_set_weights)");
+  if (rec_floats != e->O + e->A + MZ_REC_EXTRA)      // (= MZR_REC_EXTRA of include/mz_replay.h: one record layout)
+    return fail("mz_reanalyse: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, e->O + e->A + MZ_REC_EXTRA);
+  if (kind < 0 || kind > 3)
+    return fail("mz_reanalyse: kind must be 0 (synthetic), 1 (TicTacToe), 2 (CartPole) or 3 (Connect Four), got %d", kind);
+  const char *why = nullptr;
+  if (reanalyse_shape(e, kind, &why)) return fail("mz_reanalyse: %s", why);
+  if (n_rows < 0) return fail("mz_reanalyse: n_rows must be >= 0, got %d", n_rows);
+  if (num_simulations < 1 || num_simulations > e->sims)
+    return fail("mz_reanalyse: num_simulations must be in 1 .. %d (the engine's pool), got %d", e->sims, num_simulations);
+  if (n_rows == 0) return 0;
+  if (!rows_host || !fresh_host) return fail("mz_reanalyse: null buffer");
+  const float *rows_dev = nullptr;
+  float *fresh_dev = nullptr;
+  if (hipHostGetDevicePointer((void **)&rows_dev, (void *)rows_host, 0) != hipSuccess || !rows_dev ||
+      hipHostGetDevicePointer((void **)&fresh_dev, (void *)fresh_host, 0) != hipSuccess || !fresh_dev) {
+    (void)hipGetLastError();
+    return fail("mz_reanalyse: rows and fresh must be page-locked (pinned) host memory");
+  }
+  ReanalyseState &rs = e->ra;
+  const int B = e->B, O = e->O, A = e->A;
+  if (!rs.to_play) {      // allocated on the first call (which therefore synchronises: hipMalloc + hipMemset); to_play is the last one
+    rs = ReanalyseState{};      // (an earlier call that failed half-way starts over: what it got stays with the engine's allocations)
+    if (dmalloc(e, &rs.obs, (size_t)e->Bp * O) || dmalloc(e, &rs.legal, (size_t)B * A) || dmalloc(e, &rs.to_play, (size_t)B)) {
+      rs = ReanalyseState{};
+      return -1;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 block(128), grid_obs(((size_t)B * O + 127) / 128), grid_store(((size_t)B * (A + 2) + 127) / 128);
+  int rc = 0;
+  for (int at = 0; at < n_rows && !rc; at += B) {
+    const int n = n_rows - at < B ? n_rows - at : B;
+    hipLaunchKernelGGL(k_reanalyse_observe, grid_obs, block, 0, s, rs, rows_dev + (size_t)at * rec_floats, n, rec_floats, kind, B, O, A);
+    if (hipGetLastError() != hipSuccess) { rc = fail("mz_reanalyse: k_reanalyse_observe did not launch"); break; }
+    rc = mz_initial_inference(e, rs.obs, s) || mz_root_prepare(e, rs.to_play, rs.legal, nullptr, 0, 0, s) ||
+         mz_search(e, num_simulations, s);
+    if (rc) break;
+    hipLaunchKernelGGL(k_reanalyse_store, grid_store, block, 0, s, e->tv, fresh_dev + (size_t)at * (A + 2), n);
+    if (hipGetLastError() != hipSuccess) rc = fail("mz_reanalyse: k_reanalyse_store did not launch");
+  }
+  if (rc) {      // what was enqueued still reads / writes the caller's buffers: let it end before they are handed back
+    (void)hipStreamSynchronize(s);
+    return -1;
+  }
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}

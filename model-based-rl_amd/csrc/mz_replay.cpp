@@ -46,6 +46,7 @@ struct Hist {
   int64_t off = 0;              // first row of the slice inside `rows` (a finished game hands its whole buffer over)
   int64_t refs = 0;             // leaves pointing at this slice (touched by the inserting thread only)
   bool payload = false;         // rows carry observations / policies / values (mzr_save_history may omit them)
+  uint64_t picked = 0;          // the reanalyse ticket that last took this slice (mzr_reanalyse_pick: a pass takes a slice once)
   std::vector<float> rows;
 };
 
@@ -169,6 +170,11 @@ struct mz_replay {
   // ingest threads ran SLOWER than one thread's
   std::mutex spare_mu;
   std::vector<std::vector<float>> hist_spare;
+  // Reanalyse (mzr_reanalyse_pick / _write / _release): the walk's cursor over the leaves, and the ONE outstanding ticket -- the
+  // slices it took, each held by one reference of its own (as a leaf holds one), so that they outlive their leaves' eviction
+  int64_t re_cursor = 0, re_rows = 0;
+  uint64_t re_last = 0, re_ticket = 0;          // the last ticket number handed out; the outstanding one (0: none)
+  std::vector<Hist *> re_slices;
 };
 #define MZR_LOCK(r) std::lock_guard<std::recursive_mutex> api_lock_(const_cast<mz_replay *>(r)->api_mu)
 
@@ -455,6 +461,9 @@ int mzr_destroy(mz_replay *r) {
   if (r) {
     stop_inserter(r);
     r->pool.stop();
+    for (Hist *h : r->re_slices)
+      if (--h->refs == 0) delete h;
+    r->re_slices.clear();
     for (int64_t i = 0; i < (int64_t)r->leaf_hist.size();) {
       Hist *h = r->leaf_hist[(size_t)i];
       int64_t j = i + 1;
@@ -1284,6 +1293,107 @@ int mzr_ingest_slices(mz_replay *r, const void *blob, int64_t bytes, int env_bas
     r->queue.push_back(std::move(job));
   }
   r->qcv.notify_one();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ reanalyse
+// The stored child_visits / root_value of a slice are those of the weights that played it; mzr_sample_batch builds its targets from
+// them at sampling time.  A pass takes whole slices out (pick), a search under newer weights computes fresh statistics for their rows,
+// and write puts exactly those two fields back.  The unit is the SLICE, not the leaf: the value target of step s reads root_value of
+// row s + td_steps, which may lie in the slice's ignored tail that no leaf points at.  Every call drains the deferred insertions and
+// runs under the handle's lock: Hist::refs is then touched by this thread alone.
+
+static void drop_ticket(mz_replay *r) {
+  for (Hist *h : r->re_slices)
+    if (--h->refs == 0) retire(r, h);
+  r->re_slices.clear();
+  r->re_rows = 0;
+  r->re_ticket = 0;
+}
+
+int64_t mzr_reanalyse_pick(mz_replay *r, int64_t max_rows, float *rows_out, int32_t *slice_rows_out, int64_t max_slices,
+                           int64_t *n_slices, uint64_t *ticket, int64_t *info) {
+  if (!r || !rows_out || !slice_rows_out || !n_slices || !ticket || max_rows < 0 || max_slices < 0)
+    return fail("mzr_reanalyse_pick: bad argument");
+  MZR_LOCK(r);
+  drain(r);
+  if (r->c.obs_u8) return fail("mzr_reanalyse_pick: a replay with byte observations (obs_u8) cannot be reanalysed");
+  if (r->re_ticket) {      // -2, not -1: a caller that shares the handle (several actors, one replay) can tell "busy" from an error
+    fail("mzr_reanalyse_pick: ticket %llu is still outstanding (write or release it first)", (unsigned long long)r->re_ticket);
+    return -2;
+  }
+  const int64_t cap = r->capacity;
+  const size_t R = (size_t)r->R;
+  const uint64_t id = ++r->re_last;
+  int64_t rows = 0, slices = 0, skipped = 0, walked = 0;
+  int64_t pos = r->re_cursor < cap ? r->re_cursor : 0;
+  while (walked < cap) {
+    Hist *h = r->leaf_hist[(size_t)pos];
+    int64_t e = pos + 1;                                  // the run of leaves that share h, up to the end of the ring
+    while (e < cap && e - pos < cap - walked && r->leaf_hist[(size_t)e] == h) ++e;
+    // a run at leaf 0 that continues the ring's last run is that slice's second half: it is taken where the walk meets its first
+    const bool wrapped_half = pos == 0 && cap > 1 && h == r->leaf_hist[(size_t)(cap - 1)] && e < cap;
+    if (h && h->payload && h->picked != id && !wrapped_half) {
+      if (h->n > max_rows) {
+        ++skipped;
+        h->picked = id;
+      } else {
+        if (rows + h->n > max_rows || slices + 1 > max_slices) break;      // the next call starts at this slice
+        memcpy(rows_out + (size_t)rows * R, h->rows.data() + (size_t)h->off * R, (size_t)h->n * R * sizeof(float));
+        slice_rows_out[slices++] = (int32_t)h->n;
+        rows += h->n;
+        h->picked = id;
+        h->refs += 1;
+        r->re_slices.push_back(h);
+      }
+    }
+    walked += e - pos;
+    pos = e == cap ? 0 : e;
+  }
+  r->re_cursor = pos;
+  r->re_rows = rows;
+  r->re_ticket = slices ? id : 0;
+  *n_slices = slices;
+  *ticket = r->re_ticket;
+  if (info) info[0] = skipped;
+  return rows;
+}
+
+int64_t mzr_reanalyse_write(mz_replay *r, uint64_t ticket, const float *fresh, int64_t n_rows, double *stats_out) {
+  if (!r || !fresh) return fail("mzr_reanalyse_write: null argument");
+  MZR_LOCK(r);
+  drain(r);
+  if (!ticket || ticket != r->re_ticket) return fail("mzr_reanalyse_write: %llu is not the outstanding ticket", (unsigned long long)ticket);
+  if (n_rows != r->re_rows)
+    return fail("mzr_reanalyse_write: the ticket holds %lld rows, the caller brings %lld", (long long)r->re_rows, (long long)n_rows);
+  const int OS = r->OS, A = r->c.action_space;
+  const size_t R = (size_t)r->R, F = (size_t)A + 2;
+  int64_t written = 0, at = 0;
+  double dv = 0.0, dp = 0.0;
+  for (Hist *h : r->re_slices) {
+    if (h->refs > 1) {                                    // a slice all of whose leaves were evicted meanwhile is only dropped
+      float *q = h->rows.data() + (size_t)h->off * R + OS;
+      const float *f = fresh + (size_t)at * F;
+      for (int64_t i = 0; i < h->n; ++i, q += R, f += F) {
+        for (int a = 0; a < A; ++a) dp += fabs((double)f[a] - (double)q[a]);
+        dv += fabs(row_double(f + A) - row_double(q + A));
+        memcpy(q, f, F * sizeof(float));                  // child_visits[A], root_value: the row's own layout from OS on
+      }
+      written += h->n;
+    }
+    at += h->n;
+  }
+  drop_ticket(r);
+  if (stats_out) { stats_out[0] = (double)written; stats_out[1] = dv; stats_out[2] = dp; }
+  return written;
+}
+
+int mzr_reanalyse_release(mz_replay *r, uint64_t ticket) {
+  if (!r) return fail("mzr_reanalyse_release: null handle");
+  MZR_LOCK(r);
+  drain(r);
+  if (!ticket || ticket != r->re_ticket) return fail("mzr_reanalyse_release: %llu is not the outstanding ticket", (unsigned long long)ticket);
+  drop_ticket(r);
   return 0;
 }
 

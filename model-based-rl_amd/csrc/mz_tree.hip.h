@@ -825,6 +825,22 @@ __device__ __forceinline__ int mz_sample_index(double *d, int n, double T, doubl
   return idx;
 }
 
+// Game.store_search_statistics (game.py:106-115) for the root of the tree whose slab starts at o: the visits of the legal
+// children summed, child a's share of them as a float64 (0 for an illegal action), and the root's mean value.  Shared by
+// mz_finalize_tree and k_reanalyse_store (mz_reanalyse.hip.h).
+__device__ __forceinline__ long mz_root_visit_sum(const TreeView &t, size_t o, uint32_t legal) {
+  long sumv = 0;
+  for (int a = 0; a < t.A; ++a)
+    if ((legal >> a) & 1u) sumv += t.N[o + 1 + a];
+  return sumv;
+}
+__device__ __forceinline__ double mz_root_visit_share(const TreeView &t, size_t o, uint32_t legal, int a, long sumv) {
+  return ((legal >> a) & 1u) ? (double)t.N[o + 1 + a] / (double)sumv : 0.0;
+}
+__device__ __forceinline__ double mz_root_mean_value(const TreeView &t, size_t o) {
+  return t.N[o] == 0 ? 0.0 : t.W[o] / (double)t.N[o];
+}
+
 // Config.select_action (config.py:70-81) + Game.store_search_statistics (game.py:106-115) + root error
 // (actors.py:147-148).  One thread per tree (A <= 32 children, once per move).
 __device__ __forceinline__ void mz_finalize_tree(const TreeView &t, int b, const double *temperature,
@@ -837,18 +853,18 @@ __device__ __forceinline__ void mz_finalize_tree(const TreeView &t, int b, const
   int acts[MZ_MAX_ACTIONS_K];
   double d[MZ_MAX_ACTIONS_K];
   int n = 0;
-  long sumv = 0;
   for (int a = 0; a < A; ++a) {
     const bool ok = (legal >> a) & 1u;
     const int c = ok ? t.N[o + 1 + a] : 0;
     if (visit_counts) visit_counts[(size_t)b * A + a] = c;
     if (!ok) continue;
-    acts[n] = a; d[n] = (double)c; sumv += c; ++n;
+    acts[n] = a; d[n] = (double)c; ++n;
   }
-  if (child_visits)
-    for (int a = 0; a < A; ++a)
-      child_visits[(size_t)b * A + a] = ((legal >> a) & 1u) ? (double)t.N[o + 1 + a] / (double)sumv : 0.0;
-  const double rv = t.N[o] == 0 ? 0.0 : t.W[o] / (double)t.N[o];
+  if (child_visits) {
+    const long sumv = mz_root_visit_sum(t, o, legal);
+    for (int a = 0; a < A; ++a) child_visits[(size_t)b * A + a] = mz_root_visit_share(t, o, legal, a, sumv);
+  }
+  const double rv = mz_root_mean_value(t, o);
   if (root_value) root_value[b] = rv;
   if (error) error[b] = rv - (double)t.root_value[b];
   if (!action) return;

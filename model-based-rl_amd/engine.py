@@ -462,6 +462,24 @@ class Engine(object):
       out[k] = acc[i]
     return out
 
+  # ---- Reanalyse of stored replay rows (mz_reanalyse, include/mz_engine.h)
+  def reanalyse(self, rows, fresh, n_rows, kind, num_simulations=None):
+    """mz_reanalyse: rows [>= n_rows, O + A + REC_EXTRA] and fresh [>= n_rows, A + 2], both PINNED float32 host tensors; the
+    first n_rows rows are searched again under the current weights in chunks of B, without exploration noise, and fresh
+    receives child_visits (float32) and root_value (float64 in two slots) per row -- what PrioritizedReplay.reanalyse_write
+    takes.  kind: an ENVS / EVAL_ENVS name or 0..3.  Returns when the last chunk has been stored."""
+    if isinstance(kind, str):
+      kind = self.ENVS[kind] if kind in self.ENVS else self.EVAL_ENVS[kind]
+    n_rows = int(n_rows)
+    for t, name, width in ((rows, 'rows', None), (fresh, 'fresh', self.A + 2)):
+      if not (torch.is_tensor(t) and t.dtype == torch.float32 and not t.is_cuda and t.is_pinned() and t.is_contiguous() and t.dim() == 2):
+        raise ValueError('reanalyse: %s must be a contiguous pinned float32 host tensor [rows, floats]' % name)
+      if t.shape[0] < n_rows or (width is not None and t.shape[1] != width):
+        raise ValueError('reanalyse: %s has shape %s for %d rows of %s floats' % (name, tuple(t.shape), n_rows, width or 'rec_floats'))
+    sims = self.sims if num_simulations is None else int(num_simulations)
+    _abi.check(self.lib.mz_reanalyse(self._h, int(kind), _ptr(rows), int(rows.shape[1]), n_rows, _ptr(fresh), sims, self.stream),
+               'mz_reanalyse')
+
   def export_tree(self, hidden=False):
     B, NN, A = self.B, self.NN, self.A
     d = dict(N=np.zeros((B, NN), np.int32), W=np.zeros((B, NN)), P=np.zeros((B, NN)),

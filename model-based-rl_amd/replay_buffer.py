@@ -192,6 +192,65 @@ class PrioritizedReplay(object):
     ptr = C.c_void_p(blob.data_ptr()) if hasattr(blob, 'data_ptr') else C.c_void_p(np.asarray(blob).ctypes.data)
     _abi.check_replay(self.lib.mzr_ingest_slices(self._h, ptr, int(nbytes), int(env_base)), 'mzr_ingest_slices')
 
+  # ---- reanalyse (include/mz_replay.h): whole history slices out, fresh child_visits / root_value back in
+  @property
+  def rec_floats(self):
+    from .engine import REC_EXTRA
+    u8, O, A = self.tree._rows
+    return ((O + 3) // 4 if u8 else O) + A + REC_EXTRA
+
+  @staticmethod
+  def _float_rows(a, name, width):
+    """a float32, C-contiguous [rows, width] host array or tensor, as the native calls read / write it through its address"""
+    if hasattr(a, 'data_ptr'):
+      import torch
+      ok = a.dtype == torch.float32 and not a.is_cuda and a.is_contiguous() and a.dim() == 2
+    else:
+      ok = isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags['C_CONTIGUOUS'] and a.ndim == 2
+    if not ok or int(a.shape[1]) != width:
+      raise ValueError('%s must be a contiguous float32 host array or tensor [rows, %d], got %s %s' %
+                       (name, width, getattr(a, 'dtype', type(a)), tuple(getattr(a, 'shape', ()))))
+    return a
+
+  def reanalyse_pick(self, max_rows, out=None, busy_ok=False):
+    """the next slices of the walk over the leaves, all their rows as stored: -> dict(ticket, rows [n, rec_floats] (a view of
+    `out`, a float32 host array / pinned tensor of at least max_rows rows, when given), n_rows, slice_rows int32 [slices],
+    skipped_slices, busy).  ticket 0: nothing was picked (an empty replay).  The slices stay alive until reanalyse_write /
+    reanalyse_release(ticket); one ticket may be outstanding: a pick meanwhile raises, or with busy_ok (callers that share the
+    replay: several actors) returns busy = True and nothing picked."""
+    max_rows, R = int(max_rows), self.rec_floats
+    if out is None:
+      out = np.empty((max_rows, R), np.float32)
+    self._float_rows(out, 'reanalyse_pick: out', R)
+    if int(out.shape[0]) < max_rows:
+      raise ValueError('reanalyse_pick: out must hold %d rows of %d floats, got %s' % (max_rows, R, tuple(out.shape)))
+    ptr = C.c_void_p(out.data_ptr()) if hasattr(out, 'data_ptr') else _p(out)
+    slice_rows = np.empty(max(1, max_rows), np.int32)
+    n_slices, ticket, info = C.c_int64(0), C.c_uint64(0), C.c_int64(0)
+    n = int(self.lib.mzr_reanalyse_pick(self._h, max_rows, ptr, _p(slice_rows), slice_rows.size, C.byref(n_slices), C.byref(ticket),
+                                        C.byref(info)))
+    if n == -2 and busy_ok:
+      return {'ticket': 0, 'rows': out[:0], 'n_rows': 0, 'slice_rows': slice_rows[:0].copy(), 'skipped_slices': 0, 'busy': True}
+    if n < 0:
+      _abi.check_replay(-1, 'mzr_reanalyse_pick')
+    return {'ticket': int(ticket.value), 'rows': out[:n], 'n_rows': n, 'slice_rows': slice_rows[:n_slices.value].copy(),
+            'skipped_slices': int(info.value), 'busy': False}
+
+  def reanalyse_write(self, ticket, fresh):
+    """fresh: float32 [n_rows, A + 2] (child_visits, then root_value as a float64 in two slots) for the ticket's rows in pick
+    order -> dict(rows, abs_value_change, policy_l1): rows written and the sums of |new - old| over them"""
+    if not hasattr(fresh, 'data_ptr'):
+      fresh = np.ascontiguousarray(fresh, np.float32)
+    self._float_rows(fresh, 'reanalyse_write: fresh', self.action_space + 2)
+    ptr = C.c_void_p(fresh.data_ptr()) if hasattr(fresh, 'data_ptr') else _p(fresh)
+    stats = np.zeros(3, np.float64)
+    if self.lib.mzr_reanalyse_write(self._h, int(ticket), ptr, int(fresh.shape[0]), _p(stats)) < 0:
+      _abi.check_replay(-1, 'mzr_reanalyse_write')
+    return {'rows': int(stats[0]), 'abs_value_change': float(stats[1]), 'policy_l1': float(stats[2])}
+
+  def reanalyse_release(self, ticket):
+    _abi.check_replay(self.lib.mzr_reanalyse_release(self._h, int(ticket)), 'mzr_reanalyse_release')
+
   # replay_buffer.py:124-163 (+ insert_target 165-198 inside the native call)
   def sample_batch_arrays(self):
     """sample_batch as the arrays the learner step consumes, no Python lists in between: (dict obs float32 [bs, ...], act

@@ -77,6 +77,10 @@ def main():
   ap.add_argument('--out', default=None)
   ap.add_argument('--no_support', action='store_true')
   ap.add_argument('--scalar_loss', default='MSE', choices=['MSE', 'Huber'])
+  ap.add_argument('--reanalyse_rows', type=int, default=0, help='train --reanalyse_rows (0: off)')
+  ap.add_argument('--reanalyse_every', type=int, default=None, help='train --reanalyse_every')
+  ap.add_argument('--keep_checkpoint', default=None, help='copy the run\'s last checkpoint to this file')
+  ap.add_argument('--match_against', default=None, help='a checkpoint kept by another run: the last checkpoint also plays it, from both seats')
   a = ap.parse_args()
   from model_based_rl_amd import train
   from model_based_rl_amd.config import make_config
@@ -86,6 +90,9 @@ def main():
           '--known_bounds', '-1', '1', '--num_simulations', '30', '--seed', '0', '--num_envs', str(a.num_envs)]
   if a.no_support:
     base += ['--no_support', '--scalar_loss', a.scalar_loss]
+  extra = ['--reanalyse_rows', str(a.reanalyse_rows)] if a.reanalyse_rows else []
+  if a.reanalyse_rows and a.reanalyse_every:
+    extra += ['--reanalyse_every', str(a.reanalyse_every)]
   torch.manual_seed(0)
   untrained_sd = get_network(make_config(base), torch.device('cpu')).state_dict()
   if a.environment == 'TicTacToe':
@@ -95,7 +102,7 @@ def main():
   before = {side: match(untrained_sd, side) for side in (1, -1)}
   saves = os.path.join('/tmp', 'mz_%s_learning_%d' % ('ttt' if a.environment == 'TicTacToe' else 'c4', os.getpid()))
   t0 = time.time()
-  thr = train.main(base + ['--max_moves', '-1', '--training_steps', str(a.training_steps), '--stored_before_train', '20000',
+  thr = train.main(base + extra + ['--max_moves', '-1', '--training_steps', str(a.training_steps), '--stored_before_train', '20000',
                            '--batch_size', '256', '--window_size', '200000', '--send_weights_frequency', '100',
                            '--weight_sync_frequency', '16', '--use_gpu_for', 'actors', 'learner', '--gpu_turns', '--runs_dir', saves,
                            '--run_tag', 'learn', '--save_state_frequency', str(a.training_steps), '--learner_log_frequency', '500'])
@@ -121,12 +128,20 @@ def main():
       setattr(cfg, k, v)
     return {'config': cfg, 'weights': st['weights'], 'training_step': st['training_step']}
   _, vs_first = play_match(side(state), side(first), 256, list(range(256)), opening_plies=2, batch=256)
-  out = {'recipe': ' '.join(base), 'training_steps': int(state['training_step']), 'train_seconds': seconds,
+  out = {'recipe': ' '.join(base + extra), 'training_steps': int(state['training_step']), 'train_seconds': seconds,
          'selfplay_frames': thr['frames'], 'selfplay_games': thr['games'], 'learner': thr.get('learner'),
          'vs_random_512_games': {'untrained': {'agent_first (win, draw, loss)': before[1], 'agent_second': before[-1]},
                                  'trained': {'agent_first (win, draw, loss)': after[1], 'agent_second': after[-1]}},
          'match_last_vs_first': dict(vs_first, a='checkpoint %d' % int(state['training_step']), b=opponent, seeds=256,
                                      opening_plies=2)}
+  if a.keep_checkpoint:
+    torch.save({'weights': state['weights'], 'training_step': int(state['training_step'])}, a.keep_checkpoint)
+  if a.match_against:
+    other = torch.load(a.match_against, map_location='cpu', weights_only=False)
+    _, vs_other = play_match(side(state), side(other), 256, list(range(256)), opening_plies=2, batch=256)
+    out['match_last_vs_given'] = dict(vs_other, a='this run, checkpoint %d' % int(state['training_step']),
+                                      b='%s, checkpoint %d' % (os.path.basename(a.match_against), int(other['training_step'])),
+                                      seeds=256, opening_plies=2)
   print(json.dumps(out))
   if a.out:
     json.dump(out, open(a.out, 'w'), indent=1)
