@@ -301,8 +301,10 @@ static void fill_fc1_biascol(std::vector<int32_t> &idx, size_t wpos, const size_
 // exactly one 1, so the bias rides in the one-hot columns: their packed weight is W[n][50 + a] + b[n] (idx2 = the
 // bias element to add, k_pack_weights).  K = 50 + A columns instead of 51 + A: one k-step of four fewer for
 // A = 6, 10, 14, ... (Pong-ram: 14 steps instead of 15).
+// Kuse < K (the rows with an action table, mz_fused_atab): only the first Kuse = 50 columns are packed, the one-hot
+// columns + bias go into the table (fill_action_table).
 static void fill_fc1_foldbias(std::vector<int32_t> &idx, std::vector<int32_t> &idx2, size_t wpos, const size_t *woff,
-                              const size_t *boff, int K, int ks) {
+                              const size_t *boff, int K, int ks, int Kuse) {
   for (int w = 0; w < 4; ++w)
     for (int tg = 0; tg < 4; ++tg)
       for (int s = 0; s < ks; ++s)
@@ -311,9 +313,25 @@ static void fill_fc1_foldbias(std::vector<int32_t> &idx, std::vector<int32_t> &i
             const int t = 4 * tg + i, head = t / 8, tt = t % 8;
             const int nf = 128 * w + 16 * tt + (lane & 15), k = 4 * s + (lane >> 4);
             const size_t o = wpos + ((((size_t)(w * 4 + tg) * ks + s) * 64 + lane) * 4 + i);
-            idx[o] = k < K ? (int32_t)(woff[head] + (size_t)nf * K + k) : -1;
-            idx2[o] = (k >= MZ_H && k < K) ? (int32_t)(boff[head] + nf) : -1;
+            idx[o] = k < Kuse ? (int32_t)(woff[head] + (size_t)nf * K + k) : -1;
+            idx2[o] = (k >= MZ_H && k < Kuse) ? (int32_t)(boff[head] + nf) : -1;
           }
+}
+
+// the action table of one wave (mz_fused.hip.h): T[a][tile 0..15][g 0..3][r 0..3] = W[nf][50 + a] + b[nf] -- what lane row g
+// holds of accumulator tile `tile` (head tile / 8, feature nf = 128 w + 16 (tile % 8) + 4 g + r) once the one-hot columns
+// and the bias are in.  Scale class 1: it is part of the fc1 layer.  Actions >= A stay zero.
+static void fill_action_table(std::vector<int32_t> &idx, std::vector<int32_t> &idx2, size_t pos, int w, const size_t *woff,
+                              const size_t *boff, int K, int A) {
+  for (int a = 0; a < A && a < MZ_ATAB_AMAX; ++a)
+    for (int t = 0; t < 16; ++t)
+      for (int g = 0; g < 4; ++g)
+        for (int r = 0; r < 4; ++r) {
+          const int head = t / 8, nf = 128 * w + 16 * (t % 8) + 4 * g + r;
+          const size_t o = pos + (size_t)a * 256 + t * 16 + g * 4 + r;
+          idx[o] = (int32_t)(woff[head] + (size_t)nf * K + MZ_H + a) | (1 << 29);
+          idx2[o] = (int32_t)(boff[head] + nf);
+        }
 }
 
 // fc2 pack: [JT][4 waves][8 tiles][64][4]: A operand row j = 16jt + (lane&15), k = 128w + 16t + 4(lane>>4) + r
@@ -530,13 +548,16 @@ static int build_packing(mz_engine *e) {
   // fused kernel: fc1 weights with the bias inside the packed matrix -- prediction: one more input column (constant-1
   // input); dynamics: added to the one-hot columns (fill_fc1_foldbias); the k-step count is that of the kernel
   // instantiation chosen for this action count (zero-padded above 50+A)
-  const int ks1f = e->shape->ks1, ks3f = (MZ_H + 1 + 3) / 4;
+  // (rows with an action table: K = 50, 13 k-steps; the one-hot columns + bias are the table behind each wave's stream)
+  const bool atab = mz_fused_atab(e->shape->ks1, e->shape->jtp, e->shape->g);
+  const int ks1f = atab ? (MZ_H + 3) / 4 : e->shape->ks1, ks3f = (MZ_H + 1 + 3) / 4;
   const size_t p_w1f = seg((size_t)4 * 4 * ks1f * 256), p_w3f = seg((size_t)4 * 4 * ks3f * 256);
   const int nj2 = 2 + jtp;
   const int real_steps = ks1f + 12 + ks3f + 2 * nj2;
-  const int rs = mz_fused_rs(ks1f, jtp);
+  const int rs = mz_fused_rs(e->shape->ks1, jtp);
   const int nsteps = rs + (real_steps - rs + MZ_NB - 1) / MZ_NB * MZ_NB;   // FusedSched::NSTEPS
-  const size_t p_ws = seg((size_t)4 * nsteps * 4 * 256);
+  const size_t wstride = (size_t)nsteps * 4 * 256 + (atab ? MZ_ATAB_WAVE_FLOATS : 0);      // floats per wave
+  const size_t p_ws = seg(4 * wstride);
   // A operands of the small MFMA (mz_fused.hip.h): rows 48..51 of the next hidden state; the policy head when A <= 4
   const size_t p_h4 = seg((size_t)4 * 8 * 256), p_p4 = seg((size_t)4 * 8 * 256);
   const bool p4 = A <= 4;
@@ -570,7 +591,7 @@ static int build_packing(mz_engine *e) {
   fill_vec(idx, p_lnb, 64, L.ln_b, MZ_H);
   {
     size_t wo[2] = {L.rew_w1, L.tr_w1}, bo[2] = {L.rew_b1, L.tr_b1};
-    fill_fc1_foldbias(idx, idx2, p_w1f, wo, bo, MZ_H + A, ks1f);
+    fill_fc1_foldbias(idx, idx2, p_w1f, wo, bo, MZ_H + A, ks1f, atab ? MZ_H : MZ_H + A);
     size_t wo3[2] = {L.val_w1, L.pol_w1}, bo3[2] = {L.val_b1, L.pol_b1};
     fill_fc1_biascol(idx, p_w3f, wo3, bo3, MZ_H, ks3f);
   }
@@ -590,7 +611,7 @@ static int build_packing(mz_engine *e) {
     // cls: the scale class of the piece (bits 29-30 of its gather indices, k_pack_weights): 1 = an fc1 layer of the
     // search (times 2^-k), 2 = a layer that consumes its activations (times 2^k) -- k_relu_scale, mz_fused.hip.h
     auto put = [&](size_t src, int cls) {
-      const size_t d0 = p_ws + ((size_t)w * nsteps * 4 + piece) * 256;
+      const size_t d0 = p_ws + (size_t)w * wstride + piece * 256;
       for (int i = 0; i < 256; ++i) {
         idx[d0 + i] = idx[src + i] < 0 ? -1 : (idx[src + i] | (cls << 29));
         idx2[d0 + i] = idx2[src + i];
@@ -608,6 +629,10 @@ static int build_packing(mz_engine *e) {
         put(p4 && jt == 2 ? p_p4 + (size_t)(w * 8 + t) * 256 : p_w4 + ((size_t)(jt * 4 + w) * 8 + t) * 256, 2);
     if ((int)piece != real_steps * 4) return fail("internal: weight stream has %zu pieces, expected %d", piece, real_steps * 4);
     // the remaining (nsteps - real_steps) * 4 pieces are padding (index -1 -> 0.0), loaded but never used
+    if (atab) {
+      size_t wo[2] = {L.rew_w1, L.tr_w1}, bo[2] = {L.rew_b1, L.tr_b1};
+      fill_action_table(idx, idx2, p_ws + (size_t)w * wstride + (size_t)nsteps * 4 * 256, w, wo, bo, MZ_H + A, A);
+    }
   }
 
   // the root kernel's stream (mz_root.hip.h).  First stage, wave w, step st, piece p: k-step 2*st + (p>>1),
@@ -750,9 +775,14 @@ static SearchPlan search_plan(const mz_engine *e) {
   auto lds_static = [](int kind, int lt) { return sizeof(float) * (size_t)(kind == 2 ? mz_h2_lds_floats(lt) : mz_fused_lds_floats(lt)); };
   // trees in LDS when 16 of them fit beside the kernel's static LDS; if not, at least the fields the descent reads
   // (N, E, P, reward + discount * Q); else (0) in the global pool
+  // (k_search_fused, rows with an action table: the table shares the dynamic LDS with whole trees, and with the pool
+  // placement's pb_c table; beside compact trees it stays in global memory -- mz_fused_atab_lds)
+  auto atab_lds = [&](int kind, int lt) {
+    return kind == 1 ? mz_fused_atab_lds(mz_fused_atab(e->shape->ks1, e->shape->jtp, e->shape->g), e->A, lt) : (size_t)0;
+  };
   auto place = [&](int kind) {
     for (int lt = 1; lt <= (!e->use_lds_trees ? 0 : (e->use_lds_hybrid ? 2 : 1)); ++lt)
-      if (lds_fits(lds_static(kind, lt), mz_fused_dyn_lds(e->sims, e->NN, lt))) return lt;
+      if (lds_fits(lds_static(kind, lt), mz_fused_dyn_lds(e->sims, e->NN, lt) + atab_lds(kind, lt))) return lt;
     return 0;
   };
   p.fkind = 2;
@@ -761,8 +791,8 @@ static SearchPlan search_plan(const mz_engine *e) {
   p.shape = p.fkind == 2 ? e->shape_h2 : e->shape;
   p.sp = !e->cfg.two_players;       // single-player games (every reference environment but TicTacToe): no to_play handling
   p.lds_static = lds_static(p.fkind, p.lt);
-  p.dyn = mz_fused_dyn_lds(e->sims, e->NN, p.lt);
-  p.dyn_head = fused_head_dyn_lds(e->sims, e->NN, p.lt);
+  p.dyn = mz_fused_dyn_lds(e->sims, e->NN, p.lt) + atab_lds(p.fkind, p.lt);
+  p.dyn_head = fused_head_dyn_lds(e->sims, e->NN, p.lt) + atab_lds(p.fkind, p.lt);
   p.kind = fused_usable(e) && !e->root_hidden_external ? p.fkind : 0;
   p.game = e->sp.env_kind;
   // whole moves: LDS trees and a HEAD kernel -- single player on the synthetic environment, or the device TicTacToe

@@ -53,10 +53,37 @@ __device__ __forceinline__ void mz_static_for(F &&f) {
 __host__ __device__ constexpr int mz_fused_rs(int ks1, int jtp) { return jtp > 1 ? 9 : (ks1 > 16 ? 11 : (ks1 > 14 ? 12 : MZ_RS_MAIN)); }
 #define MZ_XE 36     // row stride of the x-tile extensions (k >= 50): dynamics [one-hot(action) | 0 ...], prediction [1 | 0 ...]
 
+// Action table (the rows of mz_kernels.inc for which mz_fused_atab holds: the A <= 4 row).  For one tree the one-hot
+// columns of the dynamics fc1 contribute nothing but W[n][50 + a] + b[n], a vector chosen by the tree's action: no
+// multiplication is needed for it.  The host packs that vector for every action as the accumulator tiles themselves
+// (T[a][tile 0..15][lane row g][r], per wave: what lane (g, .) of tile t holds), each lane reads its column's vector
+// straight into acc[0..15] before the first k-step, and that step accumulates instead of starting from zero.  The
+// dynamics fc1 is then K = 50: 13 k-steps instead of 14, all of them resident.  The term is the first addend of the
+// sum instead of the last: the same products in another float32 order.
+// -DMZ_ACTION_COLUMNS (development switch, A/B builds): the earlier form, K = 50 + A columns.
+__host__ __device__ constexpr bool mz_fused_atab(int ks1, int jtp, int g) {
+#ifdef MZ_ACTION_COLUMNS
+  return false;
+#else
+  return ks1 == 14 && jtp == 1 && g == 4;
+#endif
+}
+#define MZ_ATAB_AMAX 4                         // actions the packed table has room for (the row's largest action count)
+#define MZ_ATAB_WAVE_FLOATS (MZ_ATAB_AMAX * 256)   // one wave's slice behind its weight stream: [a][16 tiles][4 g][4 r]
+// LDS copy (trees in the pool or whole trees in LDS): [a][wave][256 floats], the action stride padded by 64 bytes so that
+// the four actions x four lane rows of one read cover 256 distinct bytes (lanes with the same action and lane row read
+// the same address: a broadcast).  Beside compact trees (lt = 2) the table stays in global memory.
+#define MZ_ATAB_LDS_STRIDE (4096 + 64)
+__host__ __device__ constexpr size_t mz_fused_atab_lds(bool atab, int A, int lt) {
+  return atab && lt != 2 ? (size_t)A * MZ_ATAB_LDS_STRIDE : 0;
+}
+
 // per-simulation schedule (in steps of 16 MFMAs per wave)
-template <int KS1, int JTP>
+template <int KS1, int JTP, bool ATAB = false>
 struct FusedSched {
-  static constexpr int FC1 = KS1;               // dynamics fc1: K = 50 + A (the bias rides in the one-hot columns), 4 per step
+  // dynamics fc1: K = 50 + A (the bias rides in the one-hot columns), 4 per step; with the action table K = 50 (KS1
+  // stays the row's label)
+  static constexpr int FC1 = ATAB ? (MZ_H + 3) / 4 : KS1;
   static constexpr int FC2 = 12;                // reward (2 tiles) + next hidden (4 tiles): 48 pieces
   static constexpr int P1 = (MZ_H + 1 + 3) / 4; // prediction fc1: K = 51 -> 13 steps
   static constexpr int P2 = 2 * (2 + JTP);      // value (2 tiles) + policy (JTP tiles)
@@ -184,6 +211,11 @@ __device__ __forceinline__ void mz_xpair_async(f32x2 &x, unsigned xbase) {
   asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x) : "v"(xbase), "n"(4 * ST), "n"(4 * ST + 4));
 }
 __device__ __forceinline__ void mz_lds_wait2(f32x2 &x) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x)); }
+// all but the N youngest LDS reads of the wave have arrived: the tile and the x pair named are among the older ones
+template <int N>
+__device__ __forceinline__ void mz_lds_wait_n(f32x4 &tile, f32x2 &x) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(tile), "+v"(x) : "n"(N));
+}
 
 // combine the four waves' split-K partial tiles (+ bias) into fin[n][m].  Partials are exchanged as one
 // 16-byte vector per lane and tile (ds_write_b128 / ds_read_b128): 6 + 4 LDS instructions per lane instead of
@@ -501,7 +533,7 @@ __host__ __device__ constexpr int mz_fused_lds_floats(int lt) { return MZ_FUSED_
     tlast = now_;                                                              \
   }
 
-// dynamic LDS of the fused kernel: pb_c table, then the 16 trees' node arrays (lt = 1: everything + Q cache, rows of the
+// dynamic LDS of the fused kernel (behind the action table of the rows that have one, mz_fused_atab_lds): pb_c table, then the 16 trees' node arrays (lt = 1: everything + Q cache, rows of the
 // table 64 apart; lt = 2: N, E, P, to_play per node, W, R, X per expansion slot, rows sims + 2 apart; lt = 0: table only)
 __host__ __device__ inline size_t mz_fused_dyn_lds(int sims, int NN, int lt) {
   size_t b = (size_t)(sims + 2) * (lt == 2 ? sims + 2 : 64) * 8;
@@ -641,7 +673,9 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
   constexpr int GK = mz_game_kind(GAME, SP, G);    // the environment of a GAME launch
   static_assert(GK != 1 || G == 16, "TicTacToe: 9 actions");
   constexpr bool GK2P = GK == 1 || GK == 3;        // ... is a two-player board game: mover and legal moves come from the root
-  using SC = FusedSched<KS1, JTP>;
+  constexpr bool ATAB = mz_fused_atab(KS1, JTP, G);      // the action columns come out of a table (above)
+  constexpr bool ATAB_LDS = ATAB && LT != 2;             // ... that lives in LDS; beside compact trees in global memory
+  using SC = FusedSched<KS1, JTP, ATAB>;
   constexpr int NB = MZ_NB, NSTEPS = SC::NSTEPS, RS = SC::RS, NRING = SC::NRING;
   static_assert(RS <= SC::FC1, "resident steps must be fc1 steps of the dynamics stage");
   constexpr int E_FC1 = SC::FC1, E_FC2 = E_FC1 + SC::FC2, E_P1 = E_FC2 + SC::P1, E_P2 = E_P1 + SC::P2;
@@ -650,7 +684,9 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
 
   __shared__ __attribute__((aligned(16))) float smem[mz_fused_lds_floats(LT)];
   extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
-  double *s_pbc = (double *)dyn_lds;       // pb_c(Np, Nc) table (host-computed, exact), rows PBS entries apart
+  // (the action table, where it lives in LDS, comes first: its address is then a constant + the lane's own offset)
+  const int atab_bytes = (int)mz_fused_atab_lds(ATAB, n.A, LT);
+  double *s_pbc = (double *)(dyn_lds + atab_bytes);       // pb_c(Np, Nc) table (host-computed, exact), rows PBS entries apart
   const int PBS = (LT == 2) ? t.sims + 2 : 64;
   // (LT = 1, 2) the workgroup's 16 trees live in LDS for the whole launch (LT = 2: the descent's fields only)
   double *l_P = s_pbc + (t.sims + 2) * PBS;
@@ -672,6 +708,8 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
   float *s_lnw = s_b4 + 64;
   float *s_lnb = s_lnw + 64;
   float *xEd = s_lnb + 64;                // [16][MZ_XE] dynamics extension: one-hot(action) (the bias rides in its weights)
+  // (ATAB: columns 0, 1 = the k = 50, 51 the 13th k-step reaches stay zero; word MZ_XACT of a row = the tree's action)
+  constexpr int MZ_XACT = 8;
   float *xEp = xEd + 16 * MZ_XE;          // [16][MZ_XE] prediction extension: 1 (bias column), then 0
   int *s_path = (int *)(xEp + 16 * MZ_XE); // [16][MZ_FUSED_MAXPL] pending search path of every tree
   double *s_rcp = (double *)(s_path + 16 * MZ_FUSED_MAXPL);      // [MZ_FUSED_MAXPL] 1 / n (mz_tree_backup_select_f)
@@ -692,6 +730,15 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
   if (tid0 < 64) { s_lnw[tid0] = n.lnw[tid0]; s_lnb[tid0] = n.lnb[tid0]; }
   if (tid0 < MZ_FUSED_MAXPL) s_rcp[tid0] = 1.0 / (double)(tid0 > 0 ? tid0 : 1);
   for (int i = tid0; i < 16 * MZ_XE; i += 256) xEp[i] = (i % MZ_XE == 0) ? 1.f : 0.f;
+  if constexpr (ATAB) {
+    for (int i = tid0; i < 16 * MZ_XE; i += 256) xEd[i] = 0.f;
+  }
+  if constexpr (ATAB_LDS) {      // every wave copies its own slice of the packed table (behind its weight stream)
+    const int w0 = tid0 >> 6, l0 = tid0 & 63;
+    const f32x4 *src = wstream + (size_t)w0 * (SC::NSTEPS * 256 + MZ_ATAB_WAVE_FLOATS / 4) + SC::NSTEPS * 256;
+    for (int a = 0; a < n.A; ++a)
+      *(f32x4 *)(dyn_lds + a * MZ_ATAB_LDS_STRIDE + w0 * 1024 + l0 * 16) = src[a * 64 + l0];
+  }
   for (int i = tid0; i < (t.sims + 2) * (t.sims + 2); i += 256) s_pbc[(i / (t.sims + 2)) * PBS + i % (t.sims + 2)] = t.pbctab[i];
 
   // tree-lane mapping: TL lanes per tree (16, or 32 when A > 16), 256/TL trees per pass
@@ -737,7 +784,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
     // 413.5 vs 410.5 us per move, A/B on one box)
     if (ra.nst0 >= 0)
     mz_root_body<JTP, G, true, GK>(n, t, nullptr, ra.istream, ra.nst0, sp, seed, ra.alpha, ra.frac,
-                               (float *)(dyn_lds + (((t.sims + 2) * PBS * 8 + 15) & ~15)), tid_r, s_stage,
+                               (float *)(dyn_lds + atab_bytes + (((t.sims + 2) * PBS * 8 + 15) & ~15)), tid_r, s_stage,
                                [&](int k) __attribute__((always_inline)) { HSTAMP(4 + k) }, ENVS ? s_env : nullptr);
     __syncthreads();
     HSTAMP(0)
@@ -786,9 +833,11 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
   // scalar offset + immediate -- no VALU address arithmetic in the MFMA stream (with flat/global addressing the
   // compiler kept base + lane offset as a 64-bit VGPR pair and spent two VALU adds per step on it; every
   // non-MFMA instruction in a dense MFMA stream costs issue time).
-  const char *wbase = (const char *)(wstream + (size_t)__builtin_amdgcn_readfirstlane(w) * NSTEPS * 256);
+  // (ATAB: the wave's slice of the action table follows its stream)
+  constexpr int WSTRIDE = NSTEPS * 256 + (ATAB ? MZ_ATAB_WAVE_FLOATS / 4 : 0);      // f32x4 per wave
+  const char *wbase = (const char *)(wstream + (size_t)__builtin_amdgcn_readfirstlane(w) * WSTRIDE);
   const __amdgpu_buffer_rsrc_t wrsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)wbase, 0, NSTEPS * 4096, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void *)wbase, 0, WSTRIDE * 16, 0x00020000);
   const int lane_off = lane * 16;
 #define MZ_BLOAD(byteoff) __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_off, (byteoff), 0))
   // the resident steps (per move in a HEAD launch: the root needs the register file for its own ring, and 208 KB from
@@ -915,7 +964,9 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(hv[i]));
       if (tl < MZ_HS / 4) *(f32x4 *)(xR + mt * MZ_HS + 4 * tl) = hv[i];
       // (only the columns the KS1 k-steps of the dynamics fc1 reach: k < 4 KS1)
-      for (int c = tl; c < 4 * KS1 - MZ_H; c += TL) xEd[mt * MZ_XE + c] = (c == my_act[i] || (G == 4 && c == n.A)) ? 1.f : 0.f;
+      // ATAB: the tree publishes its action instead; every lane of the workgroup picks up its column's below
+      if constexpr (ATAB) { if (tl == 0) ((int *)xEd)[mt * MZ_XE + MZ_XACT] = my_act[i]; }
+      else for (int c = tl; c < 4 * KS1 - MZ_H; c += TL) xEd[mt * MZ_XE + c] = (c == my_act[i] || (G == 4 && c == n.A)) ? 1.f : 0.f;
       // (column A, where it exists, meets zero weights: the bias rides in the one-hot columns, fill_fc1_foldbias.  The
       // 4-action instantiations still write it as 1: without the second compare their simulation loop came out 13
       // instructions longer and 0.8 % slower on the LunarLander shapes, with it the 8-lane instantiation is 1 % slower
@@ -965,6 +1016,41 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
         constexpr int st = dyn ? s : s - E_FC2;
         constexpr int NST = dyn ? SC::FC1 : SC::P1;
         float x;
+        if constexpr (ATAB && dyn && st == 0) {
+          static_assert(!ATAB || RS >= 1, "the action-table step is a resident one");
+          // the action term first: the x pair, then the lane's 16 table vectors straight into the accumulator tiles (dead
+          // since the previous simulation's prediction).  At most 15 LDS reads are in flight (lgkmcnt is a 4-bit counter);
+          // MFMA t below waits for the x pair and tiles 0..t only, the last two reads follow the first two MFMAs.
+          const int act = ((const int *)xEd)[m16 * MZ_XE + MZ_XACT];
+          mz_xpair_async<0>(xpair[0], xbase);
+          if constexpr (ATAB_LDS) {
+            const unsigned toff = mz_lds_addr(dyn_lds) + (unsigned)(act * MZ_ATAB_LDS_STRIDE + w * 1024 + g4 * 16);
+            mz_static_for<14>([&](auto T_) __attribute__((always_inline)) {
+              mz_lds128<decltype(T_)::value * 64>(acc[decltype(T_)::value], toff);
+            });
+            mz_static_for<16>([&](auto T_) __attribute__((always_inline)) {
+              constexpr int tt = decltype(T_)::value;
+              if constexpr (tt == 0) mz_lds_wait_n<13>(acc[0], xpair[0]);
+              else mz_lds_wait_n<(tt < 2 ? 13 : 15 - tt)>(acc[tt], xpair[0]);
+              mz_mfma_va(acc[tt], Rw[s][tt / 4][tt % 4], xpair[0][0]);
+              if constexpr (tt < 2) mz_lds128<(14 + tt) * 64>(acc[14 + tt], toff);
+            });
+          } else {
+            // compact trees: the same 16 vectors, in the same order, from the packed table behind the wave's stream (the
+            // L2 latency is exposed once per simulation; the gather has drained every older load)
+            const int goff = act * 1024 + g4 * 16;
+            mz_static_for<16>([&](auto T_) __attribute__((always_inline)) {
+              constexpr int tt = decltype(T_)::value;
+              acc[tt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, goff, NSTEPS * 4096 + tt * 64, 0));
+            });
+            mz_lds_wait2(xpair[0]);
+            mz_static_for<16>([&](auto T_) __attribute__((always_inline)) {
+              constexpr int tt = decltype(T_)::value;
+              mz_mfma_va(acc[tt], Rw[s][tt / 4][tt % 4], xpair[0][0]);
+            });
+          }
+          mz_xpair_async<2>(xpair[1], xbase);
+        } else {
         if constexpr (st < 12) {        // k-steps 0..11 lie inside the 50 hidden columns: fetched in pairs
           f32x2 &cur = xpair[(st / 2) % 2];
           if constexpr (st % 2 == 0) {
@@ -1011,6 +1097,7 @@ __global__ __launch_bounds__(256, 1) void k_search_fused(NetView n, TreeView t, 
             __builtin_amdgcn_sched_barrier(0);
           }
         }
+        }      // (not the action-table step)
         if constexpr (s == E_FC1 - 1 || s == E_P1 - 1) {
           // (ascending tile order = the order of the stage's last 16 MFMAs: 30 instructions lie between the last MFMA and
           // the read of its tile, more than the 17 wait states its result needs -- no fence in front)

@@ -9,6 +9,8 @@
 // ---- shapes, one row each; an engine runs the first row whose largest action count is >= its own.
 // k_search_fused: X(largest action count, fc1 k-steps KS1, policy tiles JTP, lanes per child group G)
 // (dynamics fc1: K = 50 + A columns in k-steps of 4 -- the bias rides in the one-hot columns, fill_fc1_foldbias)
+// (the A <= 4 row: its one-hot columns + bias come out of an action table instead, mz_fused_atab in mz_fused.hip.h -- the
+// kernel then runs 13 k-steps; KS1 = 14 stays the row's label, the schedule derives its own step count from it)
 // k_search_h2:    X(largest action count, lanes per child group G)
 // _DEV: the two bench shapes, all that -DMZ_DEV_ONLY compiles (kernel development: a quarter of the build time)
 #define MZ_FUSED_ROWS_DEV(X) X(4, 14, 1, 4) X(6, 14, 1, 8)
@@ -36,7 +38,8 @@
 // (mz_game_kind, mz_fused.hip.h).  TicTacToe:
 #define MZ_GAME_VARIANT(V) V((MZ_GAME_SHAPE), 2, false, false, true, true)
 // the single-player game kernel (CartPole): whole trees in LDS, the placement of 2 actions at every simulation count the
-// fused kernels take (16 trees of 1 + 63 * 2 nodes fit beside the root's working set)
+// fused kernels take (16 trees of 1 + 63 * 2 nodes and the 8,320-byte action table fit beside the static LDS: 108,208 of
+// 110,080 bytes at 62 simulations)
 #define MZ_CART_VARIANT(V) V((MZ_CART_SHAPE), 1, false, true, true, true)
 // Connect Four, trees of NN = 1 + (sims + 1) * 7 nodes beside 53,760 bytes of static LDS (mz_fused_dyn_lds): whole trees in
 // LDS (LT 1) up to 24 simulations (106,304 bytes of dynamic LDS; 25: 110,512 > 110,080), the compact placement (LT 2) from 25
