@@ -280,6 +280,24 @@ int mz_eval_env_results(mz_engine *e, int32_t *step, int32_t *n_moves, double *a
                         double *child_visits, int32_t *n_actions, int32_t *depths, void *stream);
 int mz_eval_env_log_capacity(const mz_engine *e);
 
+/* The playout-search (UCT) opponent: a classical Monte-Carlo tree search on the true rules of TicTacToe (kind 1) and Connect
+ * Four (kind 3) -- random playouts, no network, planned on the device by one wave per game (DESIGN s7d;
+ * csrc/mz_playout.hip.h).  playouts: the budget per move, a multiple of 64 in 64 .. 65536.
+ *
+ * mz_playout_plan: one move for each of n_games <= num_envs given positions; game i has the seed env_id_offset + i and its
+ * plan depends on (engine seed, that seed, move, its position, playouts) only.  [host] boards [n_games][42] int8 (cell
+ * 7 * row + col; TicTacToe uses the first 9 cells of a row and the rest must be 0), turn [n_games] int8 (+1 / -1, the
+ * mover), step [n_games] int32 (plies played: the number of stones).  Every position must be one of the game's with a
+ * legal action.  Out, [host]: action_out [n_games] int32, visits_out / wins_out [n_games][A] int32 (either may be NULL):
+ * the root's playouts per action and 2 * wins + draws of the mover.  Does not need weights.  Synchronises once.
+ *
+ * mz_eval_env_set_opponent (after mz_eval_env_reset with a random_opp seat, before the first move): the moves of that seat
+ * are planned with `playouts` playouts each, keyed by the move (0: the uniformly random mover, the state after a reset).
+ * mz_eval_env_moves then takes max_actions == 1 only. */
+int mz_playout_plan(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, int n_games,
+                    int playouts, uint64_t move, int32_t *action_out, int32_t *visits_out, int32_t *wins_out, void *stream);
+int mz_eval_env_set_opponent(mz_engine *e, int playouts, void *stream);
+
 /* A match between two networks on the device games: B games in lock-step, every ply searched by the mover's own network.
  * Replaces the per-ply host loop a match driven from Python would need (two Evaluator._play_batch loops interleaved by
  * hand: per ply one engine call sequence and one host environment step); the host touches no game between plies.

@@ -125,6 +125,14 @@ int mz_selfplay_set_env_state(mz_engine *e, int env, const double *state);
 int mz_selfplay_board_state(mz_engine *e, int8_t *out);
 int mz_selfplay_set_board_state(mz_engine *e, int env, const int8_t *cells42, int turn);
 
+/* test hook: mz_playout_plan's planning with the 64 lanes looped on the HOST -- the same __host__ __device__ bodies of
+ * csrc/mz_playout.hip.h (pick, playout, per-action results, backup), only the reduction over the lanes differs.  Takes no engine
+ * and touches no device: A is the game's action count (9 / 7), seed and env_id_offset what the engine's config would hold.
+ * Arguments and outputs as mz_playout_plan's; the two agree bit for bit. */
+int mz_playout_plan_host(int kind, int A, uint64_t seed, int env_id_offset, const int8_t *boards, const int8_t *turn,
+                         const int32_t *step, int n_games, int playouts, uint64_t move, int32_t *action_out,
+                         int32_t *visits_out, int32_t *wins_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ int mz_eval_env_reset(mz_engine *e, int kind, int max_steps, int time_limit, int
   es.two_players = e->cfg.two_players != 0; es.cap = cap; es.sims = e->sims;
   es.d_walk = nullptr; es.d_noise = nullptr; es.d_opp = nullptr;
   es.d_walk_moves = es.d_walk_m = es.d_noise_moves = es.d_opp_n = 0;
+  es.opp_playouts = 0; es.opp_action = nullptr;      // the random mover, until mz_eval_env_set_opponent says otherwise
   HIPCHECK(hipMemsetAsync(es.board, 0, nb * 42, s));
   HIPCHECK(hipMemsetAsync(es.turn, 1, nb, s));
   HIPCHECK(hipMemsetAsync(es.step, 0, nb * 4, s));
@@ -96,6 +97,8 @@ int mz_eval_env_moves(mz_engine *e, int n, int mode, int max_actions, double tem
   if (M < 1) return fail("mz_eval_env_moves: max_actions must be >= 1");
   if (es.kind == 3 && M != 1)
     return fail("mz_eval_env_moves: Connect Four takes one action per move (below the root the walk offers full columns)");
+  if (es.opp_playouts > 0 && M != 1)
+    return fail("mz_eval_env_moves: the playout opponent takes one action per move (max_actions 1), got %d", M);
   if (es.d_walk && mode == 0 && es.d_walk_m != M)
     return fail("mz_eval_env_moves: the given walk uniforms are [B][moves][%d], the walk takes %d actions", es.d_walk_m, M);
   hipStream_t s = (hipStream_t)stream;
@@ -130,6 +133,9 @@ int mz_eval_env_moves(mz_engine *e, int n, int mode, int max_actions, double tem
     } else {
       if (mz_eval_lookahead(e, mode, es.actions, es.pred_rewards, es.child_visits, nullptr, nullptr, s)) return -1;
     }
+    if (es.opp_playouts > 0 &&      // the opponent's move in the live games that are its to move, keyed by this move
+        playout_launch(e, "mz_eval_env_moves", es.kind, es.board, es.turn, es.step, es.terminal, es.random_opp, B,
+                       es.opp_playouts, (uint64_t)move, es.opp_action, nullptr, nullptr, s)) return -1;
     hipLaunchKernelGGL(k_eval_apply, grid, block, 0, s, es, (const float *)e->tv.root_value, B, A, M, mode, move,
                        (uint64_t)e->cfg.seed, e->cfg.env_id_offset);
     HIPCHECK(hipGetLastError());

@@ -54,6 +54,11 @@ struct EvalState {
   const double *d_noise; int d_noise_moves;               // [B][moves][A]
   const int32_t *d_opp; int d_opp_n;                      // [B][n] indices into the root position's legal actions
   int32_t *opp_pos;      // [B] how many of them the game has consumed
+  // the playout-search opponent (mz_eval_env_set_opponent; mz_playout.hip.h): its budget per move (0: the random mover) and
+  // the move it planned for the games whose mover is random_opp (null with the random mover)
+  int opp_playouts;
+  int32_t *opp_action;   // [B]
+  int32_t *opp_action_buf;      // (the allocation opp_action points to while the opponent is set)
   // per-move logs (null unless asked for): per applied action [B][cap], per move [B][cap]
   int32_t *log_action; double *log_reward; int8_t *log_mover; float *log_pred_reward;
   float *log_pred_value; double *log_root_value; double *log_child_visits; int32_t *log_n_actions; int32_t *log_depths;
@@ -141,7 +146,10 @@ static __global__ void k_eval_apply(EvalState es, const float *net_value, int B,
     const bool opp = es.two_players && mover == es.random_opp;
     if (opp && nlegal > 0) {
       int idx;
-      if (es.d_opp) {
+      if (es.opp_action) {      // the playout opponent's plan for this position (M == 1: the root position is the game's)
+        idx = 0;
+        for (int a = 0, want = es.opp_action[b]; a < want && a < A; ++a) idx += legal[a] ? 1 : 0;
+      } else if (es.d_opp) {
         const int pos = es.opp_pos[b];
         idx = pos < es.d_opp_n ? es.d_opp[(size_t)b * es.d_opp_n + pos] : 0;
         es.opp_pos[b] = pos + 1;

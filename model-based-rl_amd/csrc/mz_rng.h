@@ -15,6 +15,7 @@
 #define MZ_RNG_ENV 6u        // start state of a device environment's episode (mz_cartpole_reset_state): counter (env, episode, 0)
 #define MZ_RNG_OPP 7u        // the random opponent of a device evaluation game (k_eval_apply): counter (env = the game's seed, move, step)
 #define MZ_RNG_OPEN 8u       // opening ply of a match (mz_match_open_game): counter (env = the game's seed, ply, 0)
+#define MZ_RNG_PLAYOUT 9u    // random plies of the playout opponent (mz_playout.hip.h): counter (env = the game's seed, move, iteration), lane and call in the purpose word
 
 struct mz_u4 { uint32_t x, y, z, w; };
 

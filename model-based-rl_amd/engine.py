@@ -462,6 +462,29 @@ class Engine(object):
       out[k] = acc[i]
     return out
 
+  # ---- the playout-search (UCT) opponent (mz_playout_plan, mz_eval_env_set_opponent, include/mz_engine.h)
+  def eval_env_set_opponent(self, playouts):
+    """mz_eval_env_set_opponent (after eval_env_reset with a random_opp seat, before the first move): that seat's moves are
+    planned by a playout search of `playouts` playouts per move on the true rules; 0: the uniformly random mover"""
+    _abi.check(self.lib.mz_eval_env_set_opponent(self._h, int(playouts), self.stream), 'mz_eval_env_set_opponent')
+
+  def playout_plan(self, kind, boards, turn, step, playouts, move=0):
+    """mz_playout_plan: one playout-search move for each of n <= B positions of `kind` (an EVAL_ENVS name or 1 / 3): boards
+    [n, 42] (TicTacToe: the first 9 cells of a row), turn [n] +1 / -1, step [n] plies played; position i is the game with
+    the seed env_id_offset + i.  Returns numpy arrays: action [n], visits [n, A], wins [n, A] (2 * wins + draws of the
+    mover), all int32."""
+    k = self.EVAL_ENVS[kind] if isinstance(kind, str) else int(kind)
+    bd = np.ascontiguousarray(boards, np.int8)
+    tn, st = np.ascontiguousarray(turn, np.int8), np.ascontiguousarray(step, np.int32)
+    n = bd.shape[0]
+    if bd.shape != (n, 42) or tn.shape != (n,) or st.shape != (n,):
+      raise ValueError('playout_plan: boards [n, 42], turn [n], step [n]; got %s, %s, %s' % (bd.shape, tn.shape, st.shape))
+    action, visits, wins = np.zeros(n, np.int32), np.zeros((n, self.A), np.int32), np.zeros((n, self.A), np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _abi.check(self.lib.mz_playout_plan(self._h, k, p(bd), p(tn), p(st), n, int(playouts), int(move), p(action), p(visits),
+                                        p(wins), self.stream), 'mz_playout_plan')
+    return action, visits, wins
+
   # ---- Reanalyse of stored replay rows (mz_reanalyse, include/mz_engine.h)
   def reanalyse(self, rows, fresh, n_rows, kind, num_simulations=None):
     """mz_reanalyse: rows [>= n_rows, O + A + REC_EXTRA] and fresh [>= n_rows, A + 2], both PINNED float32 host tensors; the

@@ -71,6 +71,32 @@ def refuse_device_env(args_or_config):
                               'columns, which the host class refuses and a device game cannot.')
 
 
+PLAYOUT_ENVS = ('TicTacToe', 'ConnectFour')
+
+
+def refuse_opp_playouts(args_or_config, match=False):
+  """one sentence per configuration --opp_playouts (the playout-search opponent of the device games) leaves out
+  (NotImplementedError); nothing to refuse at 0"""
+  c = args_or_config
+  n = int(getattr(c, 'opp_playouts', 0) or 0)
+  if n == 0:
+    return
+  if match:
+    raise NotImplementedError('--opp_playouts: --match plays two networks against each other and seats no playout opponent.')
+  if n < 64 or n > 65536 or n % 64:
+    raise NotImplementedError('--opp_playouts: the budget is a multiple of 64 in 64 to 65536 playouts per move, got %d.' % n)
+  if not getattr(c, 'device_env', False):
+    raise NotImplementedError('--opp_playouts: the playout opponent is planned on the device and needs --device_env.')
+  if getattr(c, 'random_opp', None) is None:
+    raise NotImplementedError('--opp_playouts: --random_opp names the seat the playout opponent takes and is missing.')
+  env = getattr(c, 'environment', None)
+  if env is not None and env not in PLAYOUT_ENVS:
+    raise NotImplementedError('--opp_playouts: %s has no playout opponent; it plays %s.' % (env, ' and '.join(PLAYOUT_ENVS)))
+  m = getattr(c, 'apply_mcts_actions', 1)
+  if any(int(x) != 1 for x in (m if isinstance(m, (list, tuple)) else [m])):
+    raise NotImplementedError('--opp_playouts: the playout opponent answers every move and takes --apply_mcts_actions 1 only.')
+
+
 class DeviceGame(object):
   """A finished game of the device-environment path: what the summary and the CLI read, from the device's accumulators.
   With keep_history also the per-move lists under the host path's names (history.actions / rewards / to_play / dones /
@@ -132,6 +158,7 @@ class Evaluator(SummaryTools):
                                 % self.config.architecture)
     refuse_unsupported(self.config)
     refuse_device_env(self.config)
+    refuse_opp_playouts(_with(self.config, device_env=True))      # (play_games(device_env=True) may still name the device path)
     if not torch.cuda.is_available():
       raise RuntimeError('the evaluator needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
     self.device = torch.device(device if device is not None else 'cuda')
@@ -162,9 +189,10 @@ class Evaluator(SummaryTools):
     device_env (or config.device_env): the games live on the device environments and come back as DeviceGame records, with
     keep_history (or config.keep_history) carrying the per-move lists; start_states [num_games][4]: CartPole's start states
     instead of the counter RNG's (device path only)."""
-    assert self.weights is not None, '.load_network() needs to be called before playing.'
     device_env = bool(device_env or getattr(self.config, 'device_env', False))
     keep_history = bool(keep_history or getattr(self.config, 'keep_history', False))
+    refuse_opp_playouts(_with(self.config, device_env=device_env))
+    assert self.weights is not None, '.load_network() needs to be called before playing.'
     if device_env and environments is not None:
       raise ValueError('play_games: a device-environment run builds no host environment')
     if start_states is not None and not device_env:
@@ -192,6 +220,8 @@ class Evaluator(SummaryTools):
     only reads the number of games still live after each chunk"""
     cfg = self.config
     refuse_device_env(_with(cfg, device_env=True))
+    refuse_opp_playouts(_with(cfg, device_env=True))
+    opp_playouts = int(getattr(cfg, 'opp_playouts', 0) or 0)
     B, A = len(seeds), int(cfg.action_space)
     only_prior, only_value = bool(getattr(cfg, 'only_prior', 0)), bool(getattr(cfg, 'only_value', 0))
     mode = 1 if only_prior else 2 if only_value else 0
@@ -207,6 +237,8 @@ class Evaluator(SummaryTools):
     eng.set_weights(self.weights)
     eng.eval_env_reset(cfg.environment, int(cfg.max_steps), CARTPOLE_TIME_LIMITS.get(cfg.environment, 0),
                        getattr(cfg, 'random_opp', None) if two else None, keep_history)
+    if opp_playouts:
+      eng.eval_env_set_opponent(opp_playouts)
     if draws is not None or start_states is not None:
       eng.eval_env_set_draws(**_pack_draws(draws, B, A, M, mode, noise_on, start_states))
     live, moves, t_dev = B, 0, 0.0
@@ -457,6 +489,7 @@ def state_generator(args):
                     c.batch = args.batch
                     c.device_env = args.device_env
                     c.keep_history = args.keep_history
+                    c.opp_playouts = args.opp_playouts
                     yield state
 
 
@@ -468,6 +501,7 @@ def run(evaluator, seed=None):
 
 def main(argv=None):
   args = get_evaluation_args(argv)
+  refuse_opp_playouts(args, match=args.match)
   if args.match:      # checkpoint against checkpoint (match.py); implies the device path
     from . import match
     return match.main(args)
@@ -489,8 +523,10 @@ def main(argv=None):
     if evaluator.config.two_players and args.random_opp is not None:
       returns = np.array([game_return(g) for g in games])
       s['wins'], s['draws'], s['losses'] = int((returns > 0).sum()), int((returns == 0).sum()), int((returns < 0).sum())
-      print("Against a random opponent (the agent moves {}): wins {} draws {} losses {}\n".format(
-          'second' if args.random_opp == 1 else 'first', s['wins'], s['draws'], s['losses']))
+      s['opp_playouts'] = int(args.opp_playouts)
+      opponent = '{}-playout search'.format(args.opp_playouts) if args.opp_playouts else 'a random opponent'
+      print("Against {} (the agent moves {}): wins {} draws {} losses {}\n".format(
+          opponent, 'second' if args.random_opp == 1 else 'first', s['wins'], s['draws'], s['losses']))
     s['games_per_s'] = len(games) / wall
     s['host_share'] = evaluator.host_seconds / wall
     results.append(s)

@@ -6,6 +6,7 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
 
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
+                                       [--opp_playouts 1024]
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --no_support adds the flag (scalar value / reward heads, MSE or Huber loss) to the recipe, for training and for the matches."""
@@ -53,15 +54,16 @@ def play_vs_random(weights, agent_side, games=512, sims=30, seed=0, no_support=F
   return int((result == 1).sum()), int((result == 0).sum()), int((result == -1).sum())
 
 
-def play_vs_random_device(config, weights, agent_side, games=512, seed=0):
+def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_playouts=0):
   """the same match through the evaluator's device-environment path (any environment with a device form); `weights` a
-  state_dict.  Returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second."""
+  state_dict.  Returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second.  opp_playouts > 0: the
+  opponent is the playout search of that budget (evaluate --opp_playouts) instead of the random mover."""
   import copy
   from model_based_rl_amd.evaluate import Evaluator, game_return
   cfg = copy.copy(config)
   for k, v in dict(temperature=0, only_prior=0, only_value=0, use_exploration_noise=0, apply_mcts_actions=1,
                    random_opp=-agent_side, human_opp=None, render=False, save_mcts=False, save_gif_as='', label='vs random',
-                   verbose=False, batch=games, device_env=True, keep_history=False).items():
+                   verbose=False, batch=games, device_env=True, keep_history=False, opp_playouts=int(opp_playouts)).items():
     setattr(cfg, k, v)
   ev = Evaluator({'config': cfg, 'weights': weights, 'training_step': 0})
   ev.load_network()
@@ -81,6 +83,8 @@ def main():
   ap.add_argument('--reanalyse_every', type=int, default=None, help='train --reanalyse_every')
   ap.add_argument('--keep_checkpoint', default=None, help='copy the run\'s last checkpoint to this file')
   ap.add_argument('--match_against', default=None, help='a checkpoint kept by another run: the last checkpoint also plays it, from both seats')
+  ap.add_argument('--opp_playouts', type=int, default=0,
+                  help='also play the 512 games per side against a playout search of this many playouts per move (evaluate --opp_playouts)')
   a = ap.parse_args()
   from model_based_rl_amd import train
   from model_based_rl_amd.config import make_config
@@ -111,6 +115,9 @@ def main():
   kept = sorted(glob.glob(os.path.join(saves, '**', 'saves', '*'), recursive=True), key=os.path.getmtime)
   state = torch.load(kept[-1], map_location='cpu', weights_only=False)
   after = {side: match(state['weights'], side) for side in (1, -1)}
+  if a.opp_playouts:      # an absolute line: the same games against a search whose strength ignores the weights
+    vs_playouts = {name: {side: play_vs_random_device(make_config(base), sd, side, opp_playouts=a.opp_playouts) for side in (1, -1)}
+                   for name, sd in (('untrained', untrained_sd), ('trained', state['weights']))}
   # the last checkpoint against the first kept one, from both seats (match.play_match); where the run kept a single
   # checkpoint, against the untrained network
   from model_based_rl_amd.match import play_match
@@ -134,6 +141,9 @@ def main():
                                  'trained': {'agent_first (win, draw, loss)': after[1], 'agent_second': after[-1]}},
          'match_last_vs_first': dict(vs_first, a='checkpoint %d' % int(state['training_step']), b=opponent, seeds=256,
                                      opening_plies=2)}
+  if a.opp_playouts:
+    out['vs_%d_playout_search_512_games' % a.opp_playouts] = {
+        name: {'agent_first (win, draw, loss)': r[1], 'agent_second': r[-1]} for name, r in vs_playouts.items()}
   if a.keep_checkpoint:
     torch.save({'weights': state['weights'], 'training_step': int(state['training_step'])}, a.keep_checkpoint)
   if a.match_against:
