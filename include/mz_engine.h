@@ -511,6 +511,16 @@ int mz_fcl_set_optimizer(mz_fcl *c, int kind, double momentum, double alpha);
  *   categorical one with one bin.  The kind holds for every later mz_fcl_step, mz_fcl_update and mz_fcl_run.  Refuses a null handle,
  *   an unknown kind and kinds 1 / 2 on a handle with wider supports (mz_last_error). */
 int mz_fcl_set_scalar_loss(mz_fcl *c, int kind);
+/* mz_fcl_set_symmetry: board-symmetry augmentation of every later update's batch (DESIGN s7e).  kind as mz_game_kind: 0 = off (the
+ *   default), 1 = TicTacToe (8 images: g = 4 f + q, q quarter turns (r, c) -> (c, 2 - r), then the mirror (r, c) -> (r, 2 - c) if f),
+ *   3 = Connect Four (2 images: g = 1 maps col -> 6 - col).  Sample b of the handle's update number u is replaced by its image
+ *   under g = philox(seed, u, b).x & (n - 1): the observation's cells, the K unrolled actions (padded ones included, dtype kept) and
+ *   the K + 1 policy targets move together, everything else is left alone.  One extra launch ahead of the step on its stream, into a
+ *   device buffer of the handle; the caller's arrays are not written.  u starts at first_update (a resumed run passes its training
+ *   step) and advances by one with every mz_fcl_step without no_update, mz_fcl_update and update of mz_fcl_run; a step with
+ *   no_update set is neither transformed nor counted.  Refuses an unknown kind and a handle whose obs_dim / action_space are not the
+ *   game's (9 / 9, 42 / 7) (mz_last_error); with a kind set, mz_fcl_run refuses MZ_FCL_RUN_GRAPH=1. */
+int mz_fcl_set_symmetry(mz_fcl *c, int kind, uint64_t seed, uint32_t first_update);
 int mz_fcl_step(mz_fcl *c, const float *obs, const void *actions, int actions_are_i32, const float *target_rewards, const float *target_values,
                 const float *target_policies, const void *is_weights, int weights_are_f64, double beta1, double beta2, double eps,
                 double weight_decay, double clip_grad, int adamw, int no_update, float *new_errors, double *loss_sums, void *stream);

@@ -133,6 +133,19 @@ int mz_playout_plan_host(int kind, int A, uint64_t seed, int env_id_offset, cons
                          const int32_t *step, int n_games, int playouts, uint64_t move, int32_t *action_out,
                          int32_t *visits_out, int32_t *wins_out);
 
+/* test hooks of mz_fcl_set_symmetry.  mz_fcl_symmetry_apply: the symmetry kernel alone, with the handle's kind and seed and the
+ * given update number, on device-visible arrays of the handle's batch (obs [batch][obs_dim], actions [batch][K] int32 / int64,
+ * target_policies [batch][K + 1][A]; device memory, or mapped pinned host memory as mz_fcl_run's staging is -- the hook looks its
+ * device address up) into [dev] obs_out / actions_out / policies_out of the same shapes (not the sources themselves) and
+ * elements_out [batch] (may be NULL): the element drawn for every sample; enqueued on `stream`, the handle's counter stays.
+ * mz_fcl_symmetry_host: the same __host__ __device__ bodies of csrc/mz_symmetry.hip.h looped on the HOST over host arrays: no
+ * handle, no device.  The two agree bit for bit. */
+int mz_fcl_symmetry_apply(mz_fcl *c, const float *obs, const void *actions, int actions_are_i32, const float *target_policies,
+                          uint32_t update, float *obs_out, void *actions_out, float *policies_out, int32_t *elements_out, void *stream);
+int mz_fcl_symmetry_host(int kind, uint64_t seed, uint32_t update, int batch, int K, const float *obs, const void *actions,
+                         int actions_are_i32, const float *target_policies, float *obs_out, void *actions_out, float *policies_out,
+                         int32_t *elements_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ def build_parser():
          'root_value rewritten in place (reanalyse.py); 0: off')
   a('--reanalyse_every', type=int, default=None,
     help='learner steps between Reanalyse passes (default: --weight_sync_frequency); a pass follows the first weight pull past each multiple')
+  a('--symmetry', action='store_true',
+    help='TicTacToe / ConnectFour: train every sample of a batch on one of the equivalent images of its position (8 rotations and '
+         'mirrors / the left-right mirror), drawn per (seed, update, sample); observation, unrolled actions and policy targets move '
+         'together (symmetry.py; on the native learner step one HIP launch, mz_fcl_set_symmetry)')
   a('--parity_rng', action='store_true',
     help="draw Dirichlet noise / action samples from numpy's global stream in the reference's order")
   return p

@@ -35,6 +35,7 @@
 #include "mz_match.hip.h"
 #include "mz_reanalyse.hip.h"
 #include "mz_playout.hip.h"
+#include "mz_symmetry.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"

@@ -56,6 +56,12 @@ struct mz_fcl {
   double run_stats[6] = {0, 0, 0, 0, 0, 0};      // host seconds in: waiting for a slot, refresh, sampling, launching, the whole call; updates
   hipStream_t run_cap = nullptr;
   size_t soff_lr = 0;
+  // mz_fcl_set_symmetry: the game kind (0: off), the draw's seed, the counter of the handle's updates (the draw's `update`) and the
+  // device buffer the images of a batch's observations, actions and policies are written into (sections at soff[0], soff[1], soff[4])
+  int sym_kind = 0;
+  uint64_t sym_seed = 0;
+  uint32_t sym_update = 0;
+  char *sym_d = nullptr;
   std::vector<void *> allocs;
 };
 
@@ -410,6 +416,70 @@ int mz_fcl_set_scalar_loss(mz_fcl *c, int kind) {
   return 0;
 }
 
+int mz_fcl_set_symmetry(mz_fcl *c, int kind, uint64_t seed, uint32_t first_update) {
+  if (!c) return fail("mz_fcl_set_symmetry: null argument");
+  if (kind != 0 && sym_elements(kind) == 0) return fail("mz_fcl_set_symmetry: unknown kind %d (0 off, 1 TicTacToe, 3 Connect Four)", kind);
+  if (kind != 0 && (c->O != sym_cells(kind) || c->A != sym_actions(kind)))
+    return fail("mz_fcl_set_symmetry: %s has obs_dim %d and action_space %d, the handle was created with %d and %d",
+                kind == 1 ? "TicTacToe" : "Connect Four", sym_cells(kind), sym_actions(kind), c->O, c->A);
+  if (kind != 0 && !c->sym_d) {
+    // ONE buffer for every update of the handle, however many mz_fcl_run keeps in flight: an update's symmetry kernel and the step
+    // kernels that read its output are enqueued on the same stream, and so are the next update's, so the next image is written only
+    // after every reader of this one has finished (stream order); the staging slots exist because the HOST writes them ahead
+    FCL_ENTER(c);
+    if (fcl_alloc(c, &c->sym_d, c->soff[5])) return -1;
+  }
+  c->sym_kind = kind; c->sym_seed = seed; c->sym_update = first_update;
+  return 0;
+}
+
+// the symmetry kernel over one batch on `s`
+static int fcl_symmetry_launch(const SymBatch &b, hipStream_t s) {
+  const size_t total = sym_total(b);
+  hipLaunchKernelGGL(k_fcl_symmetry, dim3((unsigned)((total + MZ_SYM_THREADS - 1) / MZ_SYM_THREADS)), dim3(MZ_SYM_THREADS), 0, s, b);
+  if (hipGetLastError() != hipSuccess) return fail("mz_fcl: k_fcl_symmetry did not launch");
+  return 0;
+}
+
+// the address the device reads `p` at: mapped pinned host memory (hipHostMalloc, torch's pin_memory) by its device address, device
+// memory as it is
+static const void *fcl_device_address(const void *p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return p; }
+  return (at.type == hipMemoryTypeHost && at.devicePointer) ? (const void *)at.devicePointer : p;
+}
+
+// test hook (include/mz_engine_debug.h): the kernel alone on given device arrays, with the handle's kind and seed
+int mz_fcl_symmetry_apply(mz_fcl *c, const float *obs, const void *actions, int actions_are_i32, const float *target_policies,
+                          uint32_t update, float *obs_out, void *actions_out, float *policies_out, int32_t *elements_out, void *stream) {
+  if (!c || !obs || !actions || !target_policies || !obs_out || !actions_out || !policies_out)
+    return fail("mz_fcl_symmetry_apply: null argument");
+  if (!c->sym_kind) return fail("mz_fcl_symmetry_apply: the handle has no symmetry set (mz_fcl_set_symmetry)");
+  if ((const void *)obs == (const void *)obs_out || actions == (const void *)actions_out || (const void *)target_policies == (const void *)policies_out)
+    return fail("mz_fcl_symmetry_apply: the images cannot be written over their sources");
+  FCL_ENTER(c);
+  SymBatch b = {(const float *)fcl_device_address(obs), fcl_device_address(actions), (const float *)fcl_device_address(target_policies), obs_out,
+                actions_out, policies_out, elements_out, c->sym_seed, update, c->sym_kind, c->bs, c->K, actions_are_i32 ? 1 : 0};
+  return fcl_symmetry_launch(b, (hipStream_t)stream);
+}
+
+// test hook: the same bodies looped on the host; no handle, no device
+int mz_fcl_symmetry_host(int kind, uint64_t seed, uint32_t update, int batch, int K, const float *obs, const void *actions,
+                         int actions_are_i32, const float *target_policies, float *obs_out, void *actions_out, float *policies_out,
+                         int32_t *elements_out) {
+  if (sym_elements(kind) == 0) return fail("mz_fcl_symmetry_host: unknown kind %d (1 TicTacToe, 3 Connect Four)", kind);
+  if (batch < 0 || K < 1) return fail("mz_fcl_symmetry_host: batch %d and %d unroll steps", batch, K);
+  if (batch && (!obs || !actions || !target_policies || !obs_out || !actions_out || !policies_out))
+    return fail("mz_fcl_symmetry_host: null argument");
+  if (batch && ((const void *)obs == (const void *)obs_out || actions == (const void *)actions_out || (const void *)target_policies == (const void *)policies_out))
+    return fail("mz_fcl_symmetry_host: the images cannot be written over their sources");
+  SymBatch b = {obs, actions, target_policies, obs_out, actions_out, policies_out, elements_out, seed, update, kind, batch, K,
+                actions_are_i32 ? 1 : 0};
+  const size_t total = sym_total(b);
+  for (size_t t = 0; t < total; ++t) sym_element(b, t);
+  return 0;
+}
+
 int mz_fcl_repack(mz_fcl *c, void *stream) {
   if (!c || !c->P) return fail("mz_fcl_repack: no parameters bound");
   FCL_ENTER(c);
@@ -451,6 +521,15 @@ static int fcl_step_lr(mz_fcl *c, const float *obs, const void *actions, int act
   if (!c->P) return fail("mz_fcl_step: no parameters bound (mz_fcl_bind)");
   FCL_ENTER(c);
   hipStream_t s = (hipStream_t)stream;
+  if (c->sym_kind && !no_update) {
+    // the batch's images into sym_d, ahead of the step on its stream; the step reads them in the batch's place
+    char *d = c->sym_d;
+    SymBatch b = {obs, actions, target_policies, (float *)(d + c->soff[0]), (void *)(d + c->soff[1]), (float *)(d + c->soff[4]), nullptr,
+                  c->sym_seed, c->sym_update, c->sym_kind, c->bs, c->K, actions_are_i32 ? 1 : 0};
+    if (fcl_symmetry_launch(b, s)) return -1;
+    c->sym_update += 1u;
+    obs = b.obs_out; actions = b.act_out; target_policies = b.pol_out;
+  }
   FclView v = c->view;
   v.P = c->P; v.pk = c->pk;
   v.obs = obs; v.act = actions; v.act_i32 = actions_are_i32 ? 1 : 0; v.t_rew = target_rewards; v.t_val = target_values; v.t_pol = target_policies;
@@ -624,6 +703,7 @@ int mz_fcl_run(mz_fcl *c, const mz_fcl_source *src, int n_updates, const uint32_
   // without gaps inside a graph, but consecutive graph launches start ~15 us apart -- 105 us per update against 96.5 us for the
   // five direct launches (8.4 k against 9.0 k updates/s); profiles/r05_kernel_experiments.txt
   static const bool use_graph = getenv("MZ_FCL_RUN_GRAPH") && getenv("MZ_FCL_RUN_GRAPH")[0] == '1';
+  if (use_graph && c->sym_kind) return fail("mz_fcl_run: MZ_FCL_RUN_GRAPH=1 captures an update once and cannot carry the symmetry counter of mz_fcl_set_symmetry");
   const char *ev_env = getenv("MZ_FCL_RUN_EVENTS");      // (1: an event behind every update instead of the completion word; A/B and tests)
   const bool use_flag = !(ev_env && ev_env[0] == '1');
   // the captured update of each slot (rebuilt when a hyper-parameter or an address it holds changes)

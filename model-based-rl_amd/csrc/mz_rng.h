@@ -17,6 +17,8 @@
 #define MZ_RNG_OPEN 8u       // opening ply of a match (mz_match_open_game): counter (env = the game's seed, ply, 0)
 #define MZ_RNG_PLAYOUT 9u    // random plies of the playout opponent (mz_playout.hip.h): counter (env = the game's seed, move, iteration), lane and call in the purpose word
 
+#define MZ_RNG_SYM 10u       // the symmetry element of a training sample (mz_symmetry.hip.h): counter (update, sample, 0)
+
 struct mz_u4 { uint32_t x, y, z, w; };
 
 __host__ __device__ inline mz_u4 mz_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {

@@ -22,6 +22,7 @@ import torch
 from .actors import _call, set_all_seeds
 from .logger import Logger
 from .networks import get_network, support_to_scalar
+from .symmetry import apply_batch, kind_of, refuse_symmetry, seed_of
 
 
 def scalar_transform(x):
@@ -244,6 +245,10 @@ class _NativeFC(object):
     mom = float(g.get('momentum', 0.0) or 0.0) if self.kind != self.ADAM else 0.0
     _abi.check(self.lib.mz_fcl_set_optimizer(self.h, self.kind, mom, float(g.get('alpha', 0.0)) if self.kind == self.RMSPROP else 0.0),
                'mz_fcl_set_optimizer')
+    # --symmetry: the handle transforms every update's batch itself (one launch ahead of the step), counting updates from the
+    # learner's training step -- after a resume the resumed one
+    self.sym_kind = kind_of(cfg) if getattr(cfg, 'symmetry', False) else 0
+    self._symmetry()
     named = dict(net.named_parameters())
     self.params = [named[k] for k in WEIGHT_ORDER]
     n = sum(p.numel() for p in self.params)
@@ -299,6 +304,14 @@ class _NativeFC(object):
 
   def fits(self, host):
     return all(host[k].shape == self.shape[k] for k in _GraphedUpdate.ORDER)
+
+  def _symmetry(self):
+    """--symmetry: the handle's first update draws with update = the learner's training step, as Learner.update_weights does for
+    the PyTorch steps; from there the handle counts its updates itself (launch() and run() alike)"""
+    if self.sym_kind:
+      from . import _abi
+      _abi.check(self.lib.mz_fcl_set_symmetry(self.h, self.sym_kind, seed_of(self.learner.config), int(self.learner.training_step) & 0xFFFFFFFF),
+                 'mz_fcl_set_symmetry')
 
   def _hyper(self):
     """(beta1, beta2, eps, weight_decay, clip_grad, adamw) of the next step; SGD / RMSprop: their rate into the device float first"""
@@ -621,6 +634,7 @@ class _BatchSource(object):
 class Learner(Logger):
 
   def __init__(self, config, storage, replay_buffer, state=None):
+    refuse_symmetry(config)      # (--symmetry on a configuration it does not cover: refused before any device is touched)
     set_all_seeds(config.seed)
     self.config = deepcopy(config)
     self.run_tag, self.group_tag = getattr(config, 'run_tag', None) or 'run', getattr(config, 'group_tag', None)
@@ -928,6 +942,9 @@ class Learner(Logger):
       if self._native is None and (self._graph is None or not self._graph.fits(host)) and _NativeFC.eligible(self, host):
         self.flush_priorities()
         self._native = _NativeFC(self, host)
+    if self._native is None and getattr(self.config, 'symmetry', False):
+      # --symmetry on the PyTorch steps (graphed or eager): the images the native step would train on, made on the host before upload
+      host = apply_batch(host, kind_of(self.config), seed_of(self.config), self.training_step)[0]
     if self._native is not None or self.use_graph:
       if self._native is not None:
         # FCNetwork: the step's HIP launches from the host batch (mz_fcl_update), no PyTorch operator, no graph to capture

@@ -324,6 +324,8 @@ def main(argv=None):
     cfg.run_tag = os.environ.get('MZ_RUN_TAG') or time.strftime('%Y-%m-%d_%H-%M-%S')
   from .reanalyse import refuse_reanalyse
   refuse_reanalyse(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))      # (before any rank or device exists)
+  from .symmetry import refuse_symmetry
+  refuse_symmetry(cfg)                                                        # (--symmetry: likewise)
   if spawn:                         # `train --ranks N` without a launcher: pre-flight here (one sentence instead of N tracebacks), then the ranks
     _preflight_ranks(ranks, cfg)
     raise SystemExit(_spawn_ranks(ranks, argv))

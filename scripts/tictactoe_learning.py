@@ -6,9 +6,10 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
 
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
-                                       [--opp_playouts 1024]
+                                       [--opp_playouts 1024] [--symmetry]
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
+--symmetry adds train's flag (every sample trained on one of the equivalent images of its position, symmetry.py) to the training run.
 --no_support adds the flag (scalar value / reward heads, MSE or Huber loss) to the recipe, for training and for the matches."""
 import argparse, json, os, sys, time, types
 import numpy as np, torch
@@ -85,6 +86,7 @@ def main():
   ap.add_argument('--match_against', default=None, help='a checkpoint kept by another run: the last checkpoint also plays it, from both seats')
   ap.add_argument('--opp_playouts', type=int, default=0,
                   help='also play the 512 games per side against a playout search of this many playouts per move (evaluate --opp_playouts)')
+  ap.add_argument('--symmetry', action='store_true', help='train --symmetry: board-symmetry augmentation of the training batches')
   a = ap.parse_args()
   from model_based_rl_amd import train
   from model_based_rl_amd.config import make_config
@@ -97,6 +99,8 @@ def main():
   extra = ['--reanalyse_rows', str(a.reanalyse_rows)] if a.reanalyse_rows else []
   if a.reanalyse_rows and a.reanalyse_every:
     extra += ['--reanalyse_every', str(a.reanalyse_every)]
+  if a.symmetry:
+    extra += ['--symmetry']
   torch.manual_seed(0)
   untrained_sd = get_network(make_config(base), torch.device('cpu')).state_dict()
   if a.environment == 'TicTacToe':
