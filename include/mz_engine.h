@@ -298,6 +298,20 @@ int mz_playout_plan(mz_engine *e, int kind, const int8_t *boards, const int8_t *
                     int playouts, uint64_t move, int32_t *action_out, int32_t *visits_out, int32_t *wins_out, void *stream);
 int mz_eval_env_set_opponent(mz_engine *e, int playouts, void *stream);
 
+/* The exact game solver (DESIGN s7f; csrc/mz_solve.hip.h): for each of n positions of TicTacToe (kind 1) or Connect Four
+ * (kind 3) and each action a, the outcome for the mover after playing a with both sides perfect from there -- +1 the mover
+ * wins, 0 a draw, -1 the mover loses (the outcome only, not the distance to it), -2 a is illegal, -3 not solved within
+ * max_nodes nodes.  A plain negamax with the window [-1, +1], a fixed move order and no transposition table; the unit of
+ * work is the subtree under one (position, action), searched by one lane with its own budget of max_nodes (1 .. 2^30)
+ * nodes, so a value depends on the position and the budget alone, not on the batch.  Takes an engine of the game's shape
+ * (as mz_playout_plan); the weights are not read.  [host] boards [n][42] int8, turn [n] int8, step [n] int32 as
+ * mz_playout_plan's, any n (chunks of num_envs inside); every position must be one of the game's with a legal action in
+ * which neither side has a line yet.  Out, [host]: values_out [n][A] int8, nodes_out [n][A] uint32 (or NULL): the nodes
+ * spent on a, saturating at max_nodes (0 where illegal).  Its device memory is its own, allocated on first use.
+ * Synchronises once, at the end. */
+int mz_solve(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
+             int8_t *values_out, uint32_t *nodes_out, void *stream);
+
 /* A match between two networks on the device games: B games in lock-step, every ply searched by the mover's own network.
  * Replaces the per-ply host loop a match driven from Python would need (two Evaluator._play_batch loops interleaved by
  * hand: per ply one engine call sequence and one host environment step); the host touches no game between plies.

@@ -133,6 +133,13 @@ int mz_playout_plan_host(int kind, int A, uint64_t seed, int env_id_offset, cons
                          const int32_t *step, int n_games, int playouts, uint64_t move, int32_t *action_out,
                          int32_t *visits_out, int32_t *wins_out);
 
+/* test hook: mz_solve's units searched one after the other on the HOST -- the same __host__ __device__ bodies of
+ * csrc/mz_solve.hip.h in the same order with the same budget, so values, the unsolved pattern and the node counts equal the
+ * device's exactly.  Takes no engine and touches no device: A is the game's action count (9 / 7).  Arguments, checks and
+ * outputs as mz_solve's. */
+int mz_solve_host(int kind, int A, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
+                  int8_t *values_out, uint32_t *nodes_out);
+
 /* test hooks of mz_fcl_set_symmetry.  mz_fcl_symmetry_apply: the symmetry kernel alone, with the handle's kind and seed and the
  * given update number, on device-visible arrays of the handle's batch (obs [batch][obs_dim], actions [batch][K] int32 / int64,
  * target_policies [batch][K + 1][A]; device memory, or mapped pinned host memory as mz_fcl_run's staging is -- the hook looks its

@@ -206,7 +206,7 @@ def make_config(argv=None, **overrides):
 def get_evaluation_args(argv=None):
   """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
   engine; default min(num_games, 4096)), --out (a JSON summary), --device_env / --keep_history (the games on the device
-  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
+  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes (moves graded against the exact solver, solver.py) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
   saves_dir + net for every pair."""
   p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
   a = p.add_argument
@@ -243,6 +243,13 @@ def get_evaluation_args(argv=None):
   a('--opp_playouts', type=int, default=0,
     help='--device_env --random_opp SEAT: that seat is played by a playout search (UCT on the true rules, no network) of this '
          'many playouts per move, a multiple of 64 in 64 .. 65536; 0: the uniformly random mover')
+  a('--grade', action='store_true',
+    help='--device_env, TicTacToe / ConnectFour: grade the moves against the exact solver (the network\'s moves with '
+         '--random_opp, both sides\' without): optimal-move rate, blunders by class, value errors against the true value')
+  a('--grade_empties', type=int, default=12,
+    help='--grade on ConnectFour: positions with at most this many empty cells are graded (TicTacToe grades every position)')
+  a('--grade_nodes', type=int, default=4096,
+    help='--grade: the solver\'s node budget per (position, action); a decision it does not settle is counted as unsolved')
   a('--match', action='store_true',
     help='play every pair of --nets against each other on the device games (TicTacToe, ConnectFour), every seed from both '
          'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise then take one '

@@ -35,6 +35,7 @@
 #include "mz_match.hip.h"
 #include "mz_reanalyse.hip.h"
 #include "mz_playout.hip.h"
+#include "mz_solve.hip.h"
 #include "mz_symmetry.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
@@ -174,6 +175,7 @@ struct mz_engine {
   bool ev_temp_set = false;
   ReanalyseState ra = {};           // Reanalyse of stored replay rows (mz_reanalyse; mz_reanalyse.hip.h), allocated on first use
   PlayoutState po = {};             // the playout-search opponent (mz_playout_plan, mz_eval_env_set_opponent; mz_playout.hip.h), allocated on first use
+  SolveState sv = {};               // the exact game solver (mz_solve; mz_solve.hip.h), allocated on first use
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -1655,6 +1657,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 
 #include "mz_selfplay_abi.inc"
 #include "mz_playout_abi.inc"
+#include "mz_solve_abi.inc"
 #include "mz_eval_abi.inc"
 #include "mz_match_abi.inc"
 #include "mz_reanalyse_abi.inc"

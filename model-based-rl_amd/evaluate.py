@@ -97,6 +97,27 @@ def refuse_opp_playouts(args_or_config, match=False):
     raise NotImplementedError('--opp_playouts: the playout opponent answers every move and takes --apply_mcts_actions 1 only.')
 
 
+GRADE_ENVS = ('TicTacToe', 'ConnectFour')
+
+
+def refuse_grade(args_or_config, match=False):
+  """one sentence per configuration --grade (moves graded against the exact solver, solver.py) leaves out
+  (NotImplementedError, starting '--grade: '); nothing to refuse without the flag"""
+  c = args_or_config
+  if not getattr(c, 'grade', False):
+    return
+  if match:
+    raise NotImplementedError('--grade: the games of --match are not graded; grade each network with evaluate --device_env --grade.')
+  if not getattr(c, 'device_env', False):
+    raise NotImplementedError('--grade: the graded games are the device environments\' and need --device_env.')
+  env = getattr(c, 'environment', None)
+  if env is not None and env not in GRADE_ENVS:
+    raise NotImplementedError('--grade: %s has no exact solver; it solves %s.' % (env, ' and '.join(GRADE_ENVS)))
+  m = getattr(c, 'apply_mcts_actions', 1)
+  if any(int(x) != 1 for x in (m if isinstance(m, (list, tuple)) else [m])):
+    raise NotImplementedError('--grade: a graded decision is one searched move and takes --apply_mcts_actions 1 only.')
+
+
 class DeviceGame(object):
   """A finished game of the device-environment path: what the summary and the CLI read, from the device's accumulators.
   With keep_history also the per-move lists under the host path's names (history.actions / rewards / to_play / dones /
@@ -159,6 +180,8 @@ class Evaluator(SummaryTools):
     refuse_unsupported(self.config)
     refuse_device_env(self.config)
     refuse_opp_playouts(_with(self.config, device_env=True))      # (play_games(device_env=True) may still name the device path)
+    refuse_grade(_with(self.config, device_env=True))
+    self.grade_report = None      # --grade: the report of the last play_games (solver.grade_games)
     if not torch.cuda.is_available():
       raise RuntimeError('the evaluator needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
     self.device = torch.device(device if device is not None else 'cuda')
@@ -190,8 +213,10 @@ class Evaluator(SummaryTools):
     keep_history (or config.keep_history) carrying the per-move lists; start_states [num_games][4]: CartPole's start states
     instead of the counter RNG's (device path only)."""
     device_env = bool(device_env or getattr(self.config, 'device_env', False))
-    keep_history = bool(keep_history or getattr(self.config, 'keep_history', False))
+    grade = bool(getattr(self.config, 'grade', False))
+    keep_history = bool(keep_history or grade or getattr(self.config, 'keep_history', False))
     refuse_opp_playouts(_with(self.config, device_env=device_env))
+    refuse_grade(_with(self.config, device_env=device_env))
     assert self.weights is not None, '.load_network() needs to be called before playing.'
     if device_env and environments is not None:
       raise ValueError('play_games: a device-environment run builds no host environment')
@@ -212,7 +237,28 @@ class Evaluator(SummaryTools):
         continue
       envs = environments[lo:hi] if environments is not None else [get_environment(self.config) for _ in range(lo, hi)]
       games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
+    if grade:
+      self.grade_report = self.grade(games)
     return games
+
+  def grade(self, games):
+    """--grade: the keep_history games graded against the exact solver (solver.grade_games) -- the network's moves where
+    --random_opp seats an opponent, both sides' otherwise; TicTacToe every position, ConnectFour those with at most
+    config.grade_empties empty cells"""
+    from . import solver
+    cfg = self.config
+    t0 = time.perf_counter()
+    opp = getattr(cfg, 'random_opp', None)
+    eng = Engine.from_config(cfg, min(len(games), self.batch), device=self.device, seed=0)
+    try:
+      report = solver.grade_games(games, cfg.environment, eng,
+                                  max_empties=None if cfg.environment == 'TicTacToe' else int(getattr(cfg, 'grade_empties', solver.DEFAULT_EMPTIES)),
+                                  graded_seat=None if opp is None else -int(opp),
+                                  max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)))
+    finally:
+      eng.close()
+    report['seconds'] = time.perf_counter() - t0
+    return report
 
   def _play_batch_device(self, seeds, draws, start_states, keep_history):
     """_play_batch with the games on the device environments: whole moves are enqueued MOVES_PER_SYNC at a time
@@ -490,6 +536,7 @@ def state_generator(args):
                     c.device_env = args.device_env
                     c.keep_history = args.keep_history
                     c.opp_playouts = args.opp_playouts
+                    c.grade, c.grade_empties, c.grade_nodes = args.grade, args.grade_empties, args.grade_nodes
                     yield state
 
 
@@ -502,6 +549,7 @@ def run(evaluator, seed=None):
 def main(argv=None):
   args = get_evaluation_args(argv)
   refuse_opp_playouts(args, match=args.match)
+  refuse_grade(args, match=args.match)
   if args.match:      # checkpoint against checkpoint (match.py); implies the device path
     from . import match
     return match.main(args)
@@ -527,6 +575,10 @@ def main(argv=None):
       opponent = '{}-playout search'.format(args.opp_playouts) if args.opp_playouts else 'a random opponent'
       print("Against {} (the agent moves {}): wins {} draws {} losses {}\n".format(
           opponent, 'second' if args.random_opp == 1 else 'first', s['wins'], s['draws'], s['losses']))
+    if evaluator.grade_report is not None:
+      from . import solver
+      s['grade'] = evaluator.grade_report
+      print(solver.format_report(evaluator.grade_report, evaluator.config.label))
     s['games_per_s'] = len(games) / wall
     s['host_share'] = evaluator.host_seconds / wall
     results.append(s)

@@ -1,0 +1,120 @@
+"""Grading of evaluation games against the exact solver (Engine.solve; DESIGN s7f): the positions of keep_history games are
+rebuilt on the host rules of envs.py, solved on the device, and every graded decision is compared with the game-theoretic
+value of its position.
+
+Perspective: history.root_values[k] is the searched root's value and pred_values[k] the value head's output at move k.  The
+root is expanded with to_play = the mover and the backup adds a leaf's value to a node with the sign of that node's own
+to_play (mcts.py:126-128), and the value head reads the observation turn * board: both are the MOVER's view, which is the
+view of the solver's values, so no sign is applied."""
+import numpy as np
+
+from .engine import Engine
+from .envs import ConnectFour, TicTacToe
+
+KINDS = {'TicTacToe': 1, 'ConnectFour': 3}
+CELLS = {1: 9, 3: 42}
+ILLEGAL, UNSOLVED = -2, -3
+BLUNDERS = ('win_to_draw', 'win_to_loss', 'draw_to_loss')
+DEFAULT_EMPTIES = 12      # Connect Four: positions with at most this many empty cells are graded (derived from profiles/solve_bench.json: README)
+DEFAULT_NODES = Engine.SOLVE_NODES
+
+
+def _kind(kind):
+  k = KINDS[kind] if isinstance(kind, str) else int(kind)
+  if k not in CELLS:
+    raise ValueError('the solver plays TicTacToe (1) and ConnectFour (3), got kind %r' % (kind,))
+  return k
+
+
+def positions_of(games, kind, min_step=0):
+  """the position before every action of keep_history games, replayed from history.actions on envs.TicTacToe /
+  envs.ConnectFour; min_step: only the positions with at least so many plies played (a game that ended before is not
+  replayed at all).  Returns a dict of arrays over the P positions: boards [P, 42] int8, turn [P] int8 (the mover), step [P]
+  int32, game [P] int32 (index into games), ply [P] int32, action [P] int32 (the action taken there)."""
+  k = _kind(kind)
+  cells = CELLS[k]
+  boards, turn, step, game, ply, action = [], [], [], [], [], []
+  for gi, g in enumerate(games):
+    if g.history is None:
+      raise ValueError('positions_of: game %d carries no history (play the games with keep_history)' % gi)
+    if len(g.history.actions) <= min_step:
+      continue
+    env = TicTacToe() if k == 1 else ConnectFour()
+    done = False
+    for p, a in enumerate(g.history.actions):
+      if done:
+        raise ValueError('positions_of: game %d goes on after its end at ply %d' % (gi, p))
+      if p >= min_step:
+        bd = np.zeros(42, np.int8)
+        bd[:cells] = env.board
+        boards.append(bd); turn.append(env.turn); step.append(p); game.append(gi); ply.append(p); action.append(int(a))
+      _, _, done, _ = env.step(int(a))
+  return dict(boards=np.array(boards, np.int8).reshape(-1, 42), turn=np.array(turn, np.int8), step=np.array(step, np.int32),
+              game=np.array(game, np.int32), ply=np.array(ply, np.int32), action=np.array(action, np.int32))
+
+
+def grade_games(games, kind, engine, max_empties=None, graded_seat=None, max_nodes=DEFAULT_NODES):
+  """grade the decisions of keep_history games (one applied action per move).  engine: an Engine of the game's shape (its
+  solve() is all that is used).  max_empties: only positions with at most so many empty cells (None: all).  graded_seat: +1
+  / -1 grades the moves of that seat only (the network's, when the other seat is an opponent's), None both.
+
+  Per decision, with value[a] the solver's outcome for the mover after a: v* = max over a of value[a], c = value[action].
+  A decision is graded when both are solved: c is not -3, and v* is +1 or no legal action is -3.  Returns a dict: graded;
+  unsolved (in scope but left out, counted); optimal (c == v*) and optimal_rate; blunders {win_to_draw, win_to_loss,
+  draw_to_loss}; root_value_mae / pred_value_mae (mean |x - v*|, the mover's view); decisive (graded with v* != 0) and
+  root_value_sign / pred_value_sign, the share of the decisive ones with sign(x) == v*; nodes, the solver's total.  Rates
+  over an empty set are None."""
+  k = _kind(kind)
+  pos = positions_of(games, k, 0 if max_empties is None else max(0, CELLS[k] - int(max_empties)))
+  scope = np.ones(len(pos['turn']), bool)
+  if graded_seat is not None:
+    scope &= pos['turn'] == int(graded_seat)
+  idx = np.flatnonzero(scope)
+  report = dict(graded=0, unsolved=0, optimal=0, optimal_rate=None, blunders={b: 0 for b in BLUNDERS}, root_value_mae=None,
+                pred_value_mae=None, decisive=0, root_value_sign=None, pred_value_sign=None, nodes=0,
+                max_empties=None if max_empties is None else int(max_empties), max_nodes=int(max_nodes))
+  if len(idx) == 0:
+    return report
+  values, nodes = engine.solve(k, pos['boards'][idx], pos['turn'][idx], pos['step'][idx], max_nodes=int(max_nodes))
+  values = np.asarray(values).astype(np.int64)
+  report['nodes'] = int(np.asarray(nodes, np.uint64).sum())
+  best = values.max(1)
+  chosen = values[np.arange(len(idx)), pos['action'][idx]]
+  if np.any(chosen == ILLEGAL):
+    raise ValueError('grade_games: a game record holds an action that is illegal in its position')
+  solved = (chosen != UNSOLVED) & ((best == 1) | ~(values == UNSOLVED).any(1))
+  report['unsolved'] = int((~solved).sum())
+  report['graded'] = n = int(solved.sum())
+  if n == 0:
+    return report
+  best, chosen, at = best[solved], chosen[solved], idx[solved]
+  report['optimal'] = int((chosen == best).sum())
+  report['optimal_rate'] = report['optimal'] / n
+  report['blunders'] = dict(win_to_draw=int(((best == 1) & (chosen == 0)).sum()), win_to_loss=int(((best == 1) & (chosen == -1)).sum()),
+                            draw_to_loss=int(((best == 0) & (chosen == -1)).sum()))
+  root = np.array([games[g].history.root_values[p] for g, p in zip(pos['game'][at], pos['ply'][at])], np.float64)
+  pred = np.array([games[g].pred_values[p] for g, p in zip(pos['game'][at], pos['ply'][at])], np.float64)
+  report['root_value_mae'] = float(np.mean(np.abs(root - best)))
+  report['pred_value_mae'] = float(np.mean(np.abs(pred - best)))
+  dec = best != 0
+  report['decisive'] = int(dec.sum())
+  if report['decisive']:
+    report['root_value_sign'] = float(np.mean(np.sign(root[dec]) == best[dec]))
+    report['pred_value_sign'] = float(np.mean(np.sign(pred[dec]) == best[dec]))
+  return report
+
+
+def format_report(r, label=''):
+  """the block the evaluate CLI prints per configuration"""
+  pct = lambda x: 'n/a' if x is None else '{:.1f}%'.format(100.0 * x)
+  num = lambda x: 'n/a' if x is None else '{:.3f}'.format(x)
+  b = r['blunders']
+  scope = 'every position' if r['max_empties'] is None else 'positions with at most {} empty cells'.format(r['max_empties'])
+  return '\n'.join([
+      'Graded against the exact solver{}: {} decisions ({}), {} left out as unsolved within {} nodes'.format(
+          ' - label: ({})'.format(label) if label else '', r['graded'], scope, r['unsolved'], r['max_nodes']),
+      'Optimal moves: {} of {} ({})'.format(r['optimal'], r['graded'], pct(r['optimal_rate'])),
+      'Blunders: win to draw {}, win to loss {}, draw to loss {}'.format(b['win_to_draw'], b['win_to_loss'], b['draw_to_loss']),
+      'Value error against the true value: mcts {} (sign right {}), predicted {} (sign right {}) - {} decisive positions'.format(
+          num(r['root_value_mae']), pct(r['root_value_sign']), num(r['pred_value_mae']), pct(r['pred_value_sign']), r['decisive']),
+      ''])

@@ -6,7 +6,7 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
 
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
-                                       [--opp_playouts 1024] [--symmetry]
+                                       [--opp_playouts 1024] [--symmetry] [--grade]
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --symmetry adds train's flag (every sample trained on one of the equivalent images of its position, symmetry.py) to the training run.
@@ -55,20 +55,23 @@ def play_vs_random(weights, agent_side, games=512, sims=30, seed=0, no_support=F
   return int((result == 1).sum()), int((result == 0).sum()), int((result == -1).sum())
 
 
-def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_playouts=0):
+def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_playouts=0, grade=None):
   """the same match through the evaluator's device-environment path (any environment with a device form); `weights` a
   state_dict.  Returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second.  opp_playouts > 0: the
-  opponent is the playout search of that budget (evaluate --opp_playouts) instead of the random mover."""
+  opponent is the playout search of that budget (evaluate --opp_playouts) instead of the random mover.  grade: a list that
+  receives the report of the agent's moves graded against the exact solver (evaluate --grade), or None: no grading."""
   import copy
   from model_based_rl_amd.evaluate import Evaluator, game_return
   cfg = copy.copy(config)
   for k, v in dict(temperature=0, only_prior=0, only_value=0, use_exploration_noise=0, apply_mcts_actions=1,
                    random_opp=-agent_side, human_opp=None, render=False, save_mcts=False, save_gif_as='', label='vs random',
-                   verbose=False, batch=games, device_env=True, keep_history=False, opp_playouts=int(opp_playouts)).items():
+                   verbose=False, batch=games, device_env=True, keep_history=False, opp_playouts=int(opp_playouts), grade=grade is not None).items():
     setattr(cfg, k, v)
   ev = Evaluator({'config': cfg, 'weights': weights, 'training_step': 0})
   ev.load_network()
   ret = np.array([game_return(g) for g in ev.play_games(games, list(range(seed, seed + games)))])
+  if grade is not None:
+    grade.append(ev.grade_report)
   return int((ret > 0).sum()), int((ret == 0).sum()), int((ret < 0).sum())
 
 
@@ -87,6 +90,8 @@ def main():
   ap.add_argument('--opp_playouts', type=int, default=0,
                   help='also play the 512 games per side against a playout search of this many playouts per move (evaluate --opp_playouts)')
   ap.add_argument('--symmetry', action='store_true', help='train --symmetry: board-symmetry augmentation of the training batches')
+  ap.add_argument('--grade', action='store_true',
+                  help='also grade the agent\'s moves of 512 games per side against the exact solver (evaluate --grade), before and after training')
   a = ap.parse_args()
   from model_based_rl_amd import train
   from model_based_rl_amd.config import make_config
@@ -122,6 +127,13 @@ def main():
   if a.opp_playouts:      # an absolute line: the same games against a search whose strength ignores the weights
     vs_playouts = {name: {side: play_vs_random_device(make_config(base), sd, side, opp_playouts=a.opp_playouts) for side in (1, -1)}
                    for name, sd in (('untrained', untrained_sd), ('trained', state['weights']))}
+  if a.grade:      # the absolute line per evaluation point: optimal-move rate, blunders, value errors (no opponent's noise in it)
+    graded = {}
+    for name, sd in (('untrained', untrained_sd), ('trained', state['weights'])):
+      for side_, key in ((1, 'agent_first'), (-1, 'agent_second')):
+        got = []
+        play_vs_random_device(make_config(base), sd, side_, grade=got)
+        graded.setdefault(name, {})[key] = got[0]
   # the last checkpoint against the first kept one, from both seats (match.play_match); where the run kept a single
   # checkpoint, against the untrained network
   from model_based_rl_amd.match import play_match
@@ -148,6 +160,8 @@ def main():
   if a.opp_playouts:
     out['vs_%d_playout_search_512_games' % a.opp_playouts] = {
         name: {'agent_first (win, draw, loss)': r[1], 'agent_second': r[-1]} for name, r in vs_playouts.items()}
+  if a.grade:
+    out['graded_vs_random_512_games'] = graded
   if a.keep_checkpoint:
     torch.save({'weights': state['weights'], 'training_step': int(state['training_step'])}, a.keep_checkpoint)
   if a.match_against:
