@@ -312,6 +312,15 @@ int mz_eval_env_set_opponent(mz_engine *e, int playouts, void *stream);
 int mz_solve(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
              int8_t *values_out, uint32_t *nodes_out, void *stream);
 
+/* The table search (DESIGN s7f, "The table search"): mz_solve's arguments, checks, chunks, outputs and one synchronisation,
+ * the same units with the same top and the same budget rule, searched with the moves that do not lose at once only, ordered
+ * by the threats they make, and a transposition table of 4096 entries private to each unit.  Values are exact as
+ * mz_solve's; a unit needs far fewer nodes (nodes_out counts this search's stones), so at a given max_nodes fewer are -3.
+ * A unit sees no entry of another unit, so a value and a node count depend on the position and the budget alone.  Its
+ * tables (32 KB a lane, for min(1024, ceil(num_envs * A / 64)) waves) are its own, allocated on first use. */
+int mz_solve_tt(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
+                int8_t *values_out, uint32_t *nodes_out, void *stream);
+
 /* A match between two networks on the device games: B games in lock-step, every ply searched by the mover's own network.
  * Replaces the per-ply host loop a match driven from Python would need (two Evaluator._play_batch loops interleaved by
  * hand: per ply one engine call sequence and one host environment step); the host touches no game between plies.

@@ -140,6 +140,16 @@ int mz_playout_plan_host(int kind, int A, uint64_t seed, int env_id_offset, cons
 int mz_solve_host(int kind, int A, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
                   int8_t *values_out, uint32_t *nodes_out);
 
+/* test hooks of mz_solve_tt.  mz_solve_tt_host: its units searched one after the other on the HOST with one table and one
+ * generation counter, as one lane has them -- the same __host__ __device__ bodies, so values, the unsolved pattern and the
+ * node counts equal the device's exactly; arguments, checks and outputs as mz_solve_host's.  mz_solve_tt_set_generation:
+ * every lane's generation counter becomes `generation` (0 .. 2047; the tables are allocated if they were not; synchronous),
+ * so a test can cross the wrap at 2048, where a lane clears its table.  The tables keep their entries: set a value no
+ * entry carries yet, or one from which the wrap is crossed before an entry's generation comes round. */
+int mz_solve_tt_host(int kind, int A, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
+                     int8_t *values_out, uint32_t *nodes_out);
+int mz_solve_tt_set_generation(mz_engine *e, int generation);
+
 /* test hooks of mz_fcl_set_symmetry.  mz_fcl_symmetry_apply: the symmetry kernel alone, with the handle's kind and seed and the
  * given update number, on device-visible arrays of the handle's batch (obs [batch][obs_dim], actions [batch][K] int32 / int64,
  * target_policies [batch][K + 1][A]; device memory, or mapped pinned host memory as mz_fcl_run's staging is -- the hook looks its

@@ -160,6 +160,9 @@ SIGNATURES = {
     'mz_eval_env_set_opponent': (_I, [_VP, _I, _VP]),
     'mz_solve': (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     'mz_solve_host': (_I, [_I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP]),
+    'mz_solve_tt': (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
+    'mz_solve_tt_host': (_I, [_I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP]),
+    'mz_solve_tt_set_generation': (_I, [_VP, _I]),
     'mz_match_create': (_I, [_VP, _VP, _I, _I, _I, C.POINTER(_VP)]),
     'mz_match_destroy': (_I, [_VP]),
     'mz_match_reset': (_I, [_VP, _I, _I, _VP]),

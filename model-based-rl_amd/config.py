@@ -206,7 +206,7 @@ def make_config(argv=None, **overrides):
 def get_evaluation_args(argv=None):
   """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
   engine; default min(num_games, 4096)), --out (a JSON summary), --device_env / --keep_history (the games on the device
-  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes (moves graded against the exact solver, solver.py) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
+  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes / --grade_table (moves graded against the exact solver, solver.py) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
   saves_dir + net for every pair."""
   p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
   a = p.add_argument
@@ -250,6 +250,9 @@ def get_evaluation_args(argv=None):
     help='--grade on ConnectFour: positions with at most this many empty cells are graded (TicTacToe grades every position)')
   a('--grade_nodes', type=int, default=4096,
     help='--grade: the solver\'s node budget per (position, action); a decision it does not settle is counted as unsolved')
+  a('--grade_table', action='store_true',
+    help='--grade: solve with the table search (non-losing moves, ordered by threats, a transposition table a unit): the same '
+         'exact values from far fewer nodes, so --grade_empties can be raised at the same --grade_nodes')
   a('--match', action='store_true',
     help='play every pair of --nets against each other on the device games (TicTacToe, ConnectFour), every seed from both '
          'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise then take one '

@@ -176,6 +176,7 @@ struct mz_engine {
   ReanalyseState ra = {};           // Reanalyse of stored replay rows (mz_reanalyse; mz_reanalyse.hip.h), allocated on first use
   PlayoutState po = {};             // the playout-search opponent (mz_playout_plan, mz_eval_env_set_opponent; mz_playout.hip.h), allocated on first use
   SolveState sv = {};               // the exact game solver (mz_solve; mz_solve.hip.h), allocated on first use
+  SolveTableState svt = {};         // its table search's tables and counters (mz_solve_tt), allocated on its first use
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be

@@ -487,8 +487,9 @@ class Engine(object):
 
   SOLVE_NODES = 4096      # the default node budget of one (position, action): derived from profiles/solve_bench.json (README, "Grading moves")
 
-  def solve(self, kind, boards, turn, step, max_nodes=SOLVE_NODES):
-    """mz_solve: the exact outcome of every action of n positions of `kind` (an EVAL_ENVS name or 1 / 3; any n): boards
+  def solve(self, kind, boards, turn, step, max_nodes=SOLVE_NODES, table=False):
+    """mz_solve, or with table=True mz_solve_tt (the table search: the same exact values from far fewer nodes, so `nodes`
+    counts another search and fewer units are unsolved at a given max_nodes): the exact outcome of every action of n positions of `kind` (an EVAL_ENVS name or 1 / 3; any n): boards
     [n, 42], turn [n], step [n] as playout_plan's, none with a finished line.  Returns numpy arrays: values [n, A] int8 (+1 /
     0 / -1 for the mover after the action, -2 illegal, -3 not solved within max_nodes nodes) and nodes [n, A] uint32."""
     k = self.EVAL_ENVS[kind] if isinstance(kind, str) else int(kind)
@@ -499,8 +500,8 @@ class Engine(object):
       raise ValueError('solve: boards [n, 42], turn [n], step [n]; got %s, %s, %s' % (bd.shape, tn.shape, st.shape))
     values, nodes = np.zeros((n, self.A), np.int8), np.zeros((n, self.A), np.uint32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    _abi.check(self.lib.mz_solve(self._h, k, p(bd), p(tn), p(st), n, int(max_nodes), p(values), p(nodes), self.stream),
-               'mz_solve')
+    name = 'mz_solve_tt' if table else 'mz_solve'
+    _abi.check(getattr(self.lib, name)(self._h, k, p(bd), p(tn), p(st), n, int(max_nodes), p(values), p(nodes), self.stream), name)
     return values, nodes
 
   # ---- Reanalyse of stored replay rows (mz_reanalyse, include/mz_engine.h)

@@ -102,9 +102,12 @@ GRADE_ENVS = ('TicTacToe', 'ConnectFour')
 
 def refuse_grade(args_or_config, match=False):
   """one sentence per configuration --grade (moves graded against the exact solver, solver.py) leaves out
-  (NotImplementedError, starting '--grade: '); nothing to refuse without the flag"""
+  (NotImplementedError, starting '--grade: '); nothing to refuse without the flag, but --grade_table, which only chooses
+  the grading's search (a sentence starting '--grade_table: ')"""
   c = args_or_config
   if not getattr(c, 'grade', False):
+    if getattr(c, 'grade_table', False):
+      raise NotImplementedError('--grade_table: it chooses the search that --grade solves with and grades nothing without --grade.')
     return
   if match:
     raise NotImplementedError('--grade: the games of --match are not graded; grade each network with evaluate --device_env --grade.')
@@ -254,7 +257,8 @@ class Evaluator(SummaryTools):
       report = solver.grade_games(games, cfg.environment, eng,
                                   max_empties=None if cfg.environment == 'TicTacToe' else int(getattr(cfg, 'grade_empties', solver.DEFAULT_EMPTIES)),
                                   graded_seat=None if opp is None else -int(opp),
-                                  max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)))
+                                  max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)),
+                                  table=bool(getattr(cfg, 'grade_table', False)))
     finally:
       eng.close()
     report['seconds'] = time.perf_counter() - t0
@@ -537,6 +541,7 @@ def state_generator(args):
                     c.keep_history = args.keep_history
                     c.opp_playouts = args.opp_playouts
                     c.grade, c.grade_empties, c.grade_nodes = args.grade, args.grade_empties, args.grade_nodes
+                    c.grade_table = args.grade_table
                     yield state
 
 

@@ -53,10 +53,11 @@ def positions_of(games, kind, min_step=0):
               game=np.array(game, np.int32), ply=np.array(ply, np.int32), action=np.array(action, np.int32))
 
 
-def grade_games(games, kind, engine, max_empties=None, graded_seat=None, max_nodes=DEFAULT_NODES):
+def grade_games(games, kind, engine, max_empties=None, graded_seat=None, max_nodes=DEFAULT_NODES, table=False):
   """grade the decisions of keep_history games (one applied action per move).  engine: an Engine of the game's shape (its
   solve() is all that is used).  max_empties: only positions with at most so many empty cells (None: all).  graded_seat: +1
-  / -1 grades the moves of that seat only (the network's, when the other seat is an opponent's), None both.
+  / -1 grades the moves of that seat only (the network's, when the other seat is an opponent's), None both.  table: solve
+  with the table search (engine.solve(table=True)); the report then carries solver: 'table'.
 
   Per decision, with value[a] the solver's outcome for the mover after a: v* = max over a of value[a], c = value[action].
   A decision is graded when both are solved: c is not -3, and v* is +1 or no legal action is -3.  Returns a dict: graded;
@@ -73,9 +74,12 @@ def grade_games(games, kind, engine, max_empties=None, graded_seat=None, max_nod
   report = dict(graded=0, unsolved=0, optimal=0, optimal_rate=None, blunders={b: 0 for b in BLUNDERS}, root_value_mae=None,
                 pred_value_mae=None, decisive=0, root_value_sign=None, pred_value_sign=None, nodes=0,
                 max_empties=None if max_empties is None else int(max_empties), max_nodes=int(max_nodes))
+  if table:
+    report['solver'] = 'table'
   if len(idx) == 0:
     return report
-  values, nodes = engine.solve(k, pos['boards'][idx], pos['turn'][idx], pos['step'][idx], max_nodes=int(max_nodes))
+  values, nodes = engine.solve(k, pos['boards'][idx], pos['turn'][idx], pos['step'][idx], max_nodes=int(max_nodes),
+                               **(dict(table=True) if table else {}))
   values = np.asarray(values).astype(np.int64)
   report['nodes'] = int(np.asarray(nodes, np.uint64).sum())
   best = values.max(1)
@@ -111,8 +115,9 @@ def format_report(r, label=''):
   b = r['blunders']
   scope = 'every position' if r['max_empties'] is None else 'positions with at most {} empty cells'.format(r['max_empties'])
   return '\n'.join([
-      'Graded against the exact solver{}: {} decisions ({}), {} left out as unsolved within {} nodes'.format(
-          ' - label: ({})'.format(label) if label else '', r['graded'], scope, r['unsolved'], r['max_nodes']),
+      'Graded against the exact solver{}{}: {} decisions ({}), {} left out as unsolved within {} nodes'.format(
+          ' (table search)' if r.get('solver') == 'table' else '', ' - label: ({})'.format(label) if label else '', r['graded'],
+          scope, r['unsolved'], r['max_nodes']),
       'Optimal moves: {} of {} ({})'.format(r['optimal'], r['graded'], pct(r['optimal_rate'])),
       'Blunders: win to draw {}, win to loss {}, draw to loss {}'.format(b['win_to_draw'], b['win_to_loss'], b['draw_to_loss']),
       'Value error against the true value: mcts {} (sign right {}), predicted {} (sign right {}) - {} decisive positions'.format(
