@@ -22,7 +22,7 @@ import os
 
 from .engine import Engine, flatten_weights, records_view
 from .config import CARTPOLE_TIME_LIMITS
-from .envs import get_environment
+from .envs import get_environment, KIND_OF_ENV
 from .logger import Logger
 from .networks import get_network
 
@@ -160,9 +160,9 @@ class Actor(Logger):
     self.device = torch.device('cuda', ids[actor_key] if ids else torch.cuda.current_device())
     self.num_envs = int(getattr(config, 'num_envs', 1))
     # TicTacToe: the reference's environment object on the host for parity runs (numpy's global stream) and single games;
-    # a pool of games runs the same rules on the device (mz_selfplay_set_env, csrc/mz_selfplay.hip.h)
+    # a pool of games runs the same rules on the device (mz_selfplay_set_env, csrc/mz_games.h)
     # CartPole likewise: envs.CartPole on the host, the same dynamics bit for bit on the device for a pool; and ConnectFour
-    self.host_env = (config.environment in ('TicTacToe', 'ConnectFour') or config.environment in CARTPOLE_TIME_LIMITS) and (bool(getattr(config, 'parity_rng', False)) or self.num_envs == 1)
+    self.host_env = config.environment in KIND_OF_ENV and (bool(getattr(config, 'parity_rng', False)) or self.num_envs == 1)
     # FCNetwork: the engine's own fused HIP kernels.  Any other architecture (MuZeroNetwork / TinyNetwork): the torch
     # network stays in the loop behind the batched external-inference path (actors.py:45-47 is network-agnostic)
     self.torch_net = getattr(config, 'architecture', 'FCNetwork') != 'FCNetwork'
@@ -406,12 +406,8 @@ class Actor(Logger):
         ram = '-ram' in str(cfg.environment)
         eng.selfplay_set_obs(uint8_obs=ram, obs_min=self.obs_min if norm else None, obs_range=self.obs_range if norm else None,
                              packed=ram and bool(getattr(cfg, 'obs_u8', False)))      # (bytes in the records: a replay with obs_u8)
-      if cfg.environment == 'TicTacToe':
-        eng.selfplay_set_env('tictactoe')
-      if cfg.environment == 'ConnectFour':             # (refuses a single player and --norm_obs: the engine's sentence surfaces)
-        eng.selfplay_set_env('connect_four')
-      if cfg.environment in CARTPOLE_TIME_LIMITS:      # (refuses --norm_obs: not built for this environment)
-        eng.selfplay_set_env('cartpole')
+      if cfg.environment in KIND_OF_ENV:      # (refuses the wrong number of players, and --norm_obs where the game is not built for it: the engine's sentence surfaces)
+        eng.selfplay_set_env(KIND_OF_ENV[cfg.environment])
       # (CartPole: the episode length is the environment's time limit, whatever --episode_length says)
       eng.selfplay_reset(CARTPOLE_TIME_LIMITS.get(cfg.environment, cfg.episode_length), temperature, stagger=True)
       self._selfplay_temperature = temperature

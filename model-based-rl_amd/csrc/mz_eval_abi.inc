@@ -2,25 +2,31 @@
 // mz_engine.hip; kernels and state: mz_eval_env.hip.h).  Replaces the host loop between two moves of Evaluator._play_batch
 // (reference evaluate.py:331-374) for TicTacToe, CartPole and Connect Four.
 
-static int eval_env_shape(const mz_engine *e, int kind, const char **why) {
-  const bool two = e->cfg.two_players != 0;
-  if (kind == 1 && (e->O != 9 || e->A != 9 || !two)) { *why = "TicTacToe needs obs_dim 9, action_space 9, two_players"; return -1; }
-  if (kind == 2 && (e->O != 4 || e->A != 2 || two)) { *why = "CartPole needs obs_dim 4, action_space 2, a single player"; return -1; }
-  if (kind == 3 && (e->O != 42 || e->A != 7 || !two)) { *why = "Connect Four needs obs_dim 42, action_space 7, two_players"; return -1; }
-  return 0;
+// One searched move of engine e on the inputs laid out in io: initial inference, root preparation with the given draws
+// (have_noise: io.noise holds them), the device's, or none, then the search with its walk of M actions and finalize (mode
+// 0) or the lookahead (mode 1 only_prior, 2 only_value).  temp [B]; have_walk: io.walk_u holds the walk's uniforms.
+static int ply_search(mz_engine *e, const PlyIO &io, int mode, int M, const double *temp, bool noise_on, bool have_noise,
+                      bool have_walk, uint64_t move, hipStream_t s) {
+  if (mz_initial_inference(e, io.obs, s)) return -1;
+  const bool given = noise_on && have_noise;
+  if (mz_root_prepare(e, io.to_play, io.legal, given ? io.noise : nullptr, noise_on && !given ? 1 : 0, move, s)) return -1;
+  if (mode != 0) return mz_eval_lookahead(e, mode, io.actions, io.pred_rewards, io.child_visits, nullptr, nullptr, s);
+  if (mz_search(e, e->sims, s)) return -1;
+  if (mz_eval_walk(e, M, temp, have_walk ? io.walk_u : nullptr, move, io.actions, io.pred_rewards, io.n_actions,
+                   io.path_lengths, s)) return -1;
+  return mz_finalize(e, nullptr, nullptr, move, nullptr, io.child_visits, io.root_value, nullptr, nullptr, s);
 }
 
 int mz_eval_env_reset(mz_engine *e, int kind, int max_steps, int time_limit, int random_opp, int keep_history, void *stream) {
   if (!e) return fail("mz_eval_env_reset: null engine");
   MZ_ENTER(e);
   if (kind < 1 || kind > 3) return fail("mz_eval_env_reset: kind must be 1 (TicTacToe), 2 (CartPole) or 3 (Connect Four), got %d", kind);
-  const char *why = nullptr;
-  if (eval_env_shape(e, kind, &why)) return fail("mz_eval_env_reset: %s", why);
+  if (game_shape(e, "mz_eval_env_reset", kind)) return -1;
   if (max_steps < 1) return fail("mz_eval_env_reset: max_steps must be >= 1");
   if (kind == 2 && time_limit < 1) return fail("mz_eval_env_reset: CartPole needs its time limit (>= 1)");
   if (random_opp < -1 || random_opp > 1) return fail("mz_eval_env_reset: random_opp must be -1, 0 (none) or +1");
   EvalState &es = e->ev;
-  const int longest = kind == 1 ? 9 : kind == 3 ? 42 : time_limit;
+  const int longest = kind == 2 ? time_limit : mz_game_info(kind).longest;
   const int cap = max_steps < longest ? max_steps : longest;
   const size_t nb = (size_t)e->B, A = (size_t)e->A, sims = (size_t)e->sims;
   hipStream_t s = (hipStream_t)stream;
@@ -120,19 +126,8 @@ int mz_eval_env_moves(mz_engine *e, int n, int mode, int max_actions, double tem
     const int move = (int)e->ev_moves;
     hipLaunchKernelGGL(k_eval_observe, grid, block, 0, s, es, B, e->O, A, M, move);
     HIPCHECK(hipGetLastError());
-    if (mz_initial_inference(e, es.obs, s)) return -1;
-    const bool given = noise_on && es.d_noise;
-    if (mz_root_prepare(e, es.to_play, es.legal, given ? es.noise : nullptr, noise_on && !given ? 1 : 0, (uint64_t)move, s))
+    if (ply_search(e, es, mode, M, es.temp, noise_on != 0, es.d_noise != nullptr, es.d_walk != nullptr, (uint64_t)move, s))
       return -1;
-    if (mode == 0) {
-      if (mz_search(e, e->sims, s)) return -1;
-      if (mz_eval_walk(e, M, es.temp, es.d_walk ? es.walk_u : nullptr, (uint64_t)move, es.actions, es.pred_rewards,
-                       es.n_actions, es.path_lengths, s)) return -1;
-      if (mz_finalize(e, nullptr, nullptr, (uint64_t)move, nullptr, es.child_visits, es.root_value, nullptr, nullptr, s))
-        return -1;
-    } else {
-      if (mz_eval_lookahead(e, mode, es.actions, es.pred_rewards, es.child_visits, nullptr, nullptr, s)) return -1;
-    }
     if (es.opp_playouts > 0 &&      // the opponent's move in the live games that are its to move, keyed by this move
         playout_launch(e, "mz_eval_env_moves", es.kind, es.board, es.turn, es.step, es.terminal, es.random_opp, B,
                        es.opp_playouts, (uint64_t)move, es.opp_action, nullptr, nullptr, s)) return -1;

@@ -3,18 +3,34 @@
 //
 //   k_eval_observe       from the games' state to the engine's obs / legal / to_play inputs, and the move's given draws
 //                        laid out for mz_root_prepare and mz_eval_walk, one thread per game
-//   k_eval_apply         evaluate.py:331-374 on the device environments -- the rule functions of mz_selfplay.hip.h, not
-//                        restated -- with the summary's accumulators and the optional per-move logs, one thread per game
+//   k_eval_apply         evaluate.py:331-374 on the device environments -- the games of mz_games.h, not restated -- with
+//                        the summary's accumulators and the optional per-move logs, one thread per game
 //
 // A separate header from mz_eval.hip.h, whose kernels are the walk and the lookahead every evaluation path shares.
 #pragma once
 #include "mz_common.h"
 #include "mz_rng.h"
-#include "mz_selfplay.hip.h"
+#include "mz_games.h"
+
+// The engine's inputs of one searched move and the outputs of its walk / lookahead / finalize: what ply_search
+// (mz_eval_abi.inc) runs over, for evaluation games and matches alike (a match takes one action per ply: M = 1).
+struct PlyIO {
+  float *obs;            // [Bp][O]
+  uint8_t *legal;        // [B][A]
+  int8_t *to_play;       // [B]
+  double *noise;         // [B][A] the move's given Dirichlet draws
+  double *walk_u;        // [B][M] the move's given walk uniforms
+  int32_t *actions;      // [B][M]
+  float *pred_rewards;   // [B][M]
+  int32_t *n_actions;    // [B]
+  int32_t *path_lengths; // [B][sims of the searching engine]
+  double *child_visits;  // [B][A]
+  double *root_value;    // [B]
+};
 
 // ---- evaluation games on the device environments (mz_eval_env_*): the game and everything the summary needs stay here
 // from the first move to the last.  Separate from SelfplayState: self-play on the same engine is untouched.
-struct EvalState {
+struct EvalState : PlyIO {
   int kind;              // 1 TicTacToe, 2 CartPole, 3 Connect Four (the numbering of mz_selfplay_set_env)
   int max_steps;         // evaluate.py:372: the game is cut when game.step reaches it
   int time_limit;        // CartPole: gym's TimeLimit (envs.CartPole.max_episode_steps)
@@ -35,19 +51,8 @@ struct EvalState {
   double *acc;
   int32_t *n_moves;      // [B] moves searched (the count of the value sums)
   int32_t *depth_max;    // [B][sims] the lexicographic maximum of the per-move lists of search depths (evaluate.py:102)
-  // the engine's inputs of the coming move (k_eval_observe) and the outputs of its walk / lookahead / finalize
-  float *obs;            // [Bp][O]
-  uint8_t *legal;        // [B][A]
-  int8_t *to_play;       // [B]
-  double *noise;         // [B][A] the move's given Dirichlet draws
-  double *walk_u;        // [B][M] the move's given walk uniforms
+  // (PlyIO: the engine's inputs of the coming move, laid out by k_eval_observe, and the search's outputs)
   double *temp;          // [B]
-  int32_t *actions;      // [B][M]
-  float *pred_rewards;   // [B][M]
-  int32_t *n_actions;    // [B]
-  int32_t *path_lengths; // [B][sims]
-  double *child_visits;  // [B][A]
-  double *root_value;    // [B]
   int walk_cap;          // M the walk buffers are sized for
   // draws given by the caller (mz_eval_env_set_draws; device memory the caller keeps alive), or null = the counter RNG
   const double *d_walk; int d_walk_moves, d_walk_m;       // [B][moves][M]
@@ -70,28 +75,10 @@ struct EvalState {
 static __global__ void k_eval_observe(EvalState es, int B, int O, int A, int M, int move) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float *obs = es.obs + (size_t)b * O;
   uint8_t *legal = es.legal + (size_t)b * A;
   const bool live = !es.terminal[b];
-  int to_play = 1;
-  if (!live) {
-    for (int k = 0; k < O; ++k) obs[k] = 0.f;
-    for (int a = 0; a < A; ++a) legal[a] = 1;
-  } else if (es.kind == 1) {
-    const int8_t *bd = es.board + (size_t)b * 42;
-    to_play = es.turn[b];
-    for (int k = 0; k < 9; ++k) {
-      obs[k] = (float)(to_play * (int)bd[k]);
-      legal[k] = bd[k] == 0 ? 1 : 0;
-    }
-  } else if (es.kind == 3) {
-    const uint32_t mask = mz_c4_view(es.board + (size_t)b * 42, (int)es.turn[b], obs, &to_play);
-    for (int a = 0; a < A; ++a) legal[a] = (uint8_t)((mask >> a) & 1u);
-  } else {
-    for (int k = 0; k < 4; ++k) obs[k] = (float)es.cart[(size_t)b * 4 + k];
-    for (int a = 0; a < A; ++a) legal[a] = 1;
-  }
-  es.to_play[b] = (int8_t)to_play;
+  es.to_play[b] = (int8_t)mz_game_observe(es.kind, es.board + (size_t)b * 42, (int)es.turn[b], es.cart + (size_t)b * 4, live,
+                                          O, A, es.obs + (size_t)b * O, legal);
   if (es.d_noise) {
     const bool have = live && move < es.d_noise_moves;
     const double *src = es.d_noise + ((size_t)b * es.d_noise_moves + (have ? move : 0)) * A;
@@ -130,9 +117,9 @@ static __global__ void k_eval_apply(EvalState es, const float *net_value, int B,
     for (int a = 0; a < A; ++a) es.log_child_visits[((size_t)b * cap + mv) * A + a] = es.child_visits[(size_t)b * A + a];
   }
   // (2) the walked actions
-  const uint8_t *legal = es.legal + (size_t)b * A;      // the legal list of the move's ROOT position (the reference's stale list)
-  int nlegal = 0;
-  for (int a = 0; a < A; ++a) nlegal += legal[a] ? 1 : 0;
+  uint32_t legal = 0;      // the legal actions of the move's ROOT position (the reference's stale list)
+  for (int a = 0; a < A; ++a) legal |= (es.legal[(size_t)b * A + a] ? 1u : 0u) << a;
+  const int nlegal = __builtin_popcount(legal);
   const int nact = mode == 0 ? es.n_actions[b] : 1;
   int step = es.step[b], turn = es.two_players ? (int)es.turn[b] : 1;
   double sum_reward = *acc_reward, sum_pred = *acc_pred_reward;
@@ -147,8 +134,7 @@ static __global__ void k_eval_apply(EvalState es, const float *net_value, int B,
     if (opp && nlegal > 0) {
       int idx;
       if (es.opp_action) {      // the playout opponent's plan for this position (M == 1: the root position is the game's)
-        idx = 0;
-        for (int a = 0, want = es.opp_action[b]; a < want && a < A; ++a) idx += legal[a] ? 1 : 0;
+        idx = __builtin_popcount(legal & ((1u << es.opp_action[b]) - 1u));
       } else if (es.d_opp) {
         const int pos = es.opp_pos[b];
         idx = pos < es.d_opp_n ? es.d_opp[(size_t)b * es.d_opp_n + pos] : 0;
@@ -158,15 +144,12 @@ static __global__ void k_eval_apply(EvalState es, const float *net_value, int B,
                                   (MZ_RNG_OPP << 24) | ((uint32_t)j & 0xFFFFFFu));
         idx = (int)(mz_u01(r.x, r.y) * (double)nlegal);
       }
-      idx = idx < 0 ? 0 : (idx > nlegal - 1 ? nlegal - 1 : idx);
-      for (int a = 0; a < A; ++a)
-        if (legal[a] && idx-- == 0) { action = a; break; }
+      action = mz_pick_legal(legal, idx);
     }
     if (action < 0 || action >= A) break;      // (the walk never hands one out; no cell outside the board is ever touched)
     bool done, won = false;
-    if (es.kind == 1) done = mz_ttt_step(es.board + (size_t)b * 42, turn, action, step, &won);
-    else if (es.kind == 3) done = mz_c4_step(es.board + (size_t)b * 42, turn, action, &won);
-    else done = mz_cartpole_step(es.cart + (size_t)b * 4, action) || step + 1 >= es.time_limit;
+    if (es.kind == 2) done = mz_cartpole_step(es.cart + (size_t)b * 4, action) || step + 1 >= es.time_limit;
+    else done = mz_game_step(es.kind, es.board + (size_t)b * 42, turn, action, step, &won);
     double reward = es.kind == 2 ? 1.0 : (won ? 1.0 : 0.0);
     if (es.two_players) turn = -turn;
     const int at = step;
@@ -191,17 +174,7 @@ static __global__ void k_eval_apply(EvalState es, const float *net_value, int B,
   int32_t *dm = es.depth_max + (size_t)b * sims;
   if (mode == 0) {
     const int32_t *pl = es.path_lengths + (size_t)b * sims;
-    bool greater = mv == 0;
-    for (int s = 0; s < sims && !greater; ++s) {
-      if (pl[s] == dm[s]) continue;
-      greater = pl[s] > dm[s];
-      break;
-    }
-    if (greater) {
-      long sum = 0;
-      for (int s = 0; s < sims; ++s) { dm[s] = pl[s]; sum += pl[s]; }
-      *acc_depth = (double)sum / (double)sims;
-    }
+    mz_depth_list_max(dm, pl, sims, mv == 0, acc_depth);
     if (logs)
       for (int s = 0; s < sims; ++s) es.log_depths[((size_t)b * cap + mv) * sims + s] = pl[s];
   } else if (mv == 0) {

@@ -421,7 +421,7 @@ int mz_fcl_set_symmetry(mz_fcl *c, int kind, uint64_t seed, uint32_t first_updat
   if (kind != 0 && sym_elements(kind) == 0) return fail("mz_fcl_set_symmetry: unknown kind %d (0 off, 1 TicTacToe, 3 Connect Four)", kind);
   if (kind != 0 && (c->O != sym_cells(kind) || c->A != sym_actions(kind)))
     return fail("mz_fcl_set_symmetry: %s has obs_dim %d and action_space %d, the handle was created with %d and %d",
-                kind == 1 ? "TicTacToe" : "Connect Four", sym_cells(kind), sym_actions(kind), c->O, c->A);
+                mz_game_info(kind).name, sym_cells(kind), sym_actions(kind), c->O, c->A);
   if (kind != 0 && !c->sym_d) {
     // ONE buffer for every update of the handle, however many mz_fcl_run keeps in flight: an update's symmetry kernel and the step
     // kernels that read its output are enqueued on the same stream, and so are the next update's, so the next image is written only

@@ -547,10 +547,10 @@ __host__ __device__ inline size_t mz_fused_dyn_lds(int sims, int NN, int lt) {
 // Game.store_search_statistics, root error, Game.apply on the synthetic env and the experience record
 // (the stand-alone k_env_step_record does the same from the global pool).  Lane a stages child a's visit count
 // in LDS, lane 0 then runs the reference's sequential arithmetic (mz_sample_index) on the staged vector.
-// GAME 1: the environment is the device TicTacToe (mz_ttt_apply) instead of the synthetic one; the uniform may be the host's.
+// GAME 1: the environment is the device TicTacToe (mz_board_apply<1>) instead of the synthetic one; the uniform may be the host's.
 // GAME 2: the device CartPole (mz_cartpole_apply) on the four float64 state words of envs[8..15]; the record's observation
 // is their float cast, read by lanes 0..3 before lane 0 steps them.
-// GAME 3: the device Connect Four (mz_c4_apply), kind 1's sequence on the global board; the uniform is the device's.
+// GAME 3: the device Connect Four (mz_board_apply<3>), kind 1's sequence on the global board; the uniform is the device's.
 template <int TL, int LT, int GAME = 0>
 __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const TreeMem<LT> &tm, const SelfplayState &sp,
                                                    int b, int lane, uint32_t legal, uint64_t seed, double *stage,
@@ -588,12 +588,12 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
     const int idx = mz_sample_index(d, n, envs ? *(const double *)(envs + 4) : sp.temp[b], u);
     const int action = acts[idx];
     if constexpr (GAME == 1) {
-      mz_ttt_apply(sp, b, action, rv, err, rec, A);
+      mz_board_apply<1>(sp, b, action, rv, err, rec, A);
       sp.movecnt[b] = move + 1ull;
       return;
     }
     if constexpr (GAME == 3) {
-      mz_c4_apply(sp, b, action, rv, err, rec, A);
+      mz_board_apply<3>(sp, b, action, rv, err, rec, A);
       sp.movecnt[b] = move + 1ull;
       return;
     }
@@ -654,10 +654,10 @@ struct MzRootArgs {
 // root and search, and the resident weight steps are loaded once per launch instead of once per move.  The
 // workgroups drift apart freely: nothing is exchanged between them.
 // GAME (HEAD only): the moves are those of a device game environment; its kind (SelfplayState::env_kind) is GK below.
-// 1 (two players): the device TicTacToe environment (mz_root_body<.., GK>, mz_ttt_apply).
+// 1 (two players): the device TicTacToe environment (mz_root_body<.., GK>, mz_board_apply<1>).
 // 2 (single player): the device CartPole environment (mz_cartpole_apply); its four float64 state words live in words 8..15
 // of the workgroup's LDS environment rows across the moves of the launch.
-// 3 (two players): the device Connect Four environment (mz_c4_apply): kind 1's two-player branches, its own observation,
+// 3 (two players): the device Connect Four environment (mz_board_apply<3>): kind 1's two-player branches, its own observation,
 // legal mask and rules; like kind 1 it keeps board, turn, step and episode in global memory, current after every move.
 // The kernel's template list stays as it is -- every compiled kernel keeps its symbol, which the profiles and
 // tests/test_abi.py name -- so the kind is decoded from what the game kernels differ in: the players, and between the two

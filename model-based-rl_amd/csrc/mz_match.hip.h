@@ -4,7 +4,7 @@
 //
 //   k_match_open         the opening plies, applied with no inference: the min(floor(u * n), n - 1)-th legal action
 //   k_match_observe      from the games' state to the engines' obs / legal / to_play inputs and the ply's given draws
-//   k_match_apply        the mover's one action on the rules of mz_selfplay.hip.h (not restated), the per-network
+//   k_match_apply        the mover's one action on the games of mz_games.h (not restated), the per-network
 //                        accumulators and the optional per-ply logs
 //   k_match_temperature  the two sides' temperatures, [2][B]
 //
@@ -14,10 +14,11 @@
 #include "mz_common.h"
 #include "mz_rng.h"
 #include <vector>
-#include "mz_selfplay.hip.h"
+#include "mz_games.h"
+#include "mz_eval_env.hip.h"      // (PlyIO)
 
 // Separate from EvalState and SelfplayState: evaluation and self-play on the two engines are untouched.
-struct MatchState {
+struct MatchState : PlyIO {
   int kind;              // 1 TicTacToe, 3 Connect Four (the numbering of mz_selfplay_set_env)
   int max_steps;         // the game is cut (a draw) when its step count reaches it
   int cap;               // capacity of the per-ply logs: min(max_steps, the game's own longest)
@@ -35,19 +36,8 @@ struct MatchState {
   double *acc;
   int32_t *n_searched;   // [2][B] plies that network searched
   int32_t *depth_max;    // [2][B][S] the lexicographic maximum of its per-ply lists of search depths
-  // the mover engine's inputs of the coming ply (k_match_observe) and the outputs of its walk / lookahead / finalize
-  float *obs;            // [Bp][O]
-  uint8_t *legal;        // [B][A]
-  int8_t *to_play;       // [B]
-  double *noise;         // [B][A] the ply's given Dirichlet draws
-  double *walk_u;        // [B] the ply's given walk uniform
+  // (PlyIO, M = 1: the mover engine's inputs of the coming ply, laid out by k_match_observe, and the search's outputs)
   double *temp;          // [2][B] per network
-  int32_t *actions;      // [B]
-  float *pred_rewards;   // [B]
-  int32_t *n_actions;    // [B]
-  int32_t *path_lengths; // [B][sims of the mover's engine]
-  double *child_visits;  // [B][A]
-  double *root_value;    // [B]
   // draws given by the caller (mz_match_set_draws; device memory the caller keeps alive), or null = the counter RNG
   const double *d_walk; int d_walk_plies;       // [B][plies][1], indexed by the ply (opening plies counted)
   const double *d_noise; int d_noise_plies;     // [B][plies][A]
@@ -57,18 +47,6 @@ struct MatchState {
   float *log_pred_value; double *log_root_value; double *log_child_visits; int32_t *log_depths;
 };
 
-// The legal actions of game b's position as a mask, from the board alone.
-__host__ __device__ inline uint32_t mz_match_legal(const MatchState &ms, int b) {
-  const int8_t *bd = ms.board + (size_t)b * 42;
-  if (ms.kind == 3) {
-    int tp;
-    return mz_c4_view(bd, (int)ms.turn[b], nullptr, &tp);
-  }
-  uint32_t mask = 0;
-  for (int k = 0; k < 9; ++k) mask |= (bd[k] == 0 ? 1u : 0u) << k;
-  return mask;
-}
-
 // env.step(action) of game b for the player about to move, and everything that follows from it for the game: the step
 // count, the turn, the per-ply logs of the action, and at the end of the game (the rules' done, or the cut at max_steps)
 // the result for player +1.  Returns whether the game ended.  The caller has checked that the game is live, step < cap
@@ -77,7 +55,7 @@ __host__ __device__ inline bool mz_match_step_game(const MatchState &ms, int b, 
   const int step = ms.step[b], mover = (int)ms.turn[b];
   int8_t *bd = ms.board + (size_t)b * 42;
   bool won = false;
-  const bool done = ms.kind == 1 ? mz_ttt_step(bd, mover, action, step, &won) : mz_c4_step(bd, mover, action, &won);
+  const bool done = mz_game_step(ms.kind, bd, mover, action, step, &won);
   ms.turn[b] = (int8_t)-mover;
   ms.step[b] = step + 1;
   if (ms.log_action) {
@@ -103,9 +81,8 @@ __host__ __device__ inline bool mz_match_step_game(const MatchState &ms, int b, 
 __host__ __device__ inline bool mz_match_open_game(const MatchState &ms, int b, int A, uint64_t seed, uint32_t env) {
   for (int p = 0; p < ms.opening; ++p) {
     if (ms.terminal[b] || ms.step[b] >= ms.cap) return false;
-    const uint32_t mask = mz_match_legal(ms, b);
-    int n = 0;
-    for (int a = 0; a < A; ++a) n += (int)((mask >> a) & 1u);
+    const uint32_t mask = mz_game_legal(ms.kind, ms.board + (size_t)b * 42);
+    const int n = __builtin_popcount(mask);
     if (n == 0) return false;      // (unreachable: a live game has a legal action)
     int idx;
     if (ms.d_open) {
@@ -114,11 +91,7 @@ __host__ __device__ inline bool mz_match_open_game(const MatchState &ms, int b, 
       const mz_u4 r = mz_philox(seed, env, (uint32_t)p, 0u, MZ_RNG_OPEN << 24);
       idx = (int)(mz_u01(r.x, r.y) * (double)n);
     }
-    idx = idx < 0 ? 0 : (idx > n - 1 ? n - 1 : idx);
-    int action = 0;
-    for (int a = 0; a < A; ++a)
-      if (((mask >> a) & 1u) && idx-- == 0) { action = a; break; }
-    if (mz_match_step_game(ms, b, action, -1, 0.f)) return true;
+    if (mz_match_step_game(ms, b, mz_pick_legal(mask, idx), -1, 0.f)) return true;
   }
   return false;
 }
@@ -127,25 +100,10 @@ __host__ __device__ inline bool mz_match_open_game(const MatchState &ms, int b, 
 // finished game gets a zero observation, all actions legal and to_play +1 (as k_eval_observe feeds it).  The ply's given
 // draws are laid out for mz_root_prepare ([B][A], zero at illegal actions) and mz_eval_walk ([B]).
 __host__ __device__ inline void mz_match_observe_game(const MatchState &ms, int b, int O, int A, int ply) {
-  float *obs = ms.obs + (size_t)b * O;
   uint8_t *legal = ms.legal + (size_t)b * A;
   const bool live = !ms.terminal[b];
-  int to_play = 1;
-  if (!live) {
-    for (int k = 0; k < O; ++k) obs[k] = 0.f;
-    for (int a = 0; a < A; ++a) legal[a] = 1;
-  } else if (ms.kind == 1) {
-    const int8_t *bd = ms.board + (size_t)b * 42;
-    to_play = ms.turn[b];
-    for (int k = 0; k < 9; ++k) {
-      obs[k] = (float)(to_play * (int)bd[k]);
-      legal[k] = bd[k] == 0 ? 1 : 0;
-    }
-  } else {
-    const uint32_t mask = mz_c4_view(ms.board + (size_t)b * 42, (int)ms.turn[b], obs, &to_play);
-    for (int a = 0; a < A; ++a) legal[a] = (uint8_t)((mask >> a) & 1u);
-  }
-  ms.to_play[b] = (int8_t)to_play;
+  ms.to_play[b] = (int8_t)mz_game_observe(ms.kind, ms.board + (size_t)b * 42, (int)ms.turn[b], nullptr, live, O, A,
+                                          ms.obs + (size_t)b * O, legal);
   if (ms.d_noise) {
     const bool have = live && ply < ms.d_noise_plies;
     const double *src = ms.d_noise + ((size_t)b * ms.d_noise_plies + (have ? ply : 0)) * A;
@@ -189,17 +147,7 @@ __host__ __device__ inline bool mz_match_apply_game(const MatchState &ms, int b,
   int32_t *dm = ms.depth_max + ((size_t)net * B + b) * S;
   if (mode == 0) {
     const int32_t *pl = ms.path_lengths + (size_t)b * sims;
-    bool greater = searched == 0;
-    for (int s = 0; s < sims && !greater; ++s) {
-      if (pl[s] == dm[s]) continue;
-      greater = pl[s] > dm[s];
-      break;
-    }
-    if (greater) {
-      long sum = 0;
-      for (int s = 0; s < sims; ++s) { dm[s] = pl[s]; sum += pl[s]; }
-      acc[(size_t)3 * B] = (double)sum / (double)sims;
-    }
+    mz_depth_list_max(dm, pl, sims, searched == 0, acc + (size_t)3 * B);
     if (logs)
       for (int s = 0; s < sims; ++s) ms.log_depths[at * S + s] = pl[s];
   } else {

@@ -32,8 +32,7 @@ int mz_match_create(mz_engine *e0, mz_engine *e1, int kind, int max_steps, int k
     return fail("mz_match_create: the two engines have different shapes (obs_dim %d / %d, action_space %d / %d)", e0->O, e1->O, e0->A, e1->A);
   if (e0->cfg.seed != e1->cfg.seed || e0->cfg.env_id_offset != e1->cfg.env_id_offset)
     return fail("mz_match_create: the two engines key their draws differently (seed and env_id_offset must be equal)");
-  const char *why = nullptr;
-  if (eval_env_shape(e0, kind, &why)) return fail("mz_match_create: %s", why);
+  if (game_shape(e0, "mz_match_create", kind)) return -1;
   if (max_steps < 1) return fail("mz_match_create: max_steps must be >= 1");
   MZ_ENTER(e0);
   mz_match *m = new mz_match();
@@ -42,7 +41,7 @@ int mz_match_create(mz_engine *e0, mz_engine *e1, int kind, int max_steps, int k
   m->keep = keep_history != 0;
   MatchState &ms = m->ms;
   memset(&ms, 0, sizeof ms);
-  const int longest = kind == 1 ? 9 : 42;
+  const int longest = mz_game_info(kind).longest;
   ms.kind = kind; ms.max_steps = max_steps; ms.cap = max_steps < longest ? max_steps : longest;
   ms.S = e0->sims > e1->sims ? e0->sims : e1->sims;
   const size_t nb = (size_t)m->B, A = (size_t)m->A, S = (size_t)ms.S;
@@ -154,19 +153,8 @@ int mz_match_plies(mz_match *m, int n, const int *mode, const double *temperatur
     const int md = mode[net];
     hipLaunchKernelGGL(k_match_observe, grid, block, 0, s, ms, B, m->O, A, ply);
     HIPCHECK(hipGetLastError());
-    if (mz_initial_inference(e, ms.obs, s)) return -1;
-    const bool given = noise_on[net] && ms.d_noise;
-    if (mz_root_prepare(e, ms.to_play, ms.legal, given ? ms.noise : nullptr, noise_on[net] && !given ? 1 : 0, (uint64_t)ply, s))
-      return -1;
-    if (md == 0) {
-      if (mz_search(e, e->sims, s)) return -1;
-      if (mz_eval_walk(e, 1, ms.temp + (size_t)net * B, ms.d_walk ? ms.walk_u : nullptr, (uint64_t)ply, ms.actions,
-                       ms.pred_rewards, ms.n_actions, ms.path_lengths, s)) return -1;
-      if (mz_finalize(e, nullptr, nullptr, (uint64_t)ply, nullptr, ms.child_visits, ms.root_value, nullptr, nullptr, s))
-        return -1;
-    } else {
-      if (mz_eval_lookahead(e, md, ms.actions, ms.pred_rewards, ms.child_visits, nullptr, nullptr, s)) return -1;
-    }
+    if (ply_search(e, ms, md, 1, ms.temp + (size_t)net * B, noise_on[net] != 0, ms.d_noise != nullptr, ms.d_walk != nullptr,
+                   (uint64_t)ply, s)) return -1;
     hipLaunchKernelGGL(k_match_apply, grid, block, 0, s, ms, (const float *)e->tv.root_value, B, A, net, md, e->sims);
     HIPCHECK(hipGetLastError());
     m->plies += 1;

@@ -9,12 +9,12 @@
 // and mz_playout_plan_host (include/mz_engine_debug.h) runs them with the lanes looped on the host, bit for bit the
 // device's plan.  Only po_evaluate's reduction over the lanes differs between the two (wave ballots / a loop).
 //
-// The rules are mz_ttt_step / mz_c4_step / mz_c4_view's mask of mz_selfplay.hip.h and nothing else (no second form).
+// The rules are mz_game_step / mz_game_legal / mz_nth_legal of mz_games.h and nothing else (no second form).
 #pragma once
 #include <math.h>
 #include "mz_common.h"
 #include "mz_rng.h"
-#include "mz_selfplay.hip.h"
+#include "mz_games.h"
 
 #define MZ_PO_LANES 64
 #define MZ_PO_MIN_PLAYOUTS 64
@@ -66,22 +66,12 @@ __host__ __device__ inline void po_carve(unsigned char *mem, int nodes, int A, P
   *root = (int8_t *)(mem + lanes + (size_t)MZ_PO_LANES * MZ_PO_BOARD_STRIDE);
 }
 
-// ---- the rules: the two step functions and the legal masks, nothing restated
-__host__ __device__ inline uint32_t po_legal(int kind, const int8_t *bd) {
-  if (kind == 3) { int tp; return mz_c4_view(bd, 1, nullptr, &tp); }
-  uint32_t m = 0;
-  for (int k = 0; k < 9; ++k) m |= (bd[k] == 0 ? 1u : 0u) << k;
-  return m;
-}
+// ---- the rules, under the planner's names: the shared functions of mz_games.h, nothing restated
+__host__ __device__ inline uint32_t po_legal(int kind, const int8_t *bd) { return mz_game_legal(kind, bd); }
 __host__ __device__ inline bool po_step(int kind, int8_t *bd, int turn, int action, int t, bool *won) {
-  return kind == 3 ? mz_c4_step(bd, turn, action, won) : mz_ttt_step(bd, turn, action, t, won);
+  return mz_game_step(kind, bd, turn, action, t, won);
 }
-// the i-th legal action in ascending order (0 where the mask has no such bit: never asked for)
-__host__ __device__ inline int po_nth(uint32_t mask, int i) {
-  for (int a = 0; a < 9; ++a)
-    if (((mask >> a) & 1u) && i-- == 0) return a;
-  return 0;
-}
+__host__ __device__ inline int po_nth(uint32_t mask, int i) { return mz_nth_legal(mask, i); }
 
 // ---- one lane's playout from a fresh node: `first` by the node's mover `turn` (t plies played before it), then uniformly
 // random legal moves to the end.  Byte j of the 16 bytes of Philox call c (x, y, z, w, each low byte first) serves random

@@ -5,17 +5,17 @@
 static int playout_check(const char *fn, int kind, int A, int playouts, const int8_t *boards, const int8_t *turn,
                          const int32_t *step, int n_games) {
   if (kind != 1 && kind != 3) return fail("%s: kind must be 1 (TicTacToe) or 3 (Connect Four), got %d", fn, kind);
-  if (A != (kind == 1 ? 9 : 7)) return fail("%s: %s has %d actions, got %d", fn, kind == 1 ? "TicTacToe" : "Connect Four", kind == 1 ? 9 : 7, A);
+  const MzGameInfo g = mz_game_info(kind);
+  if (A != g.actions) return fail("%s: %s has %d actions, got %d", fn, g.name, g.actions, A);
   if (playouts < MZ_PO_MIN_PLAYOUTS || playouts > MZ_PO_MAX_PLAYOUTS || playouts % MZ_PO_LANES)
     return fail("%s: playouts must be a multiple of 64 in 64 .. 65536, got %d", fn, playouts);
   if (n_games < 0) return fail("%s: n_games must be >= 0, got %d", fn, n_games);
   if (n_games && (!boards || !turn || !step)) return fail("%s: null position array", fn);
-  const int cells = kind == 1 ? 9 : 42;
   for (int i = 0; i < n_games; ++i) {
     const int8_t *bd = boards + (size_t)i * 42;
     int stones = 0;
     for (int k = 0; k < 42; ++k) {
-      if (bd[k] < -1 || bd[k] > 1 || (k >= cells && bd[k] != 0))
+      if (bd[k] < -1 || bd[k] > 1 || (k >= g.cells && bd[k] != 0))
         return fail("%s: position %d is not a board of the game (cell %d holds %d)", fn, i, k, (int)bd[k]);
       stones += bd[k] != 0 ? 1 : 0;
     }
@@ -54,7 +54,7 @@ static int playout_ready(mz_engine *e, hipStream_t s) {
 static int playout_launch(mz_engine *e, const char *fn, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step,
                           const uint8_t *terminal, int only_mover, int n, int playouts, uint64_t move, int32_t *action,
                           int32_t *visits, int32_t *wins, hipStream_t s) {
-  const int iters = playouts / MZ_PO_LANES, A = kind == 1 ? 9 : 7;
+  const int iters = playouts / MZ_PO_LANES, A = mz_game_info(kind).actions;
   const size_t per_wave = po_wave_bytes(iters + 1, A);
   if (per_wave > (size_t)MZ_LDS_BYTES) return fail("%s: a tree of %d nodes does not fit the LDS", fn, iters + 1);
   const int waves = 4 * per_wave <= 65536 ? 4 : (2 * per_wave <= 65536 ? 2 : 1);      // per block; no more LDS than one wave needs above 64 KiB
@@ -76,9 +76,7 @@ int mz_playout_plan(mz_engine *e, int kind, const int8_t *boards, const int8_t *
   if (!e) return fail("mz_playout_plan: null engine");
   MZ_ENTER(e);
   if (kind != 1 && kind != 3) return fail("mz_playout_plan: kind must be 1 (TicTacToe) or 3 (Connect Four), got %d", kind);
-  if (e->O != (kind == 1 ? 9 : 42) || e->A != (kind == 1 ? 9 : 7) || !e->cfg.two_players)
-    return fail("mz_playout_plan: %s", kind == 1 ? "TicTacToe needs obs_dim 9, action_space 9, two_players"
-                                                 : "Connect Four needs obs_dim 42, action_space 7, two_players");
+  if (game_shape(e, "mz_playout_plan", kind)) return -1;
   if (n_games > e->B) return fail("mz_playout_plan: n_games %d exceeds the engine's num_envs %d", n_games, e->B);
   if (playout_check("mz_playout_plan", kind, e->A, playouts, boards, turn, step, n_games)) return -1;
   if (n_games == 0) return 0;

@@ -12,7 +12,7 @@
 // Between the two run mz_initial_inference, mz_root_prepare (no noise) and mz_search, unchanged.
 #pragma once
 #include "mz_common.h"
-#include "mz_selfplay.hip.h"
+#include "mz_tree.hip.h"
 
 // Separate from SelfplayState / EvalState / MatchState: self-play, evaluation and matches on the same engine are untouched.
 struct ReanalyseState {

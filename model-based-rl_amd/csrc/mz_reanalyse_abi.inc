@@ -3,14 +3,6 @@
 // engine's current weights, chunk by chunk, and the fresh child_visits / root_value come back in the layout mzr_reanalyse_write
 // takes.  Like mz_eval_env_moves / mz_match_plies: whole chunks are enqueued, the host touches nothing in between.
 
-static int reanalyse_shape(const mz_engine *e, int kind, const char **why) {
-  const bool two = e->cfg.two_players != 0;
-  if (kind == 1 && (e->O != 9 || e->A != 9 || !two)) { *why = "TicTacToe needs obs_dim 9, action_space 9, two_players"; return -1; }
-  if (kind == 2 && (e->O != 4 || e->A != 2 || two)) { *why = "CartPole needs obs_dim 4, action_space 2, a single player"; return -1; }
-  if (kind == 3 && (e->O != 42 || e->A != 7 || !two)) { *why = "Connect Four needs obs_dim 42, action_space 7, two_players"; return -1; }
-  return 0;
-}
-
 int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
                  int num_simulations, void *stream) {
   if (!e) return fail("mz_reanalyse: null engine");
@@ -20,8 +12,7 @@ int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats,
     return fail("mz_reanalyse: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, e->O + e->A + MZ_REC_EXTRA);
   if (kind < 0 || kind > 3)
     return fail("mz_reanalyse: kind must be 0 (synthetic), 1 (TicTacToe), 2 (CartPole) or 3 (Connect Four), got %d", kind);
-  const char *why = nullptr;
-  if (reanalyse_shape(e, kind, &why)) return fail("mz_reanalyse: %s", why);
+  if (kind != 0 && game_shape(e, "mz_reanalyse", kind)) return -1;
   if (n_rows < 0) return fail("mz_reanalyse: n_rows must be >= 0, got %d", n_rows);
   if (num_simulations < 1 || num_simulations > e->sims)
     return fail("mz_reanalyse: num_simulations must be in 1 .. %d (the engine's pool), got %d", e->sims, num_simulations);

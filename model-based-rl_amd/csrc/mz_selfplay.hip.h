@@ -5,6 +5,7 @@
 #include "mz_common.h"
 #include "mz_rng.h"
 #include "mz_tree.hip.h"
+#include "mz_games.h"
 
 struct SelfplayState {
   int episode_len;
@@ -147,144 +148,65 @@ static __global__ void k_env_step_record(TreeView tv, SelfplayState sp, int B, i
   }
 }
 
-
-// ---- TicTacToe on the device (custom_environments/tic_tac_toe.py:5-76; the reference's only two-player environment)
-// What Actor.play_game reads before a move (actors.py:134-142): observation = turn * board as float32
-// (tic_tac_toe.py:24,50 + actors.py:134), the legal actions (tic_tac_toe.py:27-28) and game.to_play.
-static __global__ void k_ttt_observe(SelfplayState sp, int B, int A) {
+// ---- a real game as the environment (mz_selfplay_set_env; the games themselves: mz_games.h).  TicTacToe keeps its board
+// at stride 9 here, Connect Four at stride 42: the stride is the kind's cells.
+// What Actor.play_game reads before a move (actors.py:134-142): the observation, the legal actions and game.to_play.
+static __global__ void k_game_observe(SelfplayState sp, int B, int O, int A) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const int turn = sp.turn[b];
-  for (int k = 0; k < 9; ++k) {
-    const int c = sp.board[(size_t)b * 9 + k];
-    sp.obs[(size_t)b * 9 + k] = (float)(turn * c);
-    sp.legal[(size_t)b * A + k] = c == 0 ? 1 : 0;
-  }
-  sp.to_play[b] = (int8_t)turn;
+  const int kind = sp.env_kind;
+  const bool cart = kind == 2;
+  sp.to_play[b] = (int8_t)mz_game_observe(kind, cart ? nullptr : sp.board + (size_t)b * mz_game_info(kind).cells,
+                                          cart ? 1 : (int)sp.turn[b], cart ? sp.cart + (size_t)b * 4 : nullptr, true, O, A,
+                                          sp.obs + (size_t)b * O, sp.legal + (size_t)b * A);
 }
 
-// env.step(action) (tic_tac_toe.py:30-51) for the mover `turn` on bd[9], t = the elapsed steps before this move: the mark
-// goes on the cell; *won = a line through it sums to 3 * turn; returns done = won or the ninth move (tic_tac_toe.py:37).
-// The one statement of the rules every device form calls.
-__host__ __device__ inline bool mz_ttt_step(int8_t *bd, int turn, int action, int t, bool *won) {
-  bd[action] = (int8_t)turn;
-  const int r0 = 3 * (action / 3), c0 = action % 3;
-  bool w = (bd[r0] + bd[r0 + 1] + bd[r0 + 2] == 3 * turn) || (bd[c0] + bd[c0 + 3] + bd[c0 + 6] == 3 * turn);
-  if (action % 4 == 0) w = w || (bd[0] + bd[4] + bd[8] == 3 * turn);
-  if (action == 2 || action == 4 || action == 6) w = w || (bd[2] + bd[4] + bd[6] == 3 * turn);
-  *won = w;
-  return w || t == 8;
-}
-
-// Game.apply (game.py:79-104) on env.step (tic_tac_toe.py:30-51) for environment b, by ONE lane, and the tail of its
-// experience record (root value, error, reward, action, flags with the mover, step, env id, episode).
-__device__ __forceinline__ void mz_ttt_apply(const SelfplayState &sp, int b, int action, double root_value, double error,
-                                             float *rec, int A) {
-  const int O = 9;
+// Game.apply (game.py:79-104) on env.step of the board game KIND (1 TicTacToe, tic_tac_toe.py:30-51; 3 Connect Four) for
+// environment b, by ONE lane, and the tail of its experience record (root value, error, reward, action, flags with the
+// mover, step, env id, episode).  On done run_selfplay starts a new Game: env.reset (tic_tac_toe.py:20-25) clears the
+// board, the turn is +1, the step 0, the episode advances and the next game's temperature is evaluated now.
+template <int KIND>
+__device__ __forceinline__ void mz_board_apply(const SelfplayState &sp, int b, int action, double root_value, double error,
+                                               float *rec, int A) {
+  constexpr int O = mz_game_info(KIND).cells;
   const int turn = sp.turn[b], t = sp.t[b], ep = sp.episode[b];
-  int8_t *bd = sp.board + (size_t)b * 9;
+  int8_t *bd = sp.board + (size_t)b * O;
   bool won;
-  const int done = mz_ttt_step(bd, turn, action, t, &won) ? 1 : 0;
+  const int done = mz_game_step(KIND, bd, turn, action, t, &won) ? 1 : 0;
   mz_rec_put_double(rec + O + A + 0, root_value);
   mz_rec_put_double(rec + O + A + 2, error);
   rec[O + A + 4] = won ? 1.f : 0.f;
   int32_t *ri = (int32_t *)(rec + O + A + 5);
   ri[0] = action; ri[1] = done | (turn < 0 ? 2 : 0); ri[2] = t; ri[3] = sp.env_offset + b; ri[4] = ep;
-  if (done) {      // run_selfplay starts a new Game: env.reset (tic_tac_toe.py:20-25), its temperature evaluated now
-    for (int k = 0; k < 9; ++k) bd[k] = 0;
+  if (done) {
+    for (int k = 0; k < O; ++k) bd[k] = 0;
     sp.turn[b] = 1; sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next;
   } else {
     sp.turn[b] = (int8_t)(-turn); sp.t[b] = t + 1;
   }
 }
 
-// End of a move: Config.select_action + store_search_statistics + root error (mz_finalize_tree), then Game.apply
-// (game.py:79-104) on env.step (tic_tac_toe.py:30-51): the mover's mark goes on the board; the move wins if a line
-// through it sums to +-3 (reward 1 for the mover), the game is done on a win or after the ninth move; the turn flips.
-// The record carries the mover in its flags word (to_play), as History.to_play does.
-static __global__ void k_ttt_step_record(TreeView tv, SelfplayState sp, int B, int A, uint64_t seed) {
+// End of a move of the launch-per-step form: Config.select_action + store_search_statistics + root error
+// (mz_finalize_tree), the record (pre-step observation), then Game.apply on the board game: the mover's mark goes on the
+// board; a winning move has reward 1 for the mover; the turn flips.  The record carries the mover in its flags word
+// (to_play), as History.to_play does.  Only TicTacToe takes the host's uniform (mz_selfplay_set_draws).
+template <int KIND>
+static __global__ void k_board_step_record(TreeView tv, SelfplayState sp, int B, int A, uint64_t seed) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const unsigned long long move = sp.movecnt[b];
   sp.movecnt[b] = move + 1ull;
-  mz_finalize_tree(tv, b, sp.temp, sp.draw_uniform, seed, move, sp.env_offset, sp.action, sp.child_visits, sp.root_value,
-                   sp.error, nullptr);
-  const int O = 9;
+  mz_finalize_tree(tv, b, sp.temp, KIND == 1 ? sp.draw_uniform : nullptr, seed, move, sp.env_offset, sp.action, sp.child_visits,
+                   sp.root_value, sp.error, nullptr);
+  constexpr int O = mz_game_info(KIND).cells;
   float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
   for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
   for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
-  mz_ttt_apply(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A);
+  mz_board_apply<KIND>(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A);
 }
 
 
-// ---- CartPole on the device (envs.CartPole is the definition; gym's CartPole-v1 / -v0 with its TimeLimit folded in).
-// sin / cos of the pole angle: fixed Taylor polynomials in z = theta * theta, Horner from the highest term down with plain
-// float64 multiplies and adds -- with -ffp-contract=off the host class, the host build of this function and the device run the
-// same IEEE operations, so trajectories agree bit for bit (libm's sin / cos differ between the sides in the last place,
-// and the pole grows a last-place difference by ~e^0.09 per step).
-__host__ __device__ inline double mz_cartpole_sin(double t) {
-  const double z = t * t;
-  double r = -1.0 / 1307674368000.0;
-  r = r * z + 1.0 / 6227020800.0;
-  r = r * z + -1.0 / 39916800.0;
-  r = r * z + 1.0 / 362880.0;
-  r = r * z + -1.0 / 5040.0;
-  r = r * z + 1.0 / 120.0;
-  r = r * z + -1.0 / 6.0;
-  r = r * z + 1.0;
-  return t * r;
-}
-__host__ __device__ inline double mz_cartpole_cos(double t) {
-  const double z = t * t;
-  double r = 1.0 / 20922789888000.0;
-  r = r * z + -1.0 / 87178291200.0;
-  r = r * z + 1.0 / 479001600.0;
-  r = r * z + -1.0 / 3628800.0;
-  r = r * z + 1.0 / 40320.0;
-  r = r * z + -1.0 / 720.0;
-  r = r * z + 1.0 / 24.0;
-  r = r * z + -1.0 / 2.0;
-  r = r * z + 1.0;
-  return r;
-}
-// env.step(action) on st = (x, x_dot, theta, theta_dot), in place, in the operation order of envs.CartPole.step; returns
-// whether the new state lies outside the thresholds (the time limit is the caller's: it owns the step counter).  The one
-// function every device form -- and the host side of the debug header -- calls.
-__host__ __device__ inline bool mz_cartpole_step(double *st, int action) {
-  const double g = 9.8, M = 1.1, m_pole = 0.1, l = 0.5, pml = 0.05, F = 10.0, tau = 0.02;
-  double x = st[0], x_dot = st[1], theta = st[2], theta_dot = st[3];
-  const double f = action == 1 ? F : -F;
-  const double c = mz_cartpole_cos(theta), s = mz_cartpole_sin(theta);
-  const double temp = (f + pml * theta_dot * theta_dot * s) / M;
-  const double tha = (g * s - c * temp) / (l * (4.0 / 3.0 - m_pole * c * c / M));
-  const double xa = temp - pml * tha * c / M;
-  x = x + tau * x_dot;
-  x_dot = x_dot + tau * xa;
-  theta = theta + tau * theta_dot;
-  theta_dot = theta_dot + tau * tha;
-  st[0] = x; st[1] = x_dot; st[2] = theta; st[3] = theta_dot;
-  const double th = 12 * 2 * 3.141592653589793 / 360;
-  return x < -2.4 || x > 2.4 || theta < -th || theta > th;
-}
-// env.reset() of episode `episode` of environment `env`: every component uniform in [-0.05, 0.05), from the counter RNG
-// -- integer-derived, identical on host and device, so the host can name the start of every episode.
-__host__ __device__ inline void mz_cartpole_reset_state(uint64_t seed, uint32_t env, uint32_t episode, double *out) {
-  for (uint32_t j = 0; j < 2; ++j) {
-    const mz_u4 r = mz_philox(seed, env, episode, 0u, (MZ_RNG_ENV << 24) | j);
-    out[2 * j] = (mz_u01(r.x, r.y) - 0.5) * 0.1;
-    out[2 * j + 1] = (mz_u01(r.z, r.w) - 0.5) * 0.1;
-  }
-}
-
-// What Actor.play_game reads before a move: the observation = the state as float32; every action is legal, to_play = +1
-static __global__ void k_cartpole_observe(SelfplayState sp, int B, int A) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  for (int k = 0; k < 4; ++k) sp.obs[(size_t)b * 4 + k] = (float)sp.cart[(size_t)b * 4 + k];
-  for (int a = 0; a < A; ++a) sp.legal[(size_t)b * A + a] = 1;
-  sp.to_play[b] = 1;
-}
-
+// ---- CartPole
 // Game.apply on CartPole's env.step for environment b, by ONE lane, and the tail of its experience record.  st: the
 // environment's four doubles (global memory, or the LDS words of a whole-moves launch), stepped or reset in place;
 // tt / ep: its step counter and episode before the move.  Returns done; the caller stores the counters.
@@ -321,88 +243,4 @@ static __global__ void k_cartpole_step_record(TreeView tv, SelfplayState sp, int
   for (int k = 0; k < 4; ++k) sp.cart[(size_t)b * 4 + k] = st[k];
   if (done) { sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next; }
   else sp.t[b] = tt + 1;
-}
-
-
-// ---- Connect Four on the device (envs.ConnectFour is the definition: 6 rows of 7 columns, cell 7 * row + col, row 0 at the
-// bottom; TicTacToe's conventions otherwise).  The rules are integer operations on the 42 int8 cells, so host and device
-// agree by construction; the two functions below are all the device forms know of the game.
-// env.step(col) for the mover `turn` on bd[42], the column not full (the search only offers legal columns): the stone lands
-// on the lowest empty cell; *won = a line of at least four of the mover's stones passes through it (vertical, horizontal,
-// the two diagonals); returns done = won or no empty cell left (a full board = a full top row).
-__host__ __device__ inline bool mz_c4_step(int8_t *bd, int turn, int col, bool *won) {
-  int row = 0;
-  while (row < 5 && bd[7 * row + col] != 0) ++row;
-  bd[7 * row + col] = (int8_t)turn;
-  const int dr[4] = {1, 0, 1, 1}, dc[4] = {0, 1, 1, -1};
-  bool w = false;
-  for (int d = 0; d < 4; ++d) {
-    int n = 0;
-    for (int sg = -1; sg <= 1; sg += 2) {
-      int r = row + sg * dr[d], c = col + sg * dc[d];
-      while (r >= 0 && r < 6 && c >= 0 && c < 7 && bd[7 * r + c] == turn) { ++n; r += sg * dr[d]; c += sg * dc[d]; }
-    }
-    w = w || n >= 3;
-  }
-  *won = w;
-  bool full = true;
-  for (int c = 0; c < 7; ++c) full = full && bd[35 + c] != 0;
-  return w || full;
-}
-// What Actor.play_game reads before a move: legal_actions() as a mask (the columns whose top cell is empty) and
-// game.to_play = env.turn; obs (optional) [42] = turn * board as float32, cell k of it is mz_c4_obs_cell
-__host__ __device__ inline float mz_c4_obs_cell(const int8_t *bd, int turn, int k) { return (float)(turn * (int)bd[k]); }
-__host__ __device__ inline uint32_t mz_c4_view(const int8_t *bd, int turn, float *obs, int *to_play) {
-  uint32_t mask = 0;
-  for (int c = 0; c < 7; ++c) mask |= (bd[35 + c] == 0 ? 1u : 0u) << c;
-  if (obs) for (int k = 0; k < 42; ++k) obs[k] = mz_c4_obs_cell(bd, turn, k);
-  *to_play = turn;
-  return mask;
-}
-
-static __global__ void k_c4_observe(SelfplayState sp, int B, int A) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  int to_play;
-  const uint32_t mask = mz_c4_view(sp.board + (size_t)b * 42, (int)sp.turn[b], sp.obs + (size_t)b * 42, &to_play);
-  for (int a = 0; a < A; ++a) sp.legal[(size_t)b * A + a] = (uint8_t)((mask >> a) & 1u);
-  sp.to_play[b] = (int8_t)to_play;
-}
-
-// Game.apply on env.step for environment b, by ONE lane, and the tail of its experience record -- TicTacToe's sequence
-// (mz_ttt_apply) on Connect Four's rules: on done the board is cleared, the turn is +1, the step 0, the episode advances
-// and the next game's temperature is evaluated.
-__device__ __forceinline__ void mz_c4_apply(const SelfplayState &sp, int b, int action, double root_value, double error,
-                                            float *rec, int A) {
-  const int O = 42;
-  const int turn = sp.turn[b], t = sp.t[b], ep = sp.episode[b];
-  int8_t *bd = sp.board + (size_t)b * 42;
-  bool won;
-  const int done = mz_c4_step(bd, turn, action, &won) ? 1 : 0;
-  mz_rec_put_double(rec + O + A + 0, root_value);
-  mz_rec_put_double(rec + O + A + 2, error);
-  rec[O + A + 4] = won ? 1.f : 0.f;
-  int32_t *ri = (int32_t *)(rec + O + A + 5);
-  ri[0] = action; ri[1] = done | (turn < 0 ? 2 : 0); ri[2] = t; ri[3] = sp.env_offset + b; ri[4] = ep;
-  if (done) {
-    for (int k = 0; k < 42; ++k) bd[k] = 0;
-    sp.turn[b] = 1; sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next;
-  } else {
-    sp.turn[b] = (int8_t)(-turn); sp.t[b] = t + 1;
-  }
-}
-
-// End of a move of the launch-per-step form: finalize the tree, write the record (pre-step observation), step the game
-static __global__ void k_c4_step_record(TreeView tv, SelfplayState sp, int B, int A, uint64_t seed) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const unsigned long long move = sp.movecnt[b];
-  sp.movecnt[b] = move + 1ull;
-  mz_finalize_tree(tv, b, sp.temp, nullptr, seed, move, sp.env_offset, sp.action, sp.child_visits, sp.root_value,
-                   sp.error, nullptr);
-  const int O = 42;
-  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
-  for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
-  for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
-  mz_c4_apply(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A);
 }

@@ -2,6 +2,12 @@
 // mz_engine.hip).  Replaces the per-move body of Actor.play_game (reference actors.py:131-173) for B
 // synthetic environments; the history hand-off to the replay buffer (actors.py:160-169) is the drain.
 
+// whether engine e can play the game `kind` (mz_game_shape_ok); if not, the failure is fn's: "<fn>: <Name> needs ..."
+static int game_shape(const mz_engine *e, const char *fn, int kind) {
+  char why[96];
+  return mz_game_shape_ok(kind, e->O, e->A, e->cfg.two_players != 0, why, sizeof why) ? 0 : fail("%s: %s", fn, why);
+}
+
 static int selfplay_alloc(mz_engine *e) {
   SelfplayState &sp = e->sp;
   if (sp.t) return 0;
@@ -40,16 +46,11 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
     HIPCHECK(hipMemcpyAsync(sp.t, t0.data(), t0.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHECK(hipStreamSynchronize(s));
   }
-  if (sp.env_kind == 1) {      // TicTacToe: env.reset() everywhere (tic_tac_toe.py:20-25); real games end by themselves
-    sp.episode_len = 9;
+  if (sp.env_kind == 1 || sp.env_kind == 3) {      // a board game: env.reset() everywhere (tic_tac_toe.py:20-25); real games end by themselves
+    const MzGameInfo g = mz_game_info(sp.env_kind);
+    sp.episode_len = g.longest;
     HIPCHECK(hipMemsetAsync(sp.t, 0, (size_t)e->Bp * 4, s));
-    HIPCHECK(hipMemsetAsync(sp.board, 0, (size_t)e->Bp * 9, s));
-    HIPCHECK(hipMemsetAsync(sp.turn, 1, (size_t)e->Bp, s));
-  }
-  if (sp.env_kind == 3) {      // Connect Four: env.reset() everywhere; a game ends on a line of four or a full board
-    sp.episode_len = 42;
-    HIPCHECK(hipMemsetAsync(sp.t, 0, (size_t)e->Bp * 4, s));
-    HIPCHECK(hipMemsetAsync(sp.board, 0, (size_t)e->Bp * 42, s));
+    HIPCHECK(hipMemsetAsync(sp.board, 0, (size_t)e->Bp * g.cells, s));
     HIPCHECK(hipMemsetAsync(sp.turn, 1, (size_t)e->Bp, s));
   }
   if (sp.env_kind == 2) {      // CartPole: episode_len is the time limit; every environment starts episode 0 at step 0
@@ -89,9 +90,7 @@ static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
   const bool cart = sp.env_kind == 2, c4 = sp.env_kind == 3;
-  if (cart) hipLaunchKernelGGL(k_cartpole_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
-  else if (c4) hipLaunchKernelGGL(k_c4_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
-  else hipLaunchKernelGGL(k_ttt_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, A);
+  hipLaunchKernelGGL(k_game_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, e->O, A);
   if (launch_root(e, sp.obs, false, s)) return -1;
   if (!e->draws_noise)
     hipLaunchKernelGGL(k_dirichlet, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, (const uint8_t *)sp.legal,
@@ -101,8 +100,8 @@ static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
               e->cfg.root_exploration_fraction, 1);
   if (launch_search(e, o, true, s)) return -1;
   if (cart) hipLaunchKernelGGL(k_cartpole_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
-  else if (c4) hipLaunchKernelGGL(k_c4_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
-  else hipLaunchKernelGGL(k_ttt_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
+  else if (c4) hipLaunchKernelGGL(k_board_step_record<3>, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
+  else hipLaunchKernelGGL(k_board_step_record<1>, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -167,10 +166,8 @@ int mz_selfplay_set_obs(mz_engine *e, int uint8_obs, const float *obs_min, const
   SelfplayState &sp = e->sp;
   if (uint8_obs < 0 || uint8_obs > 2) return fail("mz_selfplay_set_obs: uint8_obs %d (0 float, 1 byte-valued, 2 byte-valued and packed in the record)", uint8_obs);
   if (uint8_obs == 2 && sp.env_kind) return fail("mz_selfplay_set_obs: packed byte observations are for the synthetic -ram- environments");
-  if (sp.env_kind == 2 && (uint8_obs || obs_min))
-    return fail("mz_selfplay_set_obs: the CartPole environment has neither byte observations nor --norm_obs");
-  if (sp.env_kind == 3 && (uint8_obs || obs_min))
-    return fail("mz_selfplay_set_obs: the Connect Four environment has neither byte observations nor --norm_obs");
+  if ((sp.env_kind == 2 || sp.env_kind == 3) && (uint8_obs || obs_min))
+    return fail("mz_selfplay_set_obs: the %s environment has neither byte observations nor --norm_obs", mz_game_info(sp.env_kind).name);
   if (selfplay_alloc(e)) return -1;
   if (sp.moves_host != sp.drained) return fail("mz_selfplay_set_obs: drain the ring first (the record layout may change)");
   sp.obs_u8 = uint8_obs;
@@ -214,23 +211,16 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
   if (!e) return fail("mz_selfplay_set_env: null engine");
   MZ_ENTER(e);
   if (kind < 0 || kind > 3) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole, 3 Connect Four)", kind);
-  if (kind == 3 && (e->O != 42 || e->A != 7 || !e->cfg.two_players))
-    return fail("mz_selfplay_set_env: Connect Four needs obs_dim 42, action_space 7 and two_players (got %d, %d, %d)", e->O, e->A, e->cfg.two_players);
+  if (kind != 0 && game_shape(e, "mz_selfplay_set_env", kind)) return -1;
   if (kind == 3 && e->sp.obs_u8 == 2)
     return fail("mz_selfplay_set_env: packed byte observations are for the synthetic -ram- environments");
-  if (kind == 3 && (e->sp.obs_u8 || e->sp.obs_min))
-    return fail("mz_selfplay_set_env: the Connect Four environment has neither byte observations nor --norm_obs");
-  if (kind == 2 && (e->O != 4 || e->A != 2 || e->cfg.two_players))
-    return fail("mz_selfplay_set_env: CartPole needs obs_dim 4, action_space 2 and a single player (got %d, %d, two_players %d)", e->O, e->A, e->cfg.two_players);
-  if (kind == 2 && (e->sp.obs_u8 || e->sp.obs_min))
-    return fail("mz_selfplay_set_env: the CartPole environment has neither byte observations nor --norm_obs");
-  if (kind == 1 && (e->O != 9 || e->A != 9 || !e->cfg.two_players))
-    return fail("mz_selfplay_set_env: TicTacToe needs obs_dim 9, action_space 9 and two_players (got %d, %d, %d)", e->O, e->A, e->cfg.two_players);
+  if ((kind == 2 || kind == 3) && (e->sp.obs_u8 || e->sp.obs_min))
+    return fail("mz_selfplay_set_env: the %s environment has neither byte observations nor --norm_obs", mz_game_info(kind).name);
   if (selfplay_alloc(e)) return -1;
   HIPCHECK(hipDeviceSynchronize());
   SelfplayState &sp = e->sp;
   if ((kind == 1 || kind == 3) && !sp.board) {      // (the two board games differ in obs_dim: an engine plays one of them)
-    if (dmalloc(e, &sp.board, (size_t)e->Bp * (kind == 3 ? 42 : 9)) || dmalloc(e, &sp.turn, (size_t)e->Bp) ||
+    if (dmalloc(e, &sp.board, (size_t)e->Bp * mz_game_info(kind).cells) || dmalloc(e, &sp.turn, (size_t)e->Bp) ||
         dmalloc(e, &sp.legal, (size_t)e->Bp * e->A) || dmalloc(e, &sp.to_play, (size_t)e->Bp) ||
         dmalloc(e, &e->draw_uniform, (size_t)e->Bp))
       return -1;

@@ -5,7 +5,7 @@
 // end of the file (sv_unit_tt, k_solve_tt: non-losing moves, ordered, a table private to the unit).
 //
 // THIS FILE HOLDS A SECOND FORM OF THE RULES: bitboards (Connect Four: 7 columns of 7 bits, 6 cells and an always-empty
-// sentinel bit, bit 7 * col + row; TicTacToe: 9 bits), beside mz_ttt_step / mz_c4_step of mz_selfplay.hip.h, which
+// sentinel bit, bit 7 * col + row; TicTacToe: 9 bits), beside mz_ttt_step / mz_c4_step of mz_games.h, which
 // mz_playout.hip.h deliberately did without.  It is acceptable here only because the tests pin it against the first form:
 // tests/test_solve_cpu.py holds the values on every reachable TicTacToe position and on Connect Four endgames to a minimax
 // written on the first form's Python restatement (tests/playout_py.py).  The int8[42] board is converted once per position

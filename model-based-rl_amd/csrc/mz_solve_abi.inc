@@ -60,9 +60,7 @@ static int solve_run(const char *fn, bool table, mz_engine *e, int kind, const i
   if (!e) return fail("%s: null engine", fn);
   MZ_ENTER(e);
   if (kind != 1 && kind != 3) return fail("%s: kind must be 1 (TicTacToe) or 3 (Connect Four), got %d", fn, kind);
-  if (e->O != (kind == 1 ? 9 : 42) || e->A != (kind == 1 ? 9 : 7) || !e->cfg.two_players)
-    return fail("%s: %s", fn, kind == 1 ? "TicTacToe needs obs_dim 9, action_space 9, two_players"
-                                        : "Connect Four needs obs_dim 42, action_space 7, two_players");
+  if (game_shape(e, fn, kind)) return -1;
   if (solve_check(fn, kind, e->A, boards, turn, step, n, max_nodes)) return -1;
   if (n == 0) return 0;
   if (!values_out) return fail("%s: null values_out", fn);

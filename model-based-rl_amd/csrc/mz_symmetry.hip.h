@@ -17,12 +17,13 @@
 #pragma once
 #include <stdint.h>
 #include "mz_rng.h"
+#include "mz_games.h"
 
 #define MZ_SYM_THREADS 256
 
-// the kind's (cells, actions, group size); 0 elements: not a kind with symmetries
-__host__ __device__ inline int sym_cells(int kind) { return kind == 1 ? 9 : (kind == 3 ? 42 : 0); }
-__host__ __device__ inline int sym_actions(int kind) { return kind == 1 ? 9 : (kind == 3 ? 7 : 0); }
+// the kind's (cells, actions) of mz_games.h and its group size; 0 elements: not a kind with symmetries
+__host__ __device__ inline int sym_cells(int kind) { return mz_game_info(kind).cells; }
+__host__ __device__ inline int sym_actions(int kind) { return mz_game_info(kind).actions; }
 __host__ __device__ inline int sym_elements(int kind) { return kind == 1 ? 8 : (kind == 3 ? 2 : 0); }
 
 // TicTacToe: p_g(c) and its inverse (rows g = 4 f + q)

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from .envs import BOARD_KINDS, KIND_OF_ENV, SELFPLAY_KINDS
 
 H = 50
 
@@ -406,7 +407,7 @@ class Engine(object):
     return out
 
   # ---- evaluation games on the device environments (mz_eval_env_*, include/mz_engine.h)
-  EVAL_ENVS = {'TicTacToe': 1, 'CartPole-v0': 2, 'CartPole-v1': 2, 'ConnectFour': 3}
+  EVAL_ENVS = KIND_OF_ENV      # (envs.DEVICE_GAMES)
 
   def eval_env_reset(self, kind, max_steps, time_limit=0, random_opp=None, keep_history=False):
     """mz_eval_env_reset: B evaluation games of `kind` (an EVAL_ENVS name or 1 / 2 / 3) at their start; game b has the seed
@@ -576,7 +577,7 @@ class Engine(object):
     self.obs_packed = bool(packed)
     self.rec_floats = self.lib.mz_selfplay_rec_floats(self._h)
 
-  ENVS = {'synthetic': 0, 'tictactoe': 1, 'cartpole': 2, 'connect_four': 3}
+  ENVS = SELFPLAY_KINDS      # (envs.DEVICE_GAMES)
 
   def selfplay_set_env(self, kind):
     """'synthetic' (default), 'tictactoe' (the reference's custom_environments/tic_tac_toe.py on the device), 'cartpole'
@@ -720,7 +721,7 @@ class Match(object):
   """A match between two networks on the device games (mz_match_*, include/mz_engine.h): a handle over two Engines, network
   0 and network 1, each with its own weights and num_simulations.  The engines must share device, num_envs, shapes, seed
   and env_id_offset; the match holds them and is closed before them."""
-  KINDS = {'TicTacToe': 1, 'ConnectFour': 3}
+  KINDS = BOARD_KINDS      # (envs.DEVICE_GAMES)
   MODES = {'search': 0, 'only_prior': 1, 'only_value': 2}
 
   def __init__(self, engine0, engine1, kind, max_steps, keep_history=False):
@@ -730,7 +731,7 @@ class Match(object):
     self.B, self.A = engine0.B, engine0.A
     self.S = max(engine0.sims, engine1.sims)
     self.keep = bool(keep_history)
-    k = self.KINDS.get(kind, 2 if str(kind).startswith('CartPole') else 0) if isinstance(kind, str) else int(kind)
+    k = KIND_OF_ENV.get(kind, 0) if isinstance(kind, str) else int(kind)      # (CartPole's 2 gets mz_match_create's own refusal)
     h = C.c_void_p()
     _abi.check(self.lib.mz_match_create(engine0._h, engine1._h, k, int(max_steps), int(self.keep), C.byref(h)), 'mz_match_create')
     self._h = h

@@ -2,10 +2,10 @@
 (custom_environments/tic_tac_toe.py:5-76: gym-0.x API, observation = turn * board, reward 1 for the
 winning move, draw after nine moves).  CartPole is the classic-control task the reference reaches through gym.make
 ('CartPole-v1' / 'CartPole-v0'); gym is not installed, so the class below IS its definition and the device environment
-(csrc/mz_selfplay.hip.h, mz_cartpole_step) follows it bit for bit.  Every other reference environment (Box2D, ALE) is
+(csrc/mz_games.h, mz_cartpole_step) follows it bit for bit.  Every other reference environment (Box2D, ALE) is
 unavailable; its SHAPE is served by the on-device synthetic env (csrc/mz_selfplay.hip.h).  ConnectFour is not among the
 reference's environments: the class below is its definition, a second two-player board game next to TicTacToe with the
-same conventions, and the device environment (csrc/mz_selfplay.hip.h, mz_c4_step) follows it move for move."""
+same conventions, and the device environment (csrc/mz_games.h, mz_c4_step) follows it move for move."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -106,7 +106,7 @@ class ConnectFour(object):
 
 
 # sin / cos of the pole angle as fixed Taylor polynomials in z = theta * theta, Horner from the highest term down with plain
-# float64 multiplies and adds: the device runs the very same IEEE operations (csrc/mz_selfplay.hip.h), where its libm and
+# float64 multiplies and adds: the device runs the very same IEEE operations (csrc/mz_games.h), where its libm and
 # the host's differ in the last place -- and the pole, an unstable system, grows such a difference by ~e^0.09 per step.
 # Within 1.2e-16 of math.sin / math.cos on [-0.8, 0.8]; the state is reset before |theta| passes 0.27.
 _SIN_C = (1.0, -1.0 / 6.0, 1.0 / 120.0, -1.0 / 5040.0, 1.0 / 362880.0, -1.0 / 39916800.0, 1.0 / 6227020800.0,
@@ -185,6 +185,27 @@ class CartPole(object):
     if self._elapsed_steps >= self.max_episode_steps:
       done = True
     return self._obs(), 1.0, done, {}
+
+
+# ---- the device games: the one table of them on the Python side (csrc/mz_games.h, mz_game_info, is the device's).
+# --environment name -> (kind, obs_dim, actions, cells of the board or 0, two_players); every other table and list of
+# games in the package is a view of this one.
+DEVICE_GAMES = {
+    'TicTacToe': (1, 9, 9, 9, True),
+    'ConnectFour': (3, 42, 7, 42, True),
+    'CartPole-v0': (2, 4, 2, 0, False),
+    'CartPole-v1': (2, 4, 2, 0, False),
+}
+DEVICE_ENVS = tuple(DEVICE_GAMES)
+KIND_OF_ENV = {name: g[0] for name, g in DEVICE_GAMES.items()}
+# the two-player board games: what matches, the playout opponent, the solvers and the symmetry tables cover
+BOARD_KINDS = {name: g[0] for name, g in DEVICE_GAMES.items() if g[3]}
+BOARD_ENVS = tuple(BOARD_KINDS)
+CELLS = {g[0]: g[3] for g in DEVICE_GAMES.values() if g[3]}
+ACTIONS = {g[0]: g[2] for g in DEVICE_GAMES.values() if g[3]}
+# the self-play loop's own spellings (Engine.selfplay_set_env); 0 is its synthetic environment
+SELFPLAY_KINDS = dict({'synthetic': 0}, **{short: KIND_OF_ENV[name] for short, name in
+                                           (('tictactoe', 'TicTacToe'), ('cartpole', 'CartPole-v1'), ('connect_four', 'ConnectFour'))})
 
 
 def get_environment(config):

@@ -32,12 +32,11 @@ import torch
 
 from .config import CARTPOLE_TIME_LIMITS, get_evaluation_args
 from .engine import Engine, flatten_weights
-from .envs import get_environment
+from .envs import BOARD_ENVS, DEVICE_ENVS, get_environment
 from .game import History
 
 MAX_BATCH = 4096
 MOVES_PER_SYNC = 8      # --device_env: whole moves enqueued per host synchronisation
-DEVICE_ENVS = ('TicTacToe', 'ConnectFour', 'CartPole-v0', 'CartPole-v1')
 
 REFUSED = (
     ('render', 'rendering is an interactive tool and is not part of this evaluator (no display on the GPU machines).'),
@@ -71,7 +70,7 @@ def refuse_device_env(args_or_config):
                               'columns, which the host class refuses and a device game cannot.')
 
 
-PLAYOUT_ENVS = ('TicTacToe', 'ConnectFour')
+PLAYOUT_ENVS = BOARD_ENVS
 
 
 def refuse_opp_playouts(args_or_config, match=False):
@@ -97,7 +96,7 @@ def refuse_opp_playouts(args_or_config, match=False):
     raise NotImplementedError('--opp_playouts: the playout opponent answers every move and takes --apply_mcts_actions 1 only.')
 
 
-GRADE_ENVS = ('TicTacToe', 'ConnectFour')
+GRADE_ENVS = BOARD_ENVS
 
 
 def refuse_grade(args_or_config, match=False):

@@ -21,11 +21,11 @@ import numpy as np
 import torch
 
 from .engine import Engine, Match, flatten_weights
+from .envs import BOARD_ENVS as MATCH_ENVS
 from .game import History
 
 MAX_BATCH = 4096
 PLIES_PER_SYNC = 8      # whole plies enqueued per host synchronisation (evaluate.MOVES_PER_SYNC)
-MATCH_ENVS = ('TicTacToe', 'ConnectFour')
 
 
 def _all(x):

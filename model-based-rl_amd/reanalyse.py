@@ -18,15 +18,14 @@ import numpy as np
 import torch
 
 from .actors import _call
-from .config import CARTPOLE_TIME_LIMITS
 from .engine import Engine, REC_EXTRA
+from .envs import KIND_OF_ENV
 
-KINDS = {'TicTacToe': 1, 'ConnectFour': 3}      # Engine.ENVS numbering; CartPole-v0 / -v1: 2; anything else: 0 (all actions legal)
+KINDS = KIND_OF_ENV      # (envs.DEVICE_GAMES; anything else: 0, all actions legal)
 
 
 def env_kind(config):
-  env = str(getattr(config, 'environment', ''))
-  return 2 if env in CARTPOLE_TIME_LIMITS else KINDS.get(env, 0)
+  return KINDS.get(str(getattr(config, 'environment', '')), 0)
 
 
 def refuse_reanalyse(config, ranks=0):
@@ -44,7 +43,7 @@ def refuse_reanalyse(config, ranks=0):
     raise no('--norm_obs is not reanalysed (the stored observations are raw).')
   if getattr(config, 'episode_life', False):
     raise no('--episode_life histories do not come from device records and are not reanalysed.')
-  host_env = str(config.environment) in ('TicTacToe', 'ConnectFour') or str(config.environment) in CARTPOLE_TIME_LIMITS
+  host_env = str(config.environment) in KINDS
   if host_env and (bool(getattr(config, 'parity_rng', False)) or int(getattr(config, 'num_envs', 1)) == 1):
     raise no('host-environment actors (--num_envs 1 or --parity_rng) are not reanalysed; use the device self-play loop.')
 

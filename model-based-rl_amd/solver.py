@@ -9,10 +9,8 @@ view of the solver's values, so no sign is applied."""
 import numpy as np
 
 from .engine import Engine
-from .envs import ConnectFour, TicTacToe
+from .envs import BOARD_KINDS as KINDS, CELLS, ConnectFour, TicTacToe
 
-KINDS = {'TicTacToe': 1, 'ConnectFour': 3}
-CELLS = {1: 9, 3: 42}
 ILLEGAL, UNSOLVED = -2, -3
 BLUNDERS = ('win_to_draw', 'win_to_loss', 'draw_to_loss')
 DEFAULT_EMPTIES = 12      # Connect Four: positions with at most this many empty cells are graded (derived from profiles/solve_bench.json: README)

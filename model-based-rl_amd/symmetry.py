@@ -12,12 +12,11 @@ Kinds are mz_game_kind's: 1 TicTacToe (cell 3 * row + col, action = cell; g = 4 
 then, if f, (r, c) -> (r, 2 - c)), 3 Connect Four (cell 7 * row + col, action = column; g = 1: col -> 6 - col)."""
 import numpy as np
 
-TICTACTOE, CONNECT_FOUR = 1, 3
+from .envs import ACTIONS, BOARD_KINDS as KIND_OF_ENV, CELLS
+
+TICTACTOE, CONNECT_FOUR = KIND_OF_ENV['TicTacToe'], KIND_OF_ENV['ConnectFour']
 RNG_SYM = 10      # MZ_RNG_SYM (csrc/mz_rng.h)
-CELLS = {TICTACTOE: 9, CONNECT_FOUR: 42}
-ACTIONS = {TICTACTOE: 9, CONNECT_FOUR: 7}
 ELEMENTS = {TICTACTOE: 8, CONNECT_FOUR: 2}
-KIND_OF_ENV = {'TicTacToe': TICTACTOE, 'ConnectFour': CONNECT_FOUR}
 
 
 def _ttt_cell(g, cell):

@@ -15,7 +15,8 @@ import torch
 
 from . import rayshim as ray
 from .actors import Actor
-from .config import build_parser, CARTPOLE_TIME_LIMITS, Config, env_shapes
+from .config import build_parser, Config, env_shapes
+from .envs import KIND_OF_ENV
 from .learners import Learner
 from .networks import FCNetwork
 from .replay_buffer import PrioritizedReplay
@@ -158,7 +159,7 @@ def launch_ranks(config, max_moves, selfplay_only=False, learner_steps=None, sta
   del probe
   dedicated = bool(getattr(config, 'dedicated_learner_rank', False)) and world > 1 and not selfplay_only
 
-  if dedicated and (config.environment in ('TicTacToe', 'ConnectFour') or config.environment in CARTPOLE_TIME_LIMITS) and (getattr(config, 'parity_rng', False) or B == 1):
+  if dedicated and config.environment in KIND_OF_ENV and (getattr(config, 'parity_rng', False) or B == 1):
     raise SystemExit('--dedicated_learner_rank: host-environment actors pull weights per game, not per move count')
   if dedicated and rank == 0:
     # rank 0's GPU belongs to the learner alone (an actor beside it takes turns with it -- share_gpu_in_turns -- and so runs at

@@ -2,6 +2,7 @@
 // mz_match_apply_game) compiled for the HOST and played against a rule check of this file's own: random TicTacToe and
 // Connect Four games, every ply through the opening body (an index into the legal list) or the apply body (an action),
 // and after every ply a window scan of the whole board for a line of three / four says who -- if anyone -- has won.
+// Before the games, mz_depth_list_max (csrc/mz_games.h) is called on a handful of lists that differ.
 // A stand-alone program (tests/test_match_cpu.py builds it with the host pass of hipcc and -fsanitize=address,undefined,
 // runs it, and replays the digest's action lists on the envs.py classes).  No GPU is touched.
 //
@@ -14,7 +15,6 @@
 #include <vector>
 
 #include "mz_engine.h"
-#define MZ_MAX_ACTIONS_K MZ_MAX_ACTIONS      // (as mz_engine.hip sets it before the kernel headers)
 #include "mz_match.hip.h"
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
@@ -48,7 +48,7 @@ struct Host {
   std::vector<float> obs, pred_rewards, log_pred_reward, log_pred_value;
   Host(int kind, int max_steps, int B, int A, int O, int S) {
     memset(&ms, 0, sizeof ms);
-    const int longest = kind == 1 ? 9 : 42;
+    const int longest = mz_game_info(kind).longest;
     ms.kind = kind; ms.max_steps = max_steps; ms.cap = max_steps < longest ? max_steps : longest; ms.S = S;
     const size_t L = (size_t)B * ms.cap;
     board.assign((size_t)B * 42, 0); turn.assign(B, 1); result.assign(B, 0); to_play.assign(B, 0);
@@ -81,7 +81,7 @@ static int fail(const char *what, int kind, int b, int ply) {
 // B random games of one kind, all of them advanced ply by ply; game b goes through the opening body when b is even and
 // through the apply body when it is odd
 static int play(int kind, int max_steps, int B, long *games) {
-  const int A = kind == 1 ? 9 : 7, O = kind == 1 ? 9 : 42, S = 3;
+  const int A = mz_game_info(kind).actions, O = mz_game_info(kind).obs_dim, S = 3;
   const int rows = kind == 1 ? 3 : 6, cols = kind == 1 ? 3 : 7, need = kind == 1 ? 3 : 4, cells = rows * cols;
   Host h(kind, max_steps, B, A, O, S);
   MatchState &ms = h.ms;
@@ -152,7 +152,37 @@ static int play(int kind, int max_steps, int B, long *games) {
   return 0;
 }
 
+// mz_depth_list_max (csrc/mz_games.h) on lists that differ: the games above hand it nothing but lists it takes or ties
+static int depth_lists() {
+  struct Case { int32_t pl[4]; bool first, taken; const char *what; };
+  const Case cases[] = {
+      {{2, 1, 3, 1}, true, true, "the first list is always taken"},
+      {{2, 1, 3, 1}, false, false, "an equal list"},
+      {{2, 1, 2, 9}, false, false, "a list smaller at the first index that differs, greater later"},
+      {{1, 9, 9, 9}, false, false, "a list smaller at index 0"},
+      {{2, 2, 0, 0}, false, true, "a list greater at an early index, smaller later"},
+      {{2, 2, 0, 1}, false, true, "a list greater at the last index"},
+      {{0, 0, 0, 0}, true, true, "a smaller list that is the first"},
+  };
+  int32_t dm[4] = {7, 7, 7, 7};      // (never compared: the first case is the first list)
+  double mean = -1.0;
+  for (const Case &c : cases) {
+    int32_t before[4];
+    memcpy(before, dm, sizeof dm);
+    const double mean_before = mean;
+    const bool taken = mz_depth_list_max(dm, c.pl, 4, c.first, &mean);
+    const int32_t *want = c.taken ? c.pl : before;
+    const double want_mean = c.taken ? (double)(c.pl[0] + c.pl[1] + c.pl[2] + c.pl[3]) / 4.0 : mean_before;
+    if (taken != c.taken || memcmp(dm, want, sizeof dm) || mean != want_mean) {
+      printf("MISMATCH depth lists: %s\n", c.what);
+      return 1;
+    }
+  }
+  return 0;
+}
+
 int main() {
+  if (depth_lists()) return 1;
   long games = 0;
   // whole games, and games cut at max_steps (5 plies of TicTacToe, 11 of Connect Four)
   if (play(1, 100, 1500, &games) || play(3, 100, 1500, &games) || play(1, 5, 300, &games) || play(3, 11, 300, &games)) return 1;

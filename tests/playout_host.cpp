@@ -3,8 +3,8 @@
 // A stand-alone program (tests/test_playout_cpu.py builds it with the host pass of hipcc and -fsanitize=address,undefined,
 // runs it, and compares the plans it prints with the library's mz_playout_plan_host on the same positions).  No GPU is
 // touched.  The tree's memory is a heap block of exactly po_wave_bytes, so a node or a board cell outside it is an
-// AddressSanitizer report.  The planner knows the rules through mz_ttt_step / mz_c4_step only (there is no second form
-// of them to compare here).
+// AddressSanitizer report.  The planner knows the rules through mz_game_step / mz_game_legal of csrc/mz_games.h only
+// (there is no second form of them to compare here).
 //
 // Output: one line per position, "kind turn step action v[0..A) w[0..A) cell[0..42)"; position i is the game with the seed
 // ENV_OFFSET + i, every plan has the engine seed SEED and the move MOVE; the last line is "ok <positions>".
@@ -16,7 +16,6 @@
 #include <vector>
 
 #include "mz_engine.h"
-#define MZ_MAX_ACTIONS_K MZ_MAX_ACTIONS      // (as mz_engine.hip sets it before the kernel headers)
 #include "mz_playout.hip.h"
 
 static const uint64_t SEED = 11;
@@ -50,7 +49,7 @@ int main() {
   for (int v = 1; v <= iters; ++v) ln[v] = log(64.0 * (double)v);
   int index = 0;
   for (int kind = 1; kind <= 3; kind += 2) {
-    const int A = kind == 1 ? 9 : 7, longest = kind == 1 ? 9 : 42;
+    const int A = mz_game_info(kind).actions, longest = mz_game_info(kind).longest;
     const size_t bytes = po_wave_bytes(iters + 1, A);
     for (int i = 0; i < PER_KIND; ++i, ++index) {
       unsigned char *mem = (unsigned char *)malloc(bytes);      // (fresh and uninitialised for every plan: po_plan clears what it reads)
