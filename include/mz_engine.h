@@ -321,6 +321,32 @@ int mz_solve(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, c
 int mz_solve_tt(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, int n, int max_nodes,
                 int8_t *values_out, uint32_t *nodes_out, void *stream);
 
+/* The learned model graded by unroll depth against the true game (DESIGN s7f, "Grading by unroll depth";
+ * csrc/mz_unroll.hip.h).  A row is a start position of TicTacToe (kind 1) or Connect Four (kind 3) -- [host] boards [n][42],
+ * turn [n], step [n] as mz_solve takes them, any n (chunks of num_envs inside) -- and [host] actions [n][K] int32, -1 as
+ * padding, K in 0 .. 16.  The row's LINE: p_0 is the start; while j < K, actions[j] >= 0 and p_j is not terminal, p_{j+1} =
+ * step(p_j, actions[j]) on the true rules and the mover alternates; depth = the actions applied.  An action that is illegal
+ * in p_j stops the line there and sets bit 0 of the row's flags.  Per chunk, in stream order with no host synchronisation:
+ * the lines; mz_initial_inference of p_0 (h_0, v_0, logits_0); K times mz_recurrent_inference(h_{k-1}, a_{k-1}), the
+ * UNROLLED h_k, r_k, v_k, logits_k; K times mz_initial_inference of the real p_k, the FRESH v_k, logits_k; the terms.  A row
+ * whose line is shorter than k keeps its lane and its outputs at k are zero.
+ *   truth      [host][n][K + 1][A] int8 or NULL: mz_solve's values of the actions of p_k (-2 illegal, -3 unsolved; all -3: p_k
+ *              is not in scope).  NULL: the terms that need it stay zero.
+ *   terms_out  [host][n][K + 1][mz_unroll_num_terms()] float64, the scalars the report averages, in the order of
+ *              MzUnrollTerm (csrc/mz_unroll.hip.h; engine.Engine.UNROLL_TERMS): softmax over all A actions, float64
+ *              arithmetic on the float32 outputs, sums in ascending action order.  Values are in the view of p_k's mover.
+ *   depth_out, flags_out  [host][n] int32.
+ *   raw_out    [host][n][K + 1][mz_unroll_raw_floats()] float32 or NULL: per (row, k) the observation [obs_dim], the unrolled
+ *              hidden state [50], the unrolled and the fresh logits [A] each, then value_u, reward_u, value_f, reward_true;
+ *              raw_meta_out [host][n][K + 1][2] int32 (NULL with raw_out): the legal mask of p_k and whether it is terminal.
+ * Overwrites the engine's root outputs and hidden slot 0; the weights, the RNG keys, the evaluation environment and the
+ * solver are left alone.  Its device memory is its own, allocated on first use.  Synchronises once, at the end. */
+int mz_unroll(mz_engine *e, int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, const int32_t *actions, int n,
+              int K, const int8_t *truth, double *terms_out, int32_t *depth_out, int32_t *flags_out, float *raw_out,
+              int32_t *raw_meta_out, void *stream);
+int mz_unroll_raw_floats(const mz_engine *e);
+int mz_unroll_num_terms(void);
+
 /* A match between two networks on the device games: B games in lock-step, every ply searched by the mover's own network.
  * Replaces the per-ply host loop a match driven from Python would need (two Evaluator._play_batch loops interleaved by
  * hand: per ply one engine call sequence and one host environment step); the host touches no game between plies.

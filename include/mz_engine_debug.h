@@ -150,6 +150,21 @@ int mz_solve_tt_host(int kind, int A, const int8_t *boards, const int8_t *turn, 
                      int8_t *values_out, uint32_t *nodes_out);
 int mz_solve_tt_set_generation(mz_engine *e, int generation);
 
+/* test hooks of mz_unroll: its two __host__ __device__ bodies (csrc/mz_unroll.hip.h) looped on the HOST; no engine, no device.
+ * mz_unroll_lines_host: the lines of n rows (arguments and checks as mz_unroll's), row-major: obs_out [n][K + 1][obs_dim]
+ * float32, legal_out [n][K + 1] uint32 masks, terminal_out [n][K + 1] uint8, reward_true_out [n][K + 1] float32, depth_out and
+ * flags_out [n].  Integers and casts of -1 / 0 / +1: the device's lines equal these bit for bit.
+ * mz_unroll_terms_host: the terms of `items` independent (row, k) in the device's operation order (exp() is the host
+ * library's): logits_u / logits_f [items][A] float32, legal [items] uint32, terminal / live [items] uint8, k [items] int32,
+ * reward_true / reward_u / value_u / value_f [items] float32, truth [items][A] int8 or NULL -> terms_out
+ * [items][mz_unroll_num_terms()] float64. */
+int mz_unroll_lines_host(int kind, const int8_t *boards, const int8_t *turn, const int32_t *step, const int32_t *actions, int n, int K,
+                         float *obs_out, uint32_t *legal_out, uint8_t *terminal_out, float *reward_true_out, int32_t *depth_out,
+                         int32_t *flags_out);
+int mz_unroll_terms_host(int A, int items, const float *logits_u, const float *logits_f, const uint32_t *legal, const uint8_t *terminal,
+                         const uint8_t *live, const int32_t *k, const float *reward_true, const float *reward_u, const float *value_u,
+                         const float *value_f, const int8_t *truth, double *terms_out);
+
 /* test hooks of mz_fcl_set_symmetry.  mz_fcl_symmetry_apply: the symmetry kernel alone, with the handle's kind and seed and the
  * given update number, on device-visible arrays of the handle's batch (obs [batch][obs_dim], actions [batch][K] int32 / int64,
  * target_policies [batch][K + 1][A]; device memory, or mapped pinned host memory as mz_fcl_run's staging is -- the hook looks its

@@ -36,6 +36,7 @@
 #include "mz_reanalyse.hip.h"
 #include "mz_playout.hip.h"
 #include "mz_solve.hip.h"
+#include "mz_unroll.hip.h"
 #include "mz_symmetry.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
@@ -177,6 +178,7 @@ struct mz_engine {
   PlayoutState po = {};             // the playout-search opponent (mz_playout_plan, mz_eval_env_set_opponent; mz_playout.hip.h), allocated on first use
   SolveState sv = {};               // the exact game solver (mz_solve; mz_solve.hip.h), allocated on first use
   SolveTableState svt = {};         // its table search's tables and counters (mz_solve_tt), allocated on its first use
+  UnrollState ur = {};              // the unroll diagnostic (mz_unroll; mz_unroll.hip.h), allocated on first use
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -1659,6 +1661,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 #include "mz_selfplay_abi.inc"
 #include "mz_playout_abi.inc"
 #include "mz_solve_abi.inc"
+#include "mz_unroll_abi.inc"
 #include "mz_eval_abi.inc"
 #include "mz_match_abi.inc"
 #include "mz_reanalyse_abi.inc"

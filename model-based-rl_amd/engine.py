@@ -505,6 +505,52 @@ class Engine(object):
     _abi.check(getattr(self.lib, name)(self._h, k, p(bd), p(tn), p(st), n, int(max_nodes), p(values), p(nodes), self.stream), name)
     return values, nodes
 
+  # ---- the learned model by unroll depth (mz_unroll, include/mz_engine.h)
+  UNROLL_MAX_K = 16
+  UNROLL_TERMS = ('live', 'transition', 'position', 'reward_true', 'reward', 'reward_err', 'value', 'value_fresh', 'value_drift',
+                  'policy_tv', 'top1_agree', 'illegal_mass', 'illegal_mass_fresh', 'solved', 'vstar', 'value_err', 'value_err_fresh',
+                  'sign', 'sign_fresh', 'optimal_mass', 'optimal_mass_fresh')      # csrc/mz_unroll.hip.h MzUnrollTerm
+
+  def unroll(self, kind, boards, turn, step, actions, truth=None, raw=False):
+    """mz_unroll: the model unrolled along the actions of n rows (any n) next to the real positions those actions lead to.
+    kind: an EVAL_ENVS name or 1 / 3; boards [n, 42], turn [n], step [n] as solve's; actions [n, K] int32, -1 as padding, K in
+    0 .. 16; truth [n, K + 1, A] int8 or None: solve's values of the actions of p_k.  Returns a dict of numpy arrays: depth [n]
+    (the actions applied), terms [n, K + 1, len(UNROLL_TERMS)] float64 (the scalars of every (row, k), named by UNROLL_TERMS;
+    values are in the view of p_k's mover) and, with raw=True, obs [n, K + 1, O], hidden_u [n, K + 1, 50], logits_u / logits_f
+    [n, K + 1, A], value_u / reward_u / value_f / reward_true [n, K + 1] (float32), legal [n, K + 1, A] and terminal [n, K + 1]
+    (uint8).  Past a row's depth everything is zero.  ValueError if a row holds an action that is illegal in its position."""
+    k = self.EVAL_ENVS[kind] if isinstance(kind, str) else int(kind)
+    bd = np.ascontiguousarray(boards, np.int8)
+    tn, st = np.ascontiguousarray(turn, np.int8), np.ascontiguousarray(step, np.int32)
+    ac = np.ascontiguousarray(actions, np.int32)
+    n = bd.shape[0]
+    if bd.shape != (n, 42) or tn.shape != (n,) or st.shape != (n,) or ac.ndim != 2 or ac.shape[0] != n:
+      raise ValueError('unroll: boards [n, 42], turn [n], step [n], actions [n, K]; got %s, %s, %s, %s' % (bd.shape, tn.shape, st.shape, ac.shape))
+    K = ac.shape[1]
+    th = None
+    if truth is not None:
+      th = np.ascontiguousarray(truth, np.int8)
+      if th.shape != (n, K + 1, self.A):
+        raise ValueError('unroll: truth [n, K + 1, A] = %s, got %s' % ((n, K + 1, self.A), th.shape))
+    NT, W = len(self.UNROLL_TERMS), self.O + H + 2 * self.A + 4
+    assert NT == self.lib.mz_unroll_num_terms() and W == self.lib.mz_unroll_raw_floats(self._h)
+    terms = np.zeros((n, K + 1, NT), np.float64)
+    depth, flags = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rec = np.zeros((n, K + 1, W), np.float32) if raw else None
+    meta = np.zeros((n, K + 1, 2), np.int32) if raw else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _abi.check(self.lib.mz_unroll(self._h, k, p(bd), p(tn), p(st), p(ac), n, K, p(th), p(terms), p(depth), p(flags), p(rec), p(meta),
+                                  self.stream), 'mz_unroll')
+    if flags.any():
+      raise ValueError('unroll: row %d holds an action that is illegal in its position' % int(np.flatnonzero(flags)[0]))
+    out = dict(depth=depth, terms=terms)
+    if raw:
+      O, A = self.O, self.A
+      out.update(obs=rec[..., :O], hidden_u=rec[..., O:O + H], logits_u=rec[..., O + H:O + H + A], logits_f=rec[..., O + H + A:O + H + 2 * A],
+                 value_u=rec[..., W - 4], reward_u=rec[..., W - 3], value_f=rec[..., W - 2], reward_true=rec[..., W - 1],
+                 legal=((meta[..., 0:1] >> np.arange(A)) & 1).astype(np.uint8), terminal=meta[..., 1].astype(np.uint8))
+    return out
+
   # ---- Reanalyse of stored replay rows (mz_reanalyse, include/mz_engine.h)
   def reanalyse(self, rows, fresh, n_rows, kind, num_simulations=None):
     """mz_reanalyse: rows [>= n_rows, O + A + REC_EXTRA] and fresh [>= n_rows, A + 2], both PINNED float32 host tensors; the

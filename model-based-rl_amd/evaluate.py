@@ -120,6 +120,21 @@ def refuse_grade(args_or_config, match=False):
     raise NotImplementedError('--grade: a graded decision is one searched move and takes --apply_mcts_actions 1 only.')
 
 
+def refuse_grade_unroll(args_or_config):
+  """one sentence per configuration --grade_unroll K (the model by unroll depth, solver.grade_unroll) leaves out
+  (NotImplementedError, starting '--grade_unroll: '); nothing to refuse without the flag.  What --grade refuses stays
+  refused by --grade's own sentence (refuse_grade runs first).  --no_support checkpoints are served: the unroll goes through
+  mz_initial_inference and mz_recurrent_inference, which read the heads' single outputs."""
+  c = args_or_config
+  K = getattr(c, 'grade_unroll', None)
+  if K is None or K is False:
+    return
+  if not getattr(c, 'grade', False):
+    raise NotImplementedError('--grade_unroll: it unrolls the model along the games --grade keeps and does nothing without --grade.')
+  if int(K) < 1 or int(K) > Engine.UNROLL_MAX_K:
+    raise NotImplementedError('--grade_unroll: the depth is 1 to %d dynamics steps, got %d.' % (Engine.UNROLL_MAX_K, int(K)))
+
+
 class DeviceGame(object):
   """A finished game of the device-environment path: what the summary and the CLI read, from the device's accumulators.
   With keep_history also the per-move lists under the host path's names (history.actions / rewards / to_play / dones /
@@ -183,7 +198,9 @@ class Evaluator(SummaryTools):
     refuse_device_env(self.config)
     refuse_opp_playouts(_with(self.config, device_env=True))      # (play_games(device_env=True) may still name the device path)
     refuse_grade(_with(self.config, device_env=True))
+    refuse_grade_unroll(self.config)
     self.grade_report = None      # --grade: the report of the last play_games (solver.grade_games)
+    self.grade_unroll_report = None      # --grade_unroll K: the model by unroll depth on the same games (solver.grade_unroll)
     if not torch.cuda.is_available():
       raise RuntimeError('the evaluator needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
     self.device = torch.device(device if device is not None else 'cuda')
@@ -219,6 +236,7 @@ class Evaluator(SummaryTools):
     keep_history = bool(keep_history or grade or getattr(self.config, 'keep_history', False))
     refuse_opp_playouts(_with(self.config, device_env=device_env))
     refuse_grade(_with(self.config, device_env=device_env))
+    refuse_grade_unroll(self.config)
     assert self.weights is not None, '.load_network() needs to be called before playing.'
     if device_env and environments is not None:
       raise ValueError('play_games: a device-environment run builds no host environment')
@@ -241,6 +259,8 @@ class Evaluator(SummaryTools):
       games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
     if grade:
       self.grade_report = self.grade(games)
+      if getattr(self.config, 'grade_unroll', None):
+        self.grade_unroll_report = self.grade_unroll(games)
     return games
 
   def grade(self, games):
@@ -258,6 +278,28 @@ class Evaluator(SummaryTools):
                                   graded_seat=None if opp is None else -int(opp),
                                   max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)),
                                   table=bool(getattr(cfg, 'grade_table', False)))
+    finally:
+      eng.close()
+    report['seconds'] = time.perf_counter() - t0
+    return report
+
+  def grade_unroll(self, games):
+    """--grade_unroll K: the model unrolled K steps along the moves of the same keep_history games, against the real
+    positions and the exact solver (solver.grade_unroll), in --grade's scope: the positions where the network is to move
+    where --random_opp seats an opponent, both seats' otherwise; truth for TicTacToe everywhere, for ConnectFour at
+    positions with at most config.grade_empties empty cells"""
+    from . import solver
+    cfg = self.config
+    t0 = time.perf_counter()
+    opp = getattr(cfg, 'random_opp', None)
+    eng = Engine.from_config(cfg, min(len(games), self.batch), device=self.device, seed=0)
+    try:
+      eng.set_weights(self.weights)
+      report = solver.grade_unroll(games, cfg.environment, eng, int(cfg.grade_unroll),
+                                   max_empties=None if cfg.environment == 'TicTacToe' else int(getattr(cfg, 'grade_empties', solver.DEFAULT_EMPTIES)),
+                                   graded_seat=None if opp is None else -int(opp),
+                                   max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)),
+                                   table=bool(getattr(cfg, 'grade_table', False)))
     finally:
       eng.close()
     report['seconds'] = time.perf_counter() - t0
@@ -541,6 +583,7 @@ def state_generator(args):
                     c.opp_playouts = args.opp_playouts
                     c.grade, c.grade_empties, c.grade_nodes = args.grade, args.grade_empties, args.grade_nodes
                     c.grade_table = args.grade_table
+                    c.grade_unroll = args.grade_unroll
                     yield state
 
 
@@ -554,6 +597,7 @@ def main(argv=None):
   args = get_evaluation_args(argv)
   refuse_opp_playouts(args, match=args.match)
   refuse_grade(args, match=args.match)
+  refuse_grade_unroll(args)
   if args.match:      # checkpoint against checkpoint (match.py); implies the device path
     from . import match
     return match.main(args)
@@ -583,6 +627,9 @@ def main(argv=None):
       from . import solver
       s['grade'] = evaluator.grade_report
       print(solver.format_report(evaluator.grade_report, evaluator.config.label))
+      if evaluator.grade_unroll_report is not None:
+        s['grade'] = dict(evaluator.grade_report, unroll=evaluator.grade_unroll_report)
+        print(solver.format_unroll(evaluator.grade_unroll_report, evaluator.config.label))
     s['games_per_s'] = len(games) / wall
     s['host_share'] = evaluator.host_seconds / wall
     results.append(s)

@@ -6,7 +6,7 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
 
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
-                                       [--opp_playouts 1024] [--symmetry] [--grade [--grade_table]]
+                                       [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]]
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --symmetry adds train's flag (every sample trained on one of the equivalent images of its position, symmetry.py) to the training run.
@@ -55,25 +55,28 @@ def play_vs_random(weights, agent_side, games=512, sims=30, seed=0, no_support=F
   return int((result == 1).sum()), int((result == 0).sum()), int((result == -1).sum())
 
 
-def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_playouts=0, grade=None, grade_table=False):
+def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_playouts=0, grade=None, grade_table=False,
+                          grade_unroll=None):
   """the same match through the evaluator's device-environment path (any environment with a device form); `weights` a
   state_dict.  Returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second.  opp_playouts > 0: the
   opponent is the playout search of that budget (evaluate --opp_playouts) instead of the random mover.  grade: a list that
   receives the report of the agent's moves graded against the exact solver (evaluate --grade), or None: no grading;
-  grade_table: with the table search (evaluate --grade_table)."""
+  grade_table: with the table search (evaluate --grade_table); grade_unroll: K, the report then carries the model by unroll
+  depth under 'unroll' (evaluate --grade_unroll K)."""
   import copy
   from model_based_rl_amd.evaluate import Evaluator, game_return
   cfg = copy.copy(config)
   for k, v in dict(temperature=0, only_prior=0, only_value=0, use_exploration_noise=0, apply_mcts_actions=1,
                    random_opp=-agent_side, human_opp=None, render=False, save_mcts=False, save_gif_as='', label='vs random',
                    verbose=False, batch=games, device_env=True, keep_history=False, opp_playouts=int(opp_playouts), grade=grade is not None,
-                   grade_table=bool(grade_table) and grade is not None).items():
+                   grade_table=bool(grade_table) and grade is not None,
+                   grade_unroll=int(grade_unroll) if grade_unroll and grade is not None else None).items():
     setattr(cfg, k, v)
   ev = Evaluator({'config': cfg, 'weights': weights, 'training_step': 0})
   ev.load_network()
   ret = np.array([game_return(g) for g in ev.play_games(games, list(range(seed, seed + games)))])
   if grade is not None:
-    grade.append(ev.grade_report)
+    grade.append(ev.grade_report if ev.grade_unroll_report is None else dict(ev.grade_report, unroll=ev.grade_unroll_report))
   return int((ret > 0).sum()), int((ret == 0).sum()), int((ret < 0).sum())
 
 
@@ -95,9 +98,15 @@ def main():
   ap.add_argument('--grade', action='store_true',
                   help='also grade the agent\'s moves of 512 games per side against the exact solver (evaluate --grade), before and after training')
   ap.add_argument('--grade_table', action='store_true', help='--grade: solve with the table search (evaluate --grade_table)')
+  ap.add_argument('--grade_unroll', type=int, default=None, metavar='K',
+                  help='--grade: also the model unrolled K steps along the graded games, by depth (evaluate --grade_unroll K)')
   a = ap.parse_args()
   if a.grade_table and not a.grade:
     ap.error('--grade_table: it chooses the search that --grade solves with and grades nothing without --grade.')
+  if a.grade_unroll is not None and not a.grade:
+    ap.error('--grade_unroll: it unrolls the model along the games --grade keeps and does nothing without --grade.')
+  if a.grade_unroll is not None and not 1 <= a.grade_unroll <= 16:
+    ap.error('--grade_unroll: the depth is 1 to 16 dynamics steps, got %d.' % a.grade_unroll)
   from model_based_rl_amd import train
   from model_based_rl_amd.config import make_config
   from model_based_rl_amd.networks import get_network
@@ -137,7 +146,7 @@ def main():
     for name, sd in (('untrained', untrained_sd), ('trained', state['weights'])):
       for side_, key in ((1, 'agent_first'), (-1, 'agent_second')):
         got = []
-        play_vs_random_device(make_config(base), sd, side_, grade=got, grade_table=a.grade_table)
+        play_vs_random_device(make_config(base), sd, side_, grade=got, grade_table=a.grade_table, grade_unroll=a.grade_unroll)
         graded.setdefault(name, {})[key] = got[0]
   # the last checkpoint against the first kept one, from both seats (match.play_match); where the run kept a single
   # checkpoint, against the untrained network
