@@ -402,6 +402,38 @@ int mz_match_results(mz_match *m, int8_t *result, int32_t *length, int32_t *n_se
                      double *root_values, double *child_visits, int32_t *depths, void *stream);
 int mz_match_log_capacity(const mz_match *m);
 
+/* The true-rules search (DESIGN s7g; csrc/mz_truemodel.hip.h): MCTS.run with the same PUCT, MinMaxStats, tie rules and backup
+ * as mz_search and the same weights, in which a node below the root is a REAL position of TicTacToe (kind 1) or Connect Four
+ * (kind 3): reached by the device rules from its parent's position, evaluated by representation + prediction on its
+ * observation in the mover's view, expanded over its legal actions only (an illegal child: prior 0, to_play 0), and closed
+ * where the game ends -- reward 1 if the move into it won, else 0, value 0, no children.  A finished node takes an expansion
+ * slot at its first visit; a later visit stops there and backs up again without expanding anything.  No dynamics network
+ * runs and no hidden state is kept below the root.  The tree lies in the node pool as mz_search leaves it: mz_eval_walk (one
+ * action), mz_finalize and mz_export_tree read it unchanged.  Evaluation only.
+ *
+ * mz_set_true_model: kind 0 off (the default), 1 or 3: the engine must have that game's shape; allocates the side state
+ * (per expansion slot the position, its child mask, whether it is finished) on first use.  While it is set,
+ * mz_eval_env_moves and mz_match_plies search with it on this engine (mode 0, one action per move); they refuse games of
+ * another kind, CartPole, modes 1 / 2 and max_actions != 1.
+ * mz_tm_root (after mz_root_prepare): [dev] boards [B][42] int8, turn [B] int8, step [B] int32 (plies played) are the roots'
+ * positions; the first descent is made.
+ * mz_tm_search: num_simulations x { leaf inference on the leaves' observations, expand + backup + the next descent }: two
+ * launches per simulation, no host synchronisation.  The move's own root value and logits (mz_root_outputs) stay; hidden
+ * slot 0 is overwritten.
+ * The same loop opened up for outputs the caller computes (recorded ones in the parity tests):
+ *   mz_tm_select        = the descent; outputs (either may be NULL): obs_out [dev][B][obs_dim] float32, the leaves'
+ *                         observations (zeros where the leaf is finished), finished_out [dev][B] uint8
+ *   mz_tm_expand_backup = expand + backup with value [dev][B], logits [dev][B][A] (ignored where the leaf is finished)
+ *   mz_tm_expand_backup_select = both in one launch, then mz_tm_select's outputs; at a move's last simulation it is
+ *                         mz_tm_expand_backup alone and the outputs are left untouched. */
+int mz_set_true_model(mz_engine *e, int kind);
+int mz_tm_root(mz_engine *e, const int8_t *boards, const int8_t *turn, const int32_t *step, void *stream);
+int mz_tm_select(mz_engine *e, float *obs_out, uint8_t *finished_out, void *stream);
+int mz_tm_expand_backup(mz_engine *e, const float *value, const float *logits, void *stream);
+int mz_tm_expand_backup_select(mz_engine *e, const float *value, const float *logits, float *obs_out, uint8_t *finished_out,
+                               void *stream);
+int mz_tm_search(mz_engine *e, int num_simulations, void *stream);
+
 /* MuZero Reanalyse: stored positions of the replay searched again under the engine's CURRENT weights.  rows_host [host, pinned]
  * is [n_rows][rec_floats] record rows as mzr_reanalyse_pick (include/mz_replay.h) wrote them, rec_floats = obs_dim + action_space
  * + MZ_REC_EXTRA; fresh_host [host, pinned] receives [n_rows][action_space + 2] floats per row: child_visits as float32 (the

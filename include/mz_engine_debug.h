@@ -165,6 +165,24 @@ int mz_unroll_terms_host(int A, int items, const float *logits_u, const float *l
                          const uint8_t *live, const int32_t *k, const float *reward_true, const float *reward_u, const float *value_u,
                          const float *value_f, const int8_t *truth, double *terms_out);
 
+/* test hooks of the true-rules search (mz_set_true_model).  mz_tm_export (synchronous, [host] arrays, any may be NULL): the side
+ * state per expansion slot, [B][num_simulations + 1] each -- boards [..][42] int8, mover int8, step int32, mask uint32 (bit a =
+ * child a exists; 0 for a finished position), finished uint8 -- and nexp [B] int32, the slots taken (the root's included).
+ * mz_tm_search_host: the same search as plain sequential C++ on the HOST -- no engine, no device; exp() is the host library's.
+ * cfg: the engine's configuration (num_simulations sizes the trees); n positions of `kind` (1 / 3): boards [n][42], turn [n],
+ * step [n]; root_logits [n][A] float32; noise [n][A] float64 or NULL (no noise).  The root's children are the position's legal
+ * actions.  eval is called once per simulation on the leaves' observations obs [n][obs_dim] (zeros where the leaf is finished)
+ * and fills value [n] and logits [n][A].  Outputs (any may be NULL): the trees in mz_export_tree's layout (N, W, P, R, E, TP
+ * [n][NN], legal_mask [n], minmax [n][2]; E is -1 for a node that was never created), nexp [n], the side state as
+ * mz_tm_export's ([n][num_simulations + 1]), and leaf_depth [n][num_simulations]: len(search_path) - 1 of every simulation. */
+int mz_tm_export(mz_engine *e, int8_t *boards, int8_t *mover, int32_t *step, uint32_t *mask, uint8_t *finished, int32_t *nexp);
+int mz_tm_search_host(const mz_config *cfg, int kind, int n, const int8_t *boards, const int8_t *turn, const int32_t *step,
+                      const float *root_logits, const double *noise, int num_simulations,
+                      void (*eval)(void *ctx, const float *obs, int n, float *value, float *logits), void *ctx,
+                      int32_t *N, double *W, double *P, float *R, int32_t *E, int8_t *TP, uint32_t *legal_mask, double *minmax,
+                      int32_t *nexp_out, int8_t *slot_boards, int8_t *slot_mover, int32_t *slot_step, uint32_t *slot_mask,
+                      uint8_t *slot_finished, int32_t *leaf_depth);
+
 /* test hooks of mz_fcl_set_symmetry.  mz_fcl_symmetry_apply: the symmetry kernel alone, with the handle's kind and seed and the
  * given update number, on device-visible arrays of the handle's batch (obs [batch][obs_dim], actions [batch][K] int32 / int64,
  * target_policies [batch][K + 1][A]; device memory, or mapped pinned host memory as mz_fcl_run's staging is -- the hook looks its

@@ -206,7 +206,7 @@ def make_config(argv=None, **overrides):
 def get_evaluation_args(argv=None):
   """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
   engine; default min(num_games, 4096)), --out (a JSON summary), --device_env / --keep_history (the games on the device
-  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes / --grade_table (moves graded against the exact solver, solver.py), --grade_unroll (the model by unroll depth on the graded games) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
+  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes / --grade_table (moves graded against the exact solver, solver.py), --grade_unroll (the model by unroll depth on the graded games), --true_model (the search on the true rules of the device games) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
   saves_dir + net for every pair."""
   p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
   a = p.add_argument
@@ -256,9 +256,13 @@ def get_evaluation_args(argv=None):
   a('--grade_unroll', type=int, default=None, metavar='K',
     help='--grade: also unroll the model K (1 .. 16) dynamics steps along the moves of the graded games and report, per '
          'depth, reward, value and policy against the real positions and the exact solver (solver.grade_unroll)')
+  a('--true_model', nargs='+', type=int, default=[0],
+    help='--device_env or --match, TicTacToe / ConnectFour: 1 searches the real game below the root -- positions by the '
+         'device rules, legal actions only, true rewards and ends -- with the same weights and the same MCTS (evaluation '
+         'only); one value for all, or with --match one per side')
   a('--match', action='store_true',
     help='play every pair of --nets against each other on the device games (TicTacToe, ConnectFour), every seed from both '
-         'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise then take one '
+         'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise / --true_model then take one '
          'value for both sides or two, one per side')
   a('--opening_plies', type=int, default=0,
     help='--match: uniform random legal plies before the first searched one, the same in both seatings of a seed')

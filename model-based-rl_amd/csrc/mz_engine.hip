@@ -38,6 +38,7 @@
 #include "mz_solve.hip.h"
 #include "mz_unroll.hip.h"
 #include "mz_symmetry.hip.h"
+#include "mz_truemodel.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
@@ -179,6 +180,7 @@ struct mz_engine {
   SolveState sv = {};               // the exact game solver (mz_solve; mz_solve.hip.h), allocated on first use
   SolveTableState svt = {};         // its table search's tables and counters (mz_solve_tt), allocated on its first use
   UnrollState ur = {};              // the unroll diagnostic (mz_unroll; mz_unroll.hip.h), allocated on first use
+  TmState tm = {};                  // the true-rules search (mz_set_true_model, mz_tm_*; mz_truemodel.hip.h), allocated when set
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -732,12 +734,14 @@ static int build_packing(mz_engine *e) {
 
 // BaseNetwork.initial_inference for all B rows; selfplay: + synthetic observation, root expansion, Dirichlet
 // noise and first descent (mz_root.hip.h)
+// (tv: the engine's own view, or a copy whose root_value / root_logits aim elsewhere -- the leaf inference of the true-rules
+// search, mz_tm_search; the view goes to the kernel by value)
 template <int JTP>
-static int launch_root_j(mz_engine *e, const float *obs, bool selfplay, hipStream_t s) {
+static int launch_root_j(mz_engine *e, const TreeView &tv, const float *obs, bool selfplay, hipStream_t s) {
   const dim3 grid(e->Bp / MZ_ROWS), block(256);
   const double alpha = e->cfg.root_dirichlet_alpha, frac = e->cfg.root_exploration_fraction;
 #define MZ_ROOT_GO(G_, SP_)                                                                                     \
-  hipLaunchKernelGGL((k_root<JTP, G_, SP_>), grid, block, 0, s, e->nv, e->tv, obs, e->istream, e->nst0, e->sp, \
+  hipLaunchKernelGGL((k_root<JTP, G_, SP_>), grid, block, 0, s, e->nv, tv, obs, e->istream, e->nst0, e->sp, \
                      (uint64_t)e->cfg.seed, alpha, frac)
   if (!selfplay) MZ_ROOT_GO(4, false);
   else switch (e->G) {
@@ -750,9 +754,10 @@ static int launch_root_j(mz_engine *e, const float *obs, bool selfplay, hipStrea
   HIPCHECK(hipGetLastError());
   return 0;
 }
-static int launch_root(mz_engine *e, const float *obs, bool selfplay, hipStream_t s) {
-  return e->jtp == 1 ? launch_root_j<1>(e, obs, selfplay, s) : launch_root_j<2>(e, obs, selfplay, s);
+static int launch_root(mz_engine *e, const TreeView &tv, const float *obs, bool selfplay, hipStream_t s) {
+  return e->jtp == 1 ? launch_root_j<1>(e, tv, obs, selfplay, s) : launch_root_j<2>(e, tv, obs, selfplay, s);
 }
+static int launch_root(mz_engine *e, const float *obs, bool selfplay, hipStream_t s) { return launch_root(e, e->tv, obs, selfplay, s); }
 
 // dynamic LDS of a HEAD launch: the root's working set (mz_root_body) lies over the trees, behind the pb_c table
 static size_t fused_head_dyn_lds(int sims, int NN, int lt) {
@@ -1287,6 +1292,7 @@ int mz_root_prepare(mz_engine *e, const int8_t *to_play, const uint8_t *legal, c
   e->sims_done = 0;
   e->selection_valid = true;
   e->root_ready = true;
+  e->tm.root_set = false;
   return 0;
 }
 
@@ -1580,7 +1586,7 @@ int mz_eval_walk(mz_engine *e, int max_actions, const double *temperature, const
   if (max_actions < 1) return fail("mz_eval_walk: max_actions must be >= 1");
   const size_t lds = (size_t)(e->sims + 1) * sizeof(int32_t);
   if (lds > 48 * 1024) return fail("mz_eval_walk: num_simulations = %d exceeds the walk's LDS map", e->sims);
-  hipLaunchKernelGGL(k_eval_walk, dim3(e->B), dim3(64), lds, (hipStream_t)stream, e->tv, e->sims_done + 1, max_actions,
+  hipLaunchKernelGGL(k_eval_walk, dim3(e->B), dim3(64), lds, (hipStream_t)stream, e->tv, e->sims_done + 1, e->tm.root_set ? 1 : 0, max_actions,
                      temperature, uniform, e->cfg.seed, move, e->cfg.env_id_offset, actions, pred_rewards, n_actions,
                      path_lengths);
   HIPCHECK(hipGetLastError());
@@ -1662,6 +1668,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 #include "mz_playout_abi.inc"
 #include "mz_solve_abi.inc"
 #include "mz_unroll_abi.inc"
+#include "mz_truemodel_abi.inc"
 #include "mz_eval_abi.inc"
 #include "mz_match_abi.inc"
 #include "mz_reanalyse_abi.inc"

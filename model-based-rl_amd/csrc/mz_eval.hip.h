@@ -30,7 +30,9 @@
 //     float32 reward is the predicted one (0 for a child never expanded: Node.reward's default, mcts.py:34).  Every step
 //     consumes one uniform: uniform [B][M] from the caller, or Philox keyed (seed, env id, move, step) under MZ_RNG_EVAL.
 //     Entries from n_actions on are action -1, reward 0.
-__global__ __launch_bounds__(64) void k_eval_walk(TreeView t, int nexp, int M, const double *temperature,
+// own_nexp (after a true-rules search, mz_tm_search): the tree's own count of expansions, t.nexp[b], where it is smaller --
+// a simulation that revisits a finished node expands nothing, so the trees of a batch differ in it.
+__global__ __launch_bounds__(64) void k_eval_walk(TreeView t, int nexp, int own_nexp, int M, const double *temperature,
                                                   const double *uniform, uint64_t seed, uint64_t move, int env_offset,
                                                   int32_t *actions, float *pred_rewards, int32_t *n_actions,
                                                   int32_t *path_lengths) {
@@ -42,6 +44,7 @@ __global__ __launch_bounds__(64) void k_eval_walk(TreeView t, int nexp, int M, c
   if (b >= t.B) return;
   const int A = t.A;
   const size_t o = mz_slab(t, b);
+  if (own_nexp) nexp = t.nexp[b] < nexp ? t.nexp[b] : nexp;
   // what the walk's first step reads, issued together with the scan below (one memory round trip less on the path)
   const uint32_t legal = t.legal[b];
   const double T = temperature[b];

@@ -26,12 +26,16 @@ struct PlyIO {
   int32_t *path_lengths; // [B][sims of the searching engine]
   double *child_visits;  // [B][A]
   double *root_value;    // [B]
+  // the games themselves, as far as a search on the true rules needs them (ply_search with mz_set_true_model)
+  int kind;              // 1 TicTacToe, 2 CartPole, 3 Connect Four (the numbering of mz_selfplay_set_env)
+  int8_t *board;         // [B][42] (TicTacToe uses the first 9 cells of its row)
+  int8_t *turn;          // [B] the player about to move
+  int32_t *step;         // [B] game.step: plies applied
 };
 
 // ---- evaluation games on the device environments (mz_eval_env_*): the game and everything the summary needs stay here
 // from the first move to the last.  Separate from SelfplayState: self-play on the same engine is untouched.
 struct EvalState : PlyIO {
-  int kind;              // 1 TicTacToe, 2 CartPole, 3 Connect Four (the numbering of mz_selfplay_set_env)
   int max_steps;         // evaluate.py:372: the game is cut when game.step reaches it
   int time_limit;        // CartPole: gym's TimeLimit (envs.CartPole.max_episode_steps)
   int random_opp;        // +1 / -1: that player's moves are the random opponent's; 0: none
@@ -39,11 +43,8 @@ struct EvalState : PlyIO {
   int cap;               // capacity of the per-move / per-step logs: min(max_steps, the game's own longest)
   int sims;
   bool ready;
-  // the game
-  int8_t *board;         // [B][42] (TicTacToe uses the first 9 cells of its row)
-  int8_t *turn;          // [B] the player about to move
+  // the game (PlyIO: kind, board, turn, step)
   double *cart;          // [B][4]
-  int32_t *step;         // [B] game.step
   uint8_t *terminal;     // [B]
   int32_t *live;         // [1] games not yet terminal
   // accumulators, float64, added in move order: [5][B] = sum reward, sum predicted reward, sum predicted value, sum root

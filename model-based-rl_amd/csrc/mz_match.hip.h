@@ -19,15 +19,11 @@
 
 // Separate from EvalState and SelfplayState: evaluation and self-play on the two engines are untouched.
 struct MatchState : PlyIO {
-  int kind;              // 1 TicTacToe, 3 Connect Four (the numbering of mz_selfplay_set_env)
   int max_steps;         // the game is cut (a draw) when its step count reaches it
   int cap;               // capacity of the per-ply logs: min(max_steps, the game's own longest)
   int opening;           // plies applied by k_match_open before the first searched ply
   int S;                 // the larger of the two engines' num_simulations: row length of the depth lists
-  // the game
-  int8_t *board;         // [B][42] (TicTacToe uses the first 9 cells of its row)
-  int8_t *turn;          // [B] the player about to move; +1 moves first
-  int32_t *step;         // [B] plies applied = the game's length once it is over
+  // the game (PlyIO: kind 1 TicTacToe / 3 Connect Four; board; turn, +1 moves first; step = the game's length once it is over)
   uint8_t *terminal;     // [B]
   int32_t *live;         // [1] games not yet terminal
   int8_t *result;        // [B] for player +1, the game's first mover: +1 win, 0 draw (the cut included), -1 loss

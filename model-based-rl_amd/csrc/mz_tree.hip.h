@@ -117,6 +117,10 @@ __device__ __forceinline__ void mz_tree_select(const TreeView &t, int b, int lan
   mz_tree_select<G>(t, b, lane, s_, a_);
 }
 
+template <int G>
+__device__ __forceinline__ void mz_tree_backup_path(const TreeView &t, size_t o, const int32_t *path, int len, int tp,
+                                                    int lane, float reward, double v, double &mn, double &mx);
+
 // Node.expand for the selected leaf (mcts.py:47-55, all actions: mcts.py:97) followed by
 // MCTS.backpropagate (mcts.py:126-143).  value/reward/logits: this tree's network outputs.
 // The path's nodes are fetched G at a time, one record per lane (one round trip per G nodes instead of one per node);
@@ -136,9 +140,24 @@ __device__ __forceinline__ void mz_tree_expand_backup(const TreeView &t, int b, 
   double sum = 0.0;
   for (int a = 0; a < A; ++a) sum = sum + __shfl(p, a, G);
   if (lane < A) mz_node_fresh(t, o + 1 + e * A + lane, p / sum, 1);
-  const double g = t.discount;
   double mn = 0.0, mx = 0.0, v = (double)value;
   if (lane == 0) { mn = t.mn[b]; mx = t.mx[b]; t.nexp[b] = e + 1; }
+  mz_tree_backup_path<G>(t, o, path, len, tp, lane, reward, v, mn, mx);
+  if (lane == 0) {
+    t.E[o + leafnode] = e;
+    t.TP[o + leafnode] = (int8_t)tp;
+    t.R[o + leafnode] = reward;
+    t.mn[b] = mn;
+    t.mx[b] = mx;
+  }
+}
+
+// MCTS.backpropagate (mcts.py:126-143) along path[0 .. len), leaf last: the leaf takes `reward` and to_play tp, every node
+// above it its stored ones.  v (the leaf's value), mn / mx (MinMaxStats) are lane 0's; it stores W and N of the path's nodes.
+template <int G>
+__device__ __forceinline__ void mz_tree_backup_path(const TreeView &t, size_t o, const int32_t *path, int len, int tp,
+                                                    int lane, float reward, double v, double &mn, double &mx) {
+  const double g = t.discount;
   for (int base = 0; base < len; base += G) {
     const int j = base + lane;
     const int mynode = path[len - 1 - (j < len ? j : len - 1)];
@@ -168,13 +187,6 @@ __device__ __forceinline__ void mz_tree_expand_backup(const TreeView &t, int b, 
         v = r + g * v;
       }
     }
-  }
-  if (lane == 0) {
-    t.E[o + leafnode] = e;
-    t.TP[o + leafnode] = (int8_t)tp;
-    t.R[o + leafnode] = reward;
-    t.mn[b] = mn;
-    t.mx[b] = mx;
   }
 }
 

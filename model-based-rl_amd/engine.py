@@ -117,6 +117,78 @@ def _ptr(t):
   return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def mz_config(num_envs, obs_dim, action_space, num_simulations, two_players=False, known_bounds=(None, None),
+              value_support=(-15, 15), reward_support=(-15, 15), no_target_transform=False, no_support=False, discount=0.997,
+              pb_c_base=19652, pb_c_init=1.25, init_value_score=0.0, root_dirichlet_alpha=0.25, root_exploration_fraction=0.25,
+              seed=0, env_id_offset=0, split_f16=False):
+  """the mz_config (include/mz_engine.h) of an engine with these arguments (Engine.__init__'s); needs no GPU"""
+  lo, hi = known_bounds
+  return _abi.MzConfig(
+      int(num_envs), int(obs_dim), int(action_space), int(num_simulations), int(bool(two_players)), int(lo is not None),
+      int(hi is not None), int(value_support[0]), int(value_support[1]), int(reward_support[0]), int(reward_support[1]),
+      int(bool(no_target_transform)), 0.0 if lo is None else float(lo), 0.0 if hi is None else float(hi),
+      float(discount), float(pb_c_base), float(pb_c_init), float(init_value_score), float(root_dirichlet_alpha),
+      float(root_exploration_fraction), int(seed), int(env_id_offset), int(bool(no_support)), int(bool(split_f16)))
+
+
+_TM_EVAL = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
+
+
+def tm_search_host(cfg, kind, boards, turn, step, root_logits, eval_fn, num_simulations=None, noise=None):
+  """mz_tm_search_host (include/mz_engine_debug.h): the true-rules search of n positions as sequential C++ on the host, no
+  GPU.  cfg: an mz_config (mz_config(...) above; its num_simulations sizes the trees); kind 1 / 3; boards [n, 42], turn [n],
+  step [n]; root_logits [n, A] float32; noise [n, A] float64 or None; eval_fn(obs [n, O] float32) -> (value [n], logits
+  [n, A]) is called once per simulation on the leaves' observations.  Returns a dict of numpy arrays: the trees as
+  export_tree's (N, W, P, R, E, TP [n, NN], legal [n], minmax [n, 2]), nexp [n], the side state per expansion slot as
+  tm_export's (boards [n, sims + 1, 42], mover, step, mask, finished [n, sims + 1]), leaf_depth [n, sims] and EX [n, NN]."""
+  lib = _abi.load()
+  k = KIND_OF_ENV[kind] if isinstance(kind, str) else int(kind)
+  bd = np.ascontiguousarray(boards, np.int8)
+  tn, st = np.ascontiguousarray(turn, np.int8), np.ascontiguousarray(step, np.int32)
+  n, A, O, S = bd.shape[0], cfg.action_space, cfg.obs_dim, cfg.num_simulations
+  lg = np.ascontiguousarray(root_logits, np.float32)
+  nz = None if noise is None else np.ascontiguousarray(noise, np.float64)
+  if bd.shape != (n, 42) or tn.shape != (n,) or st.shape != (n,) or lg.shape != (n, A) or (nz is not None and nz.shape != (n, A)):
+    raise ValueError('tm_search_host: boards [n, 42], turn [n], step [n], root_logits [n, A], noise [n, A]')
+  sims = S if num_simulations is None else int(num_simulations)
+  NN = 1 + (S + 1) * A
+  d = dict(N=np.zeros((n, NN), np.int32), W=np.zeros((n, NN)), P=np.zeros((n, NN)), R=np.zeros((n, NN), np.float32),
+           E=np.zeros((n, NN), np.int32), TP=np.zeros((n, NN), np.int8), legal=np.zeros(n, np.uint32), minmax=np.zeros((n, 2)),
+           nexp=np.zeros(n, np.int32), boards=np.zeros((n, S + 1, 42), np.int8), mover=np.zeros((n, S + 1), np.int8),
+           step=np.zeros((n, S + 1), np.int32), mask=np.zeros((n, S + 1), np.uint32), finished=np.zeros((n, S + 1), np.uint8),
+           leaf_depth=np.zeros((n, S), np.int32))
+  failure = []
+
+  def cb(_ctx, obs, rows, value, logits):
+    try:
+      v, l = eval_fn(np.ctypeslib.as_array(obs, (rows, O)).copy())
+      np.ctypeslib.as_array(value, (rows,))[:] = np.asarray(v, np.float32).reshape(rows)
+      np.ctypeslib.as_array(logits, (rows, A))[:] = np.asarray(l, np.float32).reshape(rows, A)
+    except Exception as ex:      # (an exception cannot cross the C frames)
+      failure.append(ex)
+  p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+  cb_c = _TM_EVAL(cb)      # (kept alive across the call)
+  _abi.check(lib.mz_tm_search_host(C.byref(cfg), k, n, p(bd), p(tn), p(st), p(lg), p(nz), sims, C.cast(cb_c, C.c_void_p), None,
+                                   *[p(d[key]) for key in ('N', 'W', 'P', 'R', 'E', 'TP', 'legal', 'minmax', 'nexp', 'boards', 'mover',
+                                                           'step', 'mask', 'finished', 'leaf_depth')]), 'mz_tm_search_host')
+  if failure:
+    raise failure[0]
+  d['EX'] = tm_exists(d['mask'], d['nexp'], A, NN)
+  return d
+
+
+def tm_exists(mask, nexp, A, NN):
+  """EX [n, NN] of a true-rules tree: the root, and child a of every taken expansion slot whose mask has bit a"""
+  n = mask.shape[0]
+  EX = np.zeros((n, NN), np.uint8)
+  EX[:, 0] = 1
+  for b in range(n):
+    for e in range(int(nexp[b])):
+      for a in range(A):
+        EX[b, 1 + e * A + a] = (int(mask[b, e]) >> a) & 1
+  return EX
+
+
 class Engine(object):
 
   def __init__(self, num_envs, obs_dim, action_space, num_simulations, two_players=False,
@@ -137,12 +209,9 @@ class Engine(object):
     # outputs of the value / reward heads: the support sizes, one scalar each with --no_support (networks.py:135-136)
     self._outputs = (1, 1) if no_support else (int(value_support[1]) - int(value_support[0]) + 1,
                                                 int(reward_support[1]) - int(reward_support[0]) + 1)
-    self.cfg = _abi.MzConfig(
-        self.B, self.O, self.A, self.sims, int(bool(two_players)), int(lo is not None), int(hi is not None),
-        int(value_support[0]), int(value_support[1]), int(reward_support[0]), int(reward_support[1]),
-        int(bool(no_target_transform)), 0.0 if lo is None else float(lo), 0.0 if hi is None else float(hi),
-        float(discount), float(pb_c_base), float(pb_c_init), float(init_value_score), float(root_dirichlet_alpha),
-        float(root_exploration_fraction), int(seed), int(env_id_offset), int(bool(no_support)), int(bool(split_f16)))
+    self.cfg = mz_config(self.B, self.O, self.A, self.sims, two_players, known_bounds, value_support, reward_support,
+                         no_target_transform, no_support, discount, pb_c_base, pb_c_init, init_value_score,
+                         root_dirichlet_alpha, root_exploration_fraction, seed, env_id_offset, split_f16)
     # (the library also honours MZ_SPLIT_F16=1, for running the parity suite on that kernel)
     self.split_f16 = bool(split_f16) or os.environ.get('MZ_SPLIT_F16', '0')[:1] == '1'
     h = C.c_void_p()
@@ -349,6 +418,60 @@ class Engine(object):
     _abi.check(self.lib.mz_expand_backup_select(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), *ptrs, self.stream),
                'mz_expand_backup_select')
     return out
+
+  # ---- the true-rules search (mz_set_true_model, mz_tm_*, include/mz_engine.h; DESIGN s7g)
+  def set_true_model(self, kind):
+    """mz_set_true_model: kind 0 / None off, an EVAL_ENVS name or 1 (TicTacToe) / 3 (Connect Four).  While set,
+    eval_env_moves and Match.plies search the games' real positions on this engine."""
+    k = 0 if not kind else (self.EVAL_ENVS[kind] if isinstance(kind, str) else int(kind))
+    _abi.check(self.lib.mz_set_true_model(self._h, k), 'mz_set_true_model')
+    self.true_model = k
+
+  def tm_root(self, boards, turn, step):
+    """mz_tm_root (after root_prepare): the roots' positions, boards [B, 42] int8, turn [B] int8, step [B] int32"""
+    bd = self._dev(np.ascontiguousarray(boards, np.int8).reshape(self.B, 42), torch.int8)
+    tn = self._dev(np.ascontiguousarray(turn, np.int8).reshape(self.B), torch.int8)
+    st = self._dev(np.ascontiguousarray(step, np.int32).reshape(self.B), torch.int32)
+    _abi.check(self.lib.mz_tm_root(self._h, _ptr(bd), _ptr(tn), _ptr(st), self.stream), 'mz_tm_root')
+
+  def _tm_leaf_out(self):
+    return (torch.empty(self.B, self.O, dtype=torch.float32, device=self.device),
+            torch.empty(self.B, dtype=torch.uint8, device=self.device))
+
+  def tm_select(self):
+    """mz_tm_select -> (obs [B, O] float32: the leaves' observations, zeros where finished; finished [B] uint8)"""
+    obs, fin = self._tm_leaf_out()
+    _abi.check(self.lib.mz_tm_select(self._h, _ptr(obs), _ptr(fin), self.stream), 'mz_tm_select')
+    return obs, fin
+
+  def tm_expand_backup(self, value, logits):
+    value = self._dev(value, torch.float32); logits = self._dev(logits, torch.float32)
+    _abi.check(self.lib.mz_tm_expand_backup(self._h, _ptr(value), _ptr(logits), self.stream), 'mz_tm_expand_backup')
+
+  def tm_expand_backup_select(self, value, logits, last=False):
+    """tm_expand_backup of this simulation and tm_select of the next in one launch; returns what tm_select returns, or None
+    after the move's last simulation (`last`: the caller's count of simulations)"""
+    value = self._dev(value, torch.float32); logits = self._dev(logits, torch.float32)
+    out = None if last else self._tm_leaf_out()
+    ptrs = [None, None] if last else [_ptr(o) for o in out]
+    _abi.check(self.lib.mz_tm_expand_backup_select(self._h, _ptr(value), _ptr(logits), *ptrs, self.stream),
+               'mz_tm_expand_backup_select')
+    return out
+
+  def tm_search(self, num_simulations=None):
+    n = self.sims if num_simulations is None else int(num_simulations)
+    _abi.check(self.lib.mz_tm_search(self._h, n, self.stream), 'mz_tm_search')
+
+  def tm_export(self):
+    """mz_tm_export -> dict of numpy arrays per expansion slot: boards [B, sims + 1, 42], mover, step, mask, finished
+    [B, sims + 1], and nexp [B]; EX [B, NN]: the nodes that exist (export_tree's EX counts every child of an expanded node)"""
+    B, S = self.B, self.sims + 1
+    d = dict(boards=np.zeros((B, S, 42), np.int8), mover=np.zeros((B, S), np.int8), step=np.zeros((B, S), np.int32),
+             mask=np.zeros((B, S), np.uint32), finished=np.zeros((B, S), np.uint8), nexp=np.zeros(B, np.int32))
+    _abi.check(self.lib.mz_tm_export(self._h, *[d[k].ctypes.data_as(C.c_void_p) for k in ('boards', 'mover', 'step', 'mask', 'finished', 'nexp')]),
+               'mz_tm_export')
+    d['EX'] = tm_exists(d['mask'], d['nexp'], self.A, self.NN)
+    return d
 
   def finalize(self, temperature, uniform=None, move=0):
     if torch.is_tensor(temperature):

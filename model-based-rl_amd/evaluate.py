@@ -135,6 +135,36 @@ def refuse_grade_unroll(args_or_config):
     raise NotImplementedError('--grade_unroll: the depth is 1 to %d dynamics steps, got %d.' % (Engine.UNROLL_MAX_K, int(K)))
 
 
+TRUE_MODEL_ENVS = BOARD_ENVS
+
+
+def refuse_true_model(args_or_config, match=False):
+  """one sentence per configuration --true_model (the search on the true rules of the device games, Engine.tm_search) leaves
+  out (NotImplementedError, starting '--true_model: '); nothing to refuse while every value is 0.  The lists of the command
+  line are read per side with --match (one value: both sides) and as alternatives without it."""
+  c = args_or_config
+  alls = lambda x: list(x) if isinstance(x, (list, tuple)) else [x]
+  tm = [int(x or 0) for x in alls(getattr(c, 'true_model', 0))]
+  if not any(tm):
+    return
+  if any(x not in (0, 1) for x in tm):
+    raise NotImplementedError('--true_model: the values are 0 (the learned model) and 1 (the true rules), got %r.' % (tm,))
+  if not match and not getattr(c, 'device_env', False):
+    raise NotImplementedError('--true_model: the true-rules search reads the device games\' positions and needs --device_env (or --match).')
+  env = getattr(c, 'environment', None)
+  if env is not None and env not in TRUE_MODEL_ENVS:
+    raise NotImplementedError('--true_model: %s has no true-rules search; it searches %s.' % (env, ' and '.join(TRUE_MODEL_ENVS)))
+  if any(int(x) != 1 for x in alls(getattr(c, 'apply_mcts_actions', 1))):
+    raise NotImplementedError('--true_model: a move of the true-rules search applies one action and takes --apply_mcts_actions 1 only.')
+  prior, value = [int(x or 0) for x in alls(getattr(c, 'only_prior', 0))], [int(x or 0) for x in alls(getattr(c, 'only_value', 0))]
+  pick = lambda v, k: v[k if len(v) == 2 else 0]
+  sides = range(2) if match else [0]
+  if any(pick(tm, k) and ((pick(prior, k) or pick(value, k)) if match else (any(prior) or any(value))) for k in sides):
+    raise NotImplementedError('--true_model: --only_prior / --only_value run no search; a side takes one of them or the true-rules search.')
+  if getattr(c, 'architecture', 'FCNetwork') != 'FCNetwork':
+    raise NotImplementedError('--true_model: the architecture %s has no engine path; FCNetwork checkpoints only.' % c.architecture)
+
+
 class DeviceGame(object):
   """A finished game of the device-environment path: what the summary and the CLI read, from the device's accumulators.
   With keep_history also the per-move lists under the host path's names (history.actions / rewards / to_play / dones /
@@ -199,6 +229,7 @@ class Evaluator(SummaryTools):
     refuse_opp_playouts(_with(self.config, device_env=True))      # (play_games(device_env=True) may still name the device path)
     refuse_grade(_with(self.config, device_env=True))
     refuse_grade_unroll(self.config)
+    refuse_true_model(_with(self.config, device_env=True))
     self.grade_report = None      # --grade: the report of the last play_games (solver.grade_games)
     self.grade_unroll_report = None      # --grade_unroll K: the model by unroll depth on the same games (solver.grade_unroll)
     if not torch.cuda.is_available():
@@ -224,14 +255,17 @@ class Evaluator(SummaryTools):
                            draws=None if draws is None else [draws])[0]
 
   def play_games(self, num_games, seeds=None, environments=None, draws=None, device_env=False, keep_history=False,
-                 start_states=None):
+                 start_states=None, true_model=False):
     """num_games games, up to self.batch of them in lock-step per engine.  seeds: one per game, consecutive (seed + i); None
     draws a base seed.  draws (parity runs): per game a dict of recorded draws -- 'walk' [moves][M] uniforms, 'noise' [moves][A]
     Dirichlet draws at the legal positions, 'opp' the random opponent's choices (indices into the legal actions).
     device_env (or config.device_env): the games live on the device environments and come back as DeviceGame records, with
     keep_history (or config.keep_history) carrying the per-move lists; start_states [num_games][4]: CartPole's start states
-    instead of the counter RNG's (device path only)."""
+    instead of the counter RNG's (device path only).  true_model (or config.true_model): the moves are searched on the true
+    rules (Engine.tm_search; device path, TicTacToe / ConnectFour)."""
     device_env = bool(device_env or getattr(self.config, 'device_env', False))
+    true_model = bool(true_model or getattr(self.config, 'true_model', 0))
+    refuse_true_model(_with(self.config, device_env=device_env, true_model=int(true_model)))
     grade = bool(getattr(self.config, 'grade', False))
     keep_history = bool(keep_history or grade or getattr(self.config, 'keep_history', False))
     refuse_opp_playouts(_with(self.config, device_env=device_env))
@@ -253,7 +287,7 @@ class Evaluator(SummaryTools):
       hi = min(num_games, lo + self.batch)
       if device_env:
         games += self._play_batch_device(seeds[lo:hi], None if draws is None else draws[lo:hi],
-                                         None if start_states is None else start_states[lo:hi], keep_history)
+                                         None if start_states is None else start_states[lo:hi], keep_history, true_model)
         continue
       envs = environments[lo:hi] if environments is not None else [get_environment(self.config) for _ in range(lo, hi)]
       games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
@@ -305,10 +339,11 @@ class Evaluator(SummaryTools):
     report['seconds'] = time.perf_counter() - t0
     return report
 
-  def _play_batch_device(self, seeds, draws, start_states, keep_history):
+  def _play_batch_device(self, seeds, draws, start_states, keep_history, true_model=False):
     """_play_batch with the games on the device environments: whole moves are enqueued MOVES_PER_SYNC at a time
     (Engine.eval_env_moves: observe, initial inference, root, search + walk or lookahead, finalize, apply), and the host
-    only reads the number of games still live after each chunk"""
+    only reads the number of games still live after each chunk.  true_model: the engine searches the games' real positions
+    (Engine.set_true_model); everything around the search is the same."""
     cfg = self.config
     refuse_device_env(_with(cfg, device_env=True))
     refuse_opp_playouts(_with(cfg, device_env=True))
@@ -326,6 +361,8 @@ class Evaluator(SummaryTools):
     # the device RNG's key: (engine seed 0, env id = the game's seed, move, step)
     eng = Engine.from_config(cfg, B, device=self.device, seed=0, env_id_offset=seeds[0])
     eng.set_weights(self.weights)
+    if true_model:
+      eng.set_true_model(cfg.environment)
     eng.eval_env_reset(cfg.environment, int(cfg.max_steps), CARTPOLE_TIME_LIMITS.get(cfg.environment, 0),
                        getattr(cfg, 'random_opp', None) if two else None, keep_history)
     if opp_playouts:
@@ -541,6 +578,8 @@ def get_label(state, detailed=False, path_idx=None):
         label_parts.append('temp:{}'.format(state['config'].temperature))
       if state['config'].use_exploration_noise:
         label_parts.append('with noise')
+      if getattr(state['config'], 'true_model', 0):
+        label_parts.append('true rules')
   return ', '.join(label_parts)
 
 
@@ -555,7 +594,7 @@ def state_generator(args):
           for only_prior in args.only_prior:
             for only_value in args.only_value:
               for use_exploration_noise in args.use_exploration_noise:
-                for apply_mcts_actions in args.apply_mcts_actions:
+                for apply_mcts_actions, true_model in ((m, t) for m in args.apply_mcts_actions for t in getattr(args, 'true_model', [0])):
                   if not (only_prior and only_value):
                     state = copy.deepcopy(meta_state)
                     c = state['config']
@@ -567,6 +606,7 @@ def state_generator(args):
                     c.only_prior = only_prior
                     c.use_exploration_noise = use_exploration_noise
                     c.apply_mcts_actions = apply_mcts_actions
+                    c.true_model = int(true_model)
                     c.render = args.render
                     c.save_mcts = args.save_mcts
                     c.save_mcts_after_step = args.save_mcts_after_step
@@ -598,6 +638,7 @@ def main(argv=None):
   refuse_opp_playouts(args, match=args.match)
   refuse_grade(args, match=args.match)
   refuse_grade_unroll(args)
+  refuse_true_model(args, match=args.match)
   if args.match:      # checkpoint against checkpoint (match.py); implies the device path
     from . import match
     return match.main(args)
@@ -616,6 +657,9 @@ def main(argv=None):
     s = evaluator.print_summary(games)
     s['label'] = evaluator.config.label
     s['num_games'] = len(games)
+    s['true_model'] = int(getattr(evaluator.config, 'true_model', 0))
+    if args.device_env:
+      print("Search below the root: {}\n".format('the true rules of the game (--true_model)' if s['true_model'] else 'the learned model'))
     if evaluator.config.two_players and args.random_opp is not None:
       returns = np.array([game_return(g) for g in games])
       s['wins'], s['draws'], s['losses'] = int((returns > 0).sum()), int((returns == 0).sum()), int((returns < 0).sum())

@@ -11,7 +11,8 @@ Evaluator.play_games(device_env=True).  The opening plies (--opening_plies) are 
 game's seed alone (MZ_RNG_OPEN): both seatings of a seed start from the same position.
 
 Per-side settings come from each state's config: num_simulations, temperature, only_prior, only_value,
-use_exploration_noise.  One action is applied per ply, on FCNetwork checkpoints."""
+use_exploration_noise, true_model (that side searches the true rules of the game, Engine.tm_search: the same checkpoint on
+both sides with true_model (0, 1) prices its learned model in Elo).  One action is applied per ply, on FCNetwork checkpoints."""
 import copy
 import json
 import math
@@ -173,15 +174,24 @@ def _records(r, seeds, seating, opening, sides, sims, keep_history):
 
 
 def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=None, keep_history=False, batch=None,
-               device=None, stats=None):
+               device=None, stats=None, true_model=None):
   """num_games seeds, each played in both seatings (2 * num_games games), up to `batch` games of one seating in lock-step.
   seeds: consecutive, one per game; None draws a base seed.  draws (parity runs): per seed a dict of given draws -- 'walk'
   [plies] uniforms and 'noise' [plies][A] Dirichlet draws, both indexed by the ply with the opening plies counted, and
   'opening' [k] indices into the legal actions of the opening positions -- used in both seatings.  Returns (games, summary):
   MatchGame records in the order (batch, seating, seed) and summarize(games).  stats: a dict that receives plies (game plies
-  played), device_seconds and syncs."""
+  played), device_seconds and syncs.  true_model: (a, b), whether that side searches the true rules of the game instead
+  of its learned model (Engine.tm_search; evaluate --true_model); None: each state's config.true_model."""
+  from .evaluate import refuse_true_model
   ca, cb = state_a['config'], state_b['config']
   refuse_match(ca, cb)
+  if true_model is None:
+    true_model = (getattr(ca, 'true_model', 0), getattr(cb, 'true_model', 0))
+  true_model = tuple(int(bool(x)) for x in true_model)
+  if len(true_model) != 2:
+    raise ValueError('play_match: true_model takes one value per side, got %r' % (true_model,))
+  for c, t in zip((ca, cb), true_model):
+    refuse_true_model(_with_true_model(c, t), match=True)
   if not torch.cuda.is_available():
     raise RuntimeError('a match needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
   device = torch.device(device if device is not None else 'cuda')
@@ -206,8 +216,10 @@ def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=N
     B = len(sd)
     # the device RNG's key: (engine seed 0, env id = the game's seed, ply, step)
     engines = [Engine.from_config(c, B, device=device, seed=0, env_id_offset=sd[0]) for c in (ca, cb)]
-    for e, w in zip(engines, weights):
+    for e, w, t in zip(engines, weights, true_model):
       e.set_weights(w)
+      if t:
+        e.set_true_model(ca.environment)
     match = Match(engines[0], engines[1], ca.environment, max_steps, keep_history)
     packed = None if draws is None else _pack_draws(draws[lo:lo + batch], B, A)
     for seating in (0, 1):
@@ -231,7 +243,13 @@ def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=N
       e.close()
   if stats is not None:
     stats.update(plies=plies, device_seconds=t_dev, syncs=syncs)
-  return games, summarize(games)
+  return games, dict(summarize(games), true_model=list(true_model))
+
+
+def _with_true_model(cfg, t):
+  c = copy.copy(cfg)
+  c.true_model = int(t)
+  return c
 
 
 def _pick(values, side):
@@ -270,6 +288,7 @@ def side_state(state, args, side):
   c.temperature = float(_pick(args.temperatures, side))
   c.only_prior, c.only_value = int(_pick(args.only_prior, side)), int(_pick(args.only_value, side))
   c.use_exploration_noise = int(_pick(args.use_exploration_noise, side))
+  c.true_model = int(_pick(getattr(args, 'true_model', [0]), side))
   c.apply_mcts_actions = 1
   c.random_opp = c.human_opp = None
   c.batch = args.batch
@@ -278,8 +297,9 @@ def side_state(state, args, side):
 
 def _side_label(label, cfg):
   mode = 'only prior' if cfg.only_prior else 'only value' if cfg.only_value else 'sims:%d' % cfg.num_simulations
-  return '%s, %s%s%s' % (label, mode, ', temp:%g' % cfg.temperature if cfg.temperature else '',
-                         ', with noise' if cfg.use_exploration_noise else '')
+  return '%s, %s%s%s%s' % (label, mode, ', temp:%g' % cfg.temperature if cfg.temperature else '',
+                           ', with noise' if cfg.use_exploration_noise else '',
+                           ', true rules' if getattr(cfg, 'true_model', 0) else '')
 
 
 def main(args):
