@@ -434,6 +434,42 @@ int mz_tm_expand_backup_select(mz_engine *e, const float *value, const float *lo
                                void *stream);
 int mz_tm_search(mz_engine *e, int num_simulations, void *stream);
 
+/* The Gumbel MuZero search (DESIGN s7h; csrc/mz_gumbel.hip.h; Danihelka et al., ICLR 2022) beside mz_search, on the same
+ * node pool, weights, expansion and backup: at the root, simulation s goes to the legal action with the largest
+ * g(a) + logit(a) + sigma(a) among those visited seq(m, num_simulations)[s] times (Gumbel-top-m with sequential halving,
+ * m = min(max_considered, legal actions)); below the root to arg-max pi'(a) - N(a) / (1 + sum N); the move's action is the
+ * arg-max of g + logit + sigma among the most visited.  sigma(a) = (c_visit + max N) * c_scale * normalize(completedQ(a))
+ * with the tree's MinMaxStats; pi' = softmax over the existing children of log P + sigma; g = gumbel_scale * G.  Every
+ * arg-max breaks ties to the largest action.  Evaluation only.
+ *
+ * mz_set_gumbel: on 0 / 1; max_considered >= 2, c_visit >= 0, c_scale > 0, gumbel_scale >= 0 (0: no draw, deterministic).
+ * Allocates the side state on first use.  Refused while the true-rules search is set, and mz_set_true_model while this is.
+ * While it is set, mz_eval_env_moves and mz_match_plies search with it on this engine (mode 0, one action per move, no
+ * exploration noise; G drawn on the device, keyed (seed, env id, move, action): a game's draws do not depend on its batch).
+ * mz_gz_root (after mz_root_prepare WITHOUT noise; refused otherwise): gumbel [dev][B][A] float64 = G, or NULL: drawn on the
+ * device with `move` in the key (nothing is drawn with gumbel_scale 0); makes the first descent.
+ * mz_gz_search: num_simulations x { recurrent inference on the selected rows, expand + backup + the next descent }: two
+ * launches per simulation, no host synchronisation.
+ * The same loop opened up for outputs the caller computes:
+ *   mz_gz_select        = the descent; outputs (either may be NULL): parent_slot, action [dev][B] int32 (mz_gather_hidden
+ *                         gives the parents' hidden states)
+ *   mz_gz_expand_backup = expand + backup with value, reward [dev][B], logits [dev][B][A], hidden [dev][B][50] or NULL (the
+ *                         caller has stored it)
+ *   mz_gz_expand_backup_select = both in one launch, then mz_gz_select's outputs; at a move's last simulation it is
+ *                         mz_gz_expand_backup alone and the outputs are left untouched.
+ * mz_gz_pick (any output may be NULL): action [dev][B] int32, pred_reward [dev][B] float32 (the chosen child's reward),
+ * improved_policy [dev][B][A] float64 (pi' of the root, 0 on illegal actions), v_mix [dev][B] float64.  mz_finalize still
+ * gives the visit fractions and the root's mean value. */
+int mz_set_gumbel(mz_engine *e, int on, int max_considered, double c_visit, double c_scale, double gumbel_scale);
+int mz_gz_root(mz_engine *e, const double *gumbel, uint64_t move, void *stream);
+int mz_gz_select(mz_engine *e, int32_t *parent_slot, int32_t *action, void *stream);
+int mz_gz_expand_backup(mz_engine *e, const float *value, const float *reward, const float *logits, const float *hidden,
+                        void *stream);
+int mz_gz_expand_backup_select(mz_engine *e, const float *value, const float *reward, const float *logits, const float *hidden,
+                               int32_t *parent_slot, int32_t *action, void *stream);
+int mz_gz_search(mz_engine *e, int num_simulations, void *stream);
+int mz_gz_pick(mz_engine *e, int32_t *action, float *pred_reward, double *improved_policy, double *v_mix, void *stream);
+
 /* MuZero Reanalyse: stored positions of the replay searched again under the engine's CURRENT weights.  rows_host [host, pinned]
  * is [n_rows][rec_floats] record rows as mzr_reanalyse_pick (include/mz_replay.h) wrote them, rec_floats = obs_dim + action_space
  * + MZ_REC_EXTRA; fresh_host [host, pinned] receives [n_rows][action_space + 2] floats per row: child_visits as float32 (the

@@ -183,6 +183,29 @@ int mz_tm_search_host(const mz_config *cfg, int kind, int n, const int8_t *board
                       int32_t *nexp_out, int8_t *slot_boards, int8_t *slot_mover, int32_t *slot_step, uint32_t *slot_mask,
                       uint8_t *slot_finished, int32_t *leaf_depth);
 
+/* test hooks of the Gumbel search (mz_set_gumbel).  mz_gz_export (synchronous, [host], either may be NULL): gumbel [B][A]
+ * float64, this move's G (0 with gumbel_scale 0), and vhat [B][num_simulations + 1] float32, the raw network value per
+ * expansion slot.  mz_gz_seq_host: out[n] = seq(m, n), mctx's sequence of considered visits.
+ * mz_gz_search_host: the same search as plain sequential C++ on the HOST -- no engine, no device; exp() is the host library's.
+ * cfg: the engine's configuration (num_simulations sizes the trees); n roots: to_play [n] int8 (NULL: 1), legal [n][A] uint8
+ * (NULL: all), root_value [n], root_logits [n][A] float32, gumbel [n][A] float64 = G (NULL only with gumbel_scale 0).  eval is
+ * called once per simulation with the descents' parent_slot [n] and action [n] and fills value [n], reward [n], logits
+ * [n][A].  Outputs (any may be NULL): the trees in mz_export_tree's layout (N, W, P, R, E, TP [n][NN], legal_mask [n], minmax
+ * [n][2]), vhat [n][num_simulations + 1], per simulation sel_slot / sel_action [n][num_simulations], the search paths
+ * [n][num_simulations][num_simulations + 2] (-1 behind their end) with plens [n][num_simulations], mz_gz_pick's four outputs,
+ * and min_gap [1]: the smallest non-zero difference between the best and the second-best score over every arg-max taken
+ * (inf if there was none). */
+int mz_gz_export(mz_engine *e, double *gumbel, float *vhat);
+int mz_gz_seq_host(int m, int n, int32_t *out);
+int mz_gz_search_host(const mz_config *cfg, int n, const int8_t *to_play, const uint8_t *legal, const float *root_value,
+                      const float *root_logits, const double *gumbel, int max_considered, double c_visit, double c_scale,
+                      double gumbel_scale, int num_simulations,
+                      void (*eval)(void *ctx, int sim, const int32_t *parent_slot, const int32_t *action, int n, float *value,
+                                   float *reward, float *logits),
+                      void *ctx, int32_t *N, double *W, double *P, float *R, int32_t *E, int8_t *TP, uint32_t *legal_mask,
+                      double *minmax, float *vhat_out, int32_t *sel_slot, int32_t *sel_action, int32_t *paths, int32_t *plens,
+                      int32_t *action_out, float *pred_reward, double *improved_policy, double *v_mix, double *min_gap);
+
 /* test hooks of mz_fcl_set_symmetry.  mz_fcl_symmetry_apply: the symmetry kernel alone, with the handle's kind and seed and the
  * given update number, on device-visible arrays of the handle's batch (obs [batch][obs_dim], actions [batch][K] int32 / int64,
  * target_policies [batch][K + 1][A]; device memory, or mapped pinned host memory as mz_fcl_run's staging is -- the hook looks its

@@ -206,7 +206,7 @@ def make_config(argv=None, **overrides):
 def get_evaluation_args(argv=None):
   """The reference's evaluation flags (config.py:233-262) with its defaults, plus --batch (games played in lock-step on one
   engine; default min(num_games, 4096)), --out (a JSON summary), --device_env / --keep_history (the games on the device
-  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes / --grade_table (moves graded against the exact solver, solver.py), --grade_unroll (the model by unroll depth on the graded games), --true_model (the search on the true rules of the device games) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
+  environments, evaluate.py), --opp_playouts (a playout-search opponent in --random_opp's seat), --grade / --grade_empties / --grade_nodes / --grade_table (moves graded against the exact solver, solver.py), --grade_unroll (the model by unroll depth on the graded games), --true_model (the search on the true rules of the device games), --gumbel / --gumbel_considered / --gumbel_c_visit / --gumbel_c_scale / --gumbel_scale (the Gumbel MuZero search) and --match / --opening_plies (matches between the nets, match.py).  Checkpoints are
   saves_dir + net for every pair."""
   p = argparse.ArgumentParser(description='evaluate saved networks on the GPU (reference evaluate.py)')
   a = p.add_argument
@@ -260,9 +260,19 @@ def get_evaluation_args(argv=None):
     help='--device_env or --match, TicTacToe / ConnectFour: 1 searches the real game below the root -- positions by the '
          'device rules, legal actions only, true rewards and ends -- with the same weights and the same MCTS (evaluation '
          'only); one value for all, or with --match one per side')
+  a('--gumbel', nargs='+', type=int, default=[0],
+    help='--device_env or --match: 1 searches with the Gumbel MuZero search (Gumbel-top-k with sequential halving at the '
+         'root, a deterministic rule below it, the move chosen by the rule) instead of PUCT, with the same weights '
+         '(evaluation only); one value for all, or with --match one per side')
+  a('--gumbel_considered', type=int, default=16, help='--gumbel: the actions sequential halving starts from (at least 2)')
+  a('--gumbel_c_visit', type=float, default=50.0, help='--gumbel: sigma = (c_visit + max visits) * c_scale * normalised Q')
+  a('--gumbel_c_scale', type=float, default=1.0, help='--gumbel: see --gumbel_c_visit')
+  a('--gumbel_scale', type=float, default=0.0,
+    help='--gumbel: the scale of the Gumbel noise at the root; 0 (the default) draws none and is deterministic, 1 is the '
+         'acting setting of the paper')
   a('--match', action='store_true',
     help='play every pair of --nets against each other on the device games (TicTacToe, ConnectFour), every seed from both '
-         'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise / --true_model then take one '
+         'seats; --temperatures / --num_simulations / --only_prior / --only_value / --use_exploration_noise / --true_model / --gumbel then take one '
          'value for both sides or two, one per side')
   a('--opening_plies', type=int, default=0,
     help='--match: uniform random legal plies before the first searched one, the same in both seatings of a seed')

@@ -39,6 +39,7 @@
 #include "mz_unroll.hip.h"
 #include "mz_symmetry.hip.h"
 #include "mz_truemodel.hip.h"
+#include "mz_gumbel.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
@@ -181,6 +182,8 @@ struct mz_engine {
   SolveTableState svt = {};         // its table search's tables and counters (mz_solve_tt), allocated on its first use
   UnrollState ur = {};              // the unroll diagnostic (mz_unroll; mz_unroll.hip.h), allocated on first use
   TmState tm = {};                  // the true-rules search (mz_set_true_model, mz_tm_*; mz_truemodel.hip.h), allocated when set
+  GzState gz = {};                  // the Gumbel search (mz_set_gumbel, mz_gz_*; mz_gumbel.hip.h), allocated when set
+  bool root_noise = false;          // the last mz_root_prepare mixed exploration noise into the root's priors
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -1293,6 +1296,8 @@ int mz_root_prepare(mz_engine *e, const int8_t *to_play, const uint8_t *legal, c
   e->selection_valid = true;
   e->root_ready = true;
   e->tm.root_set = false;
+  e->gz.root_set = false;
+  e->root_noise = nz != nullptr;
   return 0;
 }
 
@@ -1669,6 +1674,7 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
 #include "mz_solve_abi.inc"
 #include "mz_unroll_abi.inc"
 #include "mz_truemodel_abi.inc"
+#include "mz_gumbel_abi.inc"
 #include "mz_eval_abi.inc"
 #include "mz_match_abi.inc"
 #include "mz_reanalyse_abi.inc"

@@ -50,21 +50,7 @@ __global__ __launch_bounds__(64) void k_eval_walk(TreeView t, int nexp, int own_
   const double T = temperature[b];
   const int e_root = t.E[o];
   const int n_root = lane < A ? t.N[o + 1 + lane] : 0;
-  if (path_lengths) {
-    for (int k = lane; k < nexp * A; k += 64) {
-      const int s = t.E[o + 1 + k];
-      if (s >= 1 && s < nexp) par[s] = k / A;
-    }
-    __syncthreads();
-    for (int s = 1 + lane; s <= t.sims; s += 64) {
-      int len = 0;
-      if (s < nexp) {
-        len = 1;
-        for (int p = s; p != 0 && len <= nexp; p = par[p]) ++len;      // (bounded: a cycle is impossible in a tree)
-      }
-      path_lengths[(size_t)b * t.sims + s - 1] = len;
-    }
-  }
+  if (path_lengths) mz_walk_path_lengths(t, o, b, lane, nexp, par, path_lengths);
   const uint32_t amask = A >= 32 ? 0xFFFFFFFFu : ((1u << A) - 1u);
   int node = 0, taken = 0;
   for (; taken < M; ++taken) {

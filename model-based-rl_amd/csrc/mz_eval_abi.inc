@@ -6,7 +6,9 @@
 // (have_noise: io.noise holds them), the device's, or none, then the search with its walk of M actions and finalize (mode
 // 0) or the lookahead (mode 1 only_prior, 2 only_value).  temp [B]; have_walk: io.walk_u holds the walk's uniforms.
 // An engine whose true-rules search is set (mz_set_true_model) searches the games' real positions instead: mz_tm_root +
-// mz_tm_search in place of mz_search, everything around it as it is.
+// mz_tm_search in place of mz_search, everything around it as it is.  An engine whose Gumbel search is set (mz_set_gumbel)
+// runs mz_gz_root + mz_gz_search + the pick in place of mz_search + mz_eval_walk: the pick writes what the walk writes for
+// one action per move; mz_finalize still gives the visit fractions and the root value.
 static int ply_search(mz_engine *e, const PlyIO &io, int mode, int M, const double *temp, bool noise_on, bool have_noise,
                       bool have_walk, uint64_t move, hipStream_t s) {
   const int tmk = e->tm.kind;
@@ -14,10 +16,19 @@ static int ply_search(mz_engine *e, const PlyIO &io, int mode, int M, const doub
   if (tmk && tmk != io.kind) return fail("true_model: the engine's true-rules search is set for kind %d, the games are of kind %d", tmk, io.kind);
   if (tmk && mode != 0) return fail("true_model: only_prior / only_value (mode %d) run no search; unset the true-rules search for them", mode);
   if (tmk && M != 1) return fail("true_model: the true-rules search takes one action per move (max_actions 1), got %d", M);
+  const bool gzo = e->gz.on != 0;
+  if (gzo && mode != 0) return fail("gumbel: only_prior / only_value (mode %d) run no search; unset the Gumbel search for them", mode);
+  if (gzo && M != 1) return fail("gumbel: the Gumbel search takes one action per move (max_actions 1), got %d", M);
+  if (gzo && noise_on) return fail("gumbel: the Gumbel draw replaces the exploration noise at the root (gumbel_scale is the stochastic setting); run without noise");
   if (mz_initial_inference(e, io.obs, s)) return -1;
   const bool given = noise_on && have_noise;
   if (mz_root_prepare(e, io.to_play, io.legal, given ? io.noise : nullptr, noise_on && !given ? 1 : 0, move, s)) return -1;
   if (mode != 0) return mz_eval_lookahead(e, mode, io.actions, io.pred_rewards, io.child_visits, nullptr, nullptr, s);
+  if (gzo) {
+    if (mz_gz_root(e, nullptr, move, s) || mz_gz_search(e, e->sims, s)) return -1;
+    if (gz_pick(e, "gumbel", io.actions, io.pred_rewards, io.n_actions, io.path_lengths, nullptr, nullptr, nullptr, nullptr, s)) return -1;
+    return mz_finalize(e, nullptr, nullptr, move, nullptr, io.child_visits, io.root_value, nullptr, nullptr, s);
+  }
   if (tmk ? (mz_tm_root(e, io.board, io.turn, io.step, s) || mz_tm_search(e, e->sims, s)) : mz_search(e, e->sims, s)) return -1;
   if (mz_eval_walk(e, M, temp, have_walk ? io.walk_u : nullptr, move, io.actions, io.pred_rewards, io.n_actions,
                    io.path_lengths, s)) return -1;

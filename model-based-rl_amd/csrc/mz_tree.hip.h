@@ -11,10 +11,18 @@
 #include "mz_rng.h"
 
 // MinMaxStats.normalize, reference mcts.py:16-21
-__device__ __forceinline__ double mz_normalize(double v, double mn, double mx) {
+__host__ __device__ __forceinline__ double mz_normalize(double v, double mn, double mx) {
   if (mx > mn) return (v - mn) / (mx - mn);
   if (mx == mn) return 1.0;
   return v;
+}
+
+// ucb_score's value term before it is normalised (mcts.py:120-121): reward + discount * value() of a visited child, in the
+// parent's view (value() negated with two players).  Also the q(a) of the Gumbel search (mz_gumbel.hip.h).
+__host__ __device__ __forceinline__ double mz_child_q(double W, int N, float R, int two_players, double discount) {
+  const double q = W / (double)N;
+  const double v = two_players ? -q : q;
+  return (double)R + discount * v;
 }
 
 // whole-record access to the node pool: two 16-byte loads / stores per node
@@ -72,9 +80,7 @@ __device__ __forceinline__ void mz_tree_select(const TreeView &t, int b, int lan
         const double prior_score = pb_c * p;
         double value_score;
         if (Nc > 0) {
-          const double q = c.W / (double)Nc;
-          const double v = t.two_players ? -q : q;
-          value_score = mz_normalize((double)c.R + t.discount * v, mn, mx);
+          value_score = mz_normalize(mz_child_q(c.W, Nc, c.R, t.two_players, t.discount), mn, mx);
         } else {
           value_score = t.init_value_score;
         }
@@ -902,6 +908,29 @@ static __global__ void k_tree_finalize(TreeView t, const double *temperature, co
   const uint64_t move = move_ptr ? (uint64_t)*move_ptr : move_val;
   mz_finalize_tree(t, b, temperature, uniform, seed, move, env_offset, action, child_visits, root_value, error,
                    visit_counts);
+}
+
+// len(search_path) of every simulation of tree b, recovered from the finished tree by the 64 lanes of its workgroup:
+// path_lengths[b][s] = depth of the node expanded into slot s + 1, plus one; 0 from nexp - 1 on (simulations not run).  The
+// children of expansion slot e are nodes 1 + e*A .. e*A + A, so a node k >= 1 whose expansion index is s >= 1 has parent slot
+// (k - 1) / A; the lanes scan the nexp * A children of expanded nodes for that map (par: [sims + 1] in LDS), then every slot
+// climbs to the root.  Shared by k_eval_walk (mz_eval.hip.h) and k_gz_pick (mz_gumbel.hip.h).
+__device__ __forceinline__ void mz_walk_path_lengths(const TreeView &t, size_t o, int b, int lane, int nexp, int32_t *par,
+                                                     int32_t *path_lengths) {
+  const int A = t.A;
+  for (int k = lane; k < nexp * A; k += 64) {
+    const int s = t.E[o + 1 + k];
+    if (s >= 1 && s < nexp) par[s] = k / A;
+  }
+  __syncthreads();
+  for (int s = 1 + lane; s <= t.sims; s += 64) {
+    int len = 0;
+    if (s < nexp) {
+      len = 1;
+      for (int p = s; p != 0 && len <= nexp; p = par[p]) ++len;      // (bounded: a cycle is impossible in a tree)
+    }
+    path_lengths[(size_t)b * t.sims + s - 1] = len;
+  }
 }
 
 // hidden_out[b] = pool[b][slot[b]]  (what the reference hands to recurrent_inference, mcts.py:94-96)

@@ -102,9 +102,7 @@ __device__ __forceinline__ void mz_tm_select(const TreeView &t, const TmState &t
         const double prior_score = pb_c * p;
         double value_score;
         if (Nc > 0) {
-          const double q = c.W / (double)Nc;
-          const double v = t.two_players ? -q : q;
-          value_score = mz_normalize((double)c.R + t.discount * v, mn, mx);
+          value_score = mz_normalize(mz_child_q(c.W, Nc, c.R, t.two_players, t.discount), mn, mx);
         } else {
           value_score = t.init_value_score;
         }

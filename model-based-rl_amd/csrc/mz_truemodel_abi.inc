@@ -9,6 +9,7 @@ int mz_set_true_model(mz_engine *e, int kind) {
   if (kind != 0 && kind != 1 && kind != 3)
     return fail("mz_set_true_model: kind must be 0 (off), 1 (TicTacToe) or 3 (Connect Four), got %d", kind);
   if (kind != 0 && game_shape(e, "mz_set_true_model", kind)) return -1;
+  if (kind != 0 && e->gz.on) return fail("mz_set_true_model: the Gumbel search is set on this engine; an engine takes one of the two (mz_set_gumbel off first)");
   TmState &tm = e->tm;
   if (kind != 0 && !tm.slots) {
     const size_t nb = (size_t)e->Bp;

@@ -189,6 +189,67 @@ def tm_exists(mask, nexp, A, NN):
   return EX
 
 
+_GZ_EVAL = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float),
+                       C.POINTER(C.c_float), C.POINTER(C.c_float))
+
+
+def gz_seq(m, n):
+  """mz_gz_seq_host: seq(m, n), the visit count a root action must have to be considered at each of n simulations when
+  sequential halving starts from m actions (mctx's get_sequence_of_considered_visits); needs no GPU"""
+  out = np.zeros(int(n), np.int32)
+  _abi.check(_abi.load().mz_gz_seq_host(int(m), int(n), out.ctypes.data_as(C.c_void_p)), 'mz_gz_seq_host')
+  return out
+
+
+def gz_search_host(cfg, root_value, root_logits, eval_fn, to_play=None, legal=None, gumbel=None, max_considered=16,
+                   c_visit=50.0, c_scale=1.0, gumbel_scale=0.0, num_simulations=None):
+  """mz_gz_search_host (include/mz_engine_debug.h): the Gumbel search of n roots as sequential C++ on the host, no GPU.  cfg:
+  an mz_config (its num_simulations sizes the trees); root_value [n], root_logits [n, A] float32; to_play [n] (None: 1), legal
+  [n, A] (None: all), gumbel [n, A] float64 = G (needed unless gumbel_scale is 0); eval_fn(sim, parent_slot [n], action [n]) ->
+  (value [n], reward [n], logits [n, A]) is called once per simulation.  Returns a dict of numpy arrays: the trees as
+  export_tree's (N, W, P, R, E, TP [n, NN], legal [n], minmax [n, 2]), vhat [n, sims + 1], sel_slot / sel_action / plens
+  [n, sims], paths [n, sims, sims + 2], action [n], pred_reward [n], pi [n, A], v_mix [n] and min_gap (a float)."""
+  lib = _abi.load()
+  A, S = cfg.action_space, cfg.num_simulations
+  rv = np.ascontiguousarray(root_value, np.float32)
+  lg = np.ascontiguousarray(root_logits, np.float32)
+  n = rv.shape[0]
+  tp = None if to_play is None else np.ascontiguousarray(to_play, np.int8)
+  lm = None if legal is None else np.ascontiguousarray(legal, np.uint8)
+  gm = None if gumbel is None else np.ascontiguousarray(gumbel, np.float64)
+  if rv.shape != (n,) or lg.shape != (n, A) or (tp is not None and tp.shape != (n,)) or (lm is not None and lm.shape != (n, A)) or \
+      (gm is not None and gm.shape != (n, A)):
+    raise ValueError('gz_search_host: root_value [n], root_logits [n, A], to_play [n], legal [n, A], gumbel [n, A]')
+  sims = S if num_simulations is None else int(num_simulations)
+  NN = 1 + (S + 1) * A
+  d = dict(N=np.zeros((n, NN), np.int32), W=np.zeros((n, NN)), P=np.zeros((n, NN)), R=np.zeros((n, NN), np.float32),
+           E=np.zeros((n, NN), np.int32), TP=np.zeros((n, NN), np.int8), legal=np.zeros(n, np.uint32), minmax=np.zeros((n, 2)),
+           vhat=np.zeros((n, S + 1), np.float32), sel_slot=np.zeros((n, S), np.int32), sel_action=np.zeros((n, S), np.int32),
+           paths=np.full((n, S, S + 2), -1, np.int32), plens=np.zeros((n, S), np.int32), action=np.zeros(n, np.int32),
+           pred_reward=np.zeros(n, np.float32), pi=np.zeros((n, A)), v_mix=np.zeros(n), min_gap=np.zeros(1))
+  failure = []
+
+  def cb(_ctx, sim, slot, act, rows, value, reward, logits):
+    try:
+      v, r, l = eval_fn(int(sim), np.ctypeslib.as_array(slot, (rows,)).copy(), np.ctypeslib.as_array(act, (rows,)).copy())
+      np.ctypeslib.as_array(value, (rows,))[:] = np.asarray(v, np.float32).reshape(rows)
+      np.ctypeslib.as_array(reward, (rows,))[:] = np.asarray(r, np.float32).reshape(rows)
+      np.ctypeslib.as_array(logits, (rows, A))[:] = np.asarray(l, np.float32).reshape(rows, A)
+    except Exception as ex:      # (an exception cannot cross the C frames)
+      failure.append(ex)
+  p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+  cb_c = _GZ_EVAL(cb)      # (kept alive across the call)
+  _abi.check(lib.mz_gz_search_host(C.byref(cfg), n, p(tp), p(lm), p(rv), p(lg), p(gm), int(max_considered), float(c_visit),
+                                   float(c_scale), float(gumbel_scale), sims, C.cast(cb_c, C.c_void_p), None,
+                                   *[p(d[key]) for key in ('N', 'W', 'P', 'R', 'E', 'TP', 'legal', 'minmax', 'vhat', 'sel_slot',
+                                                           'sel_action', 'paths', 'plens', 'action', 'pred_reward', 'pi', 'v_mix',
+                                                           'min_gap')]), 'mz_gz_search_host')
+  if failure:
+    raise failure[0]
+  d['min_gap'] = float(d['min_gap'][0])
+  return d
+
+
 class Engine(object):
 
   def __init__(self, num_envs, obs_dim, action_space, num_simulations, two_players=False,
@@ -471,6 +532,64 @@ class Engine(object):
     _abi.check(self.lib.mz_tm_export(self._h, *[d[k].ctypes.data_as(C.c_void_p) for k in ('boards', 'mover', 'step', 'mask', 'finished', 'nexp')]),
                'mz_tm_export')
     d['EX'] = tm_exists(d['mask'], d['nexp'], self.A, self.NN)
+    return d
+
+  # ---- the Gumbel search (mz_set_gumbel, mz_gz_*, include/mz_engine.h; DESIGN s7h)
+  def set_gumbel(self, on=True, max_considered=16, c_visit=50.0, c_scale=1.0, gumbel_scale=0.0):
+    """mz_set_gumbel: while on, eval_env_moves and Match.plies search with the Gumbel search on this engine.
+    gumbel_scale 0 (the evaluation default) draws nothing; 1 is the acting setting of the paper."""
+    _abi.check(self.lib.mz_set_gumbel(self._h, int(bool(on)), int(max_considered), float(c_visit), float(c_scale),
+                                      float(gumbel_scale)), 'mz_set_gumbel')
+    self.gumbel = bool(on)
+
+  def gz_root(self, gumbel=None, move=0):
+    """mz_gz_root (after root_prepare without noise): gumbel [B, A] float64 = G, or None: drawn on the device, `move` in the key"""
+    g = None if gumbel is None else self._dev(gumbel, torch.float64).reshape(self.B, self.A)
+    _abi.check(self.lib.mz_gz_root(self._h, _ptr(g), int(move), self.stream), 'mz_gz_root')
+
+  def _gz_leaf_out(self):
+    return [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(2)]
+
+  def gz_select(self):
+    """mz_gz_select -> (parent_slot [B], action [B]) int32; gather_hidden() gives the parents' hidden states"""
+    out = self._gz_leaf_out()
+    _abi.check(self.lib.mz_gz_select(self._h, _ptr(out[0]), _ptr(out[1]), self.stream), 'mz_gz_select')
+    return out
+
+  def gz_expand_backup(self, value, reward, logits, hidden=None):
+    value = self._dev(value, torch.float32); reward = self._dev(reward, torch.float32)
+    logits = self._dev(logits, torch.float32); hidden = self._dev(hidden, torch.float32)
+    _abi.check(self.lib.mz_gz_expand_backup(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), self.stream),
+               'mz_gz_expand_backup')
+
+  def gz_expand_backup_select(self, value, reward, logits, hidden=None, last=False):
+    """gz_expand_backup of this simulation and gz_select of the next in one launch; returns what gz_select returns, or None
+    after the move's last simulation (`last`: the caller's count of simulations)"""
+    value = self._dev(value, torch.float32); reward = self._dev(reward, torch.float32)
+    logits = self._dev(logits, torch.float32); hidden = self._dev(hidden, torch.float32)
+    out = None if last else self._gz_leaf_out()
+    ptrs = [None, None] if last else [_ptr(o) for o in out]
+    _abi.check(self.lib.mz_gz_expand_backup_select(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), *ptrs,
+                                                   self.stream), 'mz_gz_expand_backup_select')
+    return out
+
+  def gz_search(self, num_simulations=None):
+    n = self.sims if num_simulations is None else int(num_simulations)
+    _abi.check(self.lib.mz_gz_search(self._h, n, self.stream), 'mz_gz_search')
+
+  def gz_pick(self):
+    """mz_gz_pick -> (action [B] int32, pred_reward [B] float32, improved_policy [B, A] float64, v_mix [B] float64)"""
+    a = torch.empty(self.B, dtype=torch.int32, device=self.device)
+    r = torch.empty(self.B, dtype=torch.float32, device=self.device)
+    pi = torch.empty(self.B, self.A, dtype=torch.float64, device=self.device)
+    vm = torch.empty(self.B, dtype=torch.float64, device=self.device)
+    _abi.check(self.lib.mz_gz_pick(self._h, _ptr(a), _ptr(r), _ptr(pi), _ptr(vm), self.stream), 'mz_gz_pick')
+    return a, r, pi, vm
+
+  def gz_export(self):
+    """mz_gz_export -> dict of numpy arrays: G [B, A] float64 (this move's draws), vhat [B, sims + 1] float32"""
+    d = dict(G=np.zeros((self.B, self.A)), vhat=np.zeros((self.B, self.sims + 1), np.float32))
+    _abi.check(self.lib.mz_gz_export(self._h, d['G'].ctypes.data_as(C.c_void_p), d['vhat'].ctypes.data_as(C.c_void_p)), 'mz_gz_export')
     return d
 
   def finalize(self, temperature, uniform=None, move=0):

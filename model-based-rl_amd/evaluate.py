@@ -165,6 +165,63 @@ def refuse_true_model(args_or_config, match=False):
     raise NotImplementedError('--true_model: the architecture %s has no engine path; FCNetwork checkpoints only.' % c.architecture)
 
 
+GUMBEL_DEFAULTS = dict(gumbel_considered=16, gumbel_c_visit=50.0, gumbel_c_scale=1.0, gumbel_scale=0.0)
+
+
+def gumbel_params(args_or_config):
+  """(max_considered, c_visit, c_scale, gumbel_scale) of a command line or a config, the defaults where it has none"""
+  g = lambda k: getattr(args_or_config, k, None)
+  return tuple(type(v)(v if g(k) is None else g(k)) for k, v in GUMBEL_DEFAULTS.items())
+
+
+def refuse_gumbel(args_or_config, match=False):
+  """one sentence per configuration --gumbel (the Gumbel MuZero search, Engine.gz_search) leaves out (NotImplementedError,
+  starting '--gumbel: '); nothing to refuse while every value is 0.  The lists of the command line are read per side with
+  --match (one value: both sides) and as alternatives without it."""
+  c = args_or_config
+  alls = lambda x: list(x) if isinstance(x, (list, tuple)) else [x]
+  gz = [int(x or 0) for x in alls(getattr(c, 'gumbel', 0))]
+  if not any(gz):
+    return
+  if any(x not in (0, 1) for x in gz):
+    raise NotImplementedError('--gumbel: the values are 0 (PUCT) and 1 (the Gumbel search), got %r.' % (gz,))
+  if not match and not getattr(c, 'device_env', False):
+    raise NotImplementedError('--gumbel: the Gumbel search is served by the device games\' move loop and needs --device_env (or --match).')
+  if any(int(x) != 1 for x in alls(getattr(c, 'apply_mcts_actions', 1))):
+    raise NotImplementedError('--gumbel: a move of the Gumbel search applies one action and takes --apply_mcts_actions 1 only.')
+  pick = lambda v, k: v[k if len(v) == 2 else 0]
+  on_side = lambda v: any(pick(gz, k) and pick(v, k) for k in range(2)) if match else any(v)
+  if on_side([int(x or 0) for x in alls(getattr(c, 'use_exploration_noise', 0))]):
+    raise NotImplementedError('--gumbel: the Gumbel draw replaces the exploration noise at the root; a side takes --use_exploration_noise or the Gumbel search (--gumbel_scale is its stochastic setting).')
+  temps = getattr(c, 'temperatures', None)
+  temps = [float(x or 0) for x in alls(getattr(c, 'temperature', 0) if temps is None else temps)]
+  if on_side([t != 0 for t in temps]):
+    raise NotImplementedError('--gumbel: the move is chosen by the rule of the search, not sampled from the visits; a side takes temperature 0 (--gumbel_scale is the stochastic setting).')
+  prior, value = [int(x or 0) for x in alls(getattr(c, 'only_prior', 0))], [int(x or 0) for x in alls(getattr(c, 'only_value', 0))]
+  if on_side(prior) or on_side(value):
+    raise NotImplementedError('--gumbel: --only_prior / --only_value run no search; a side takes one of them or the Gumbel search.')
+  if on_side([int(x or 0) for x in alls(getattr(c, 'true_model', 0))]):
+    raise NotImplementedError('--gumbel: an engine searches the true rules or with the Gumbel search; a side takes --true_model or --gumbel.')
+  if getattr(c, 'architecture', 'FCNetwork') != 'FCNetwork':
+    raise NotImplementedError('--gumbel: the architecture %s has no engine path; FCNetwork checkpoints only.' % c.architecture)
+  m, cv, cs, sc = gumbel_params(c)
+  if m < 2:
+    raise NotImplementedError('--gumbel: --gumbel_considered must be at least 2, got %d.' % m)
+  if not cv >= 0:
+    raise NotImplementedError('--gumbel: --gumbel_c_visit must not be negative, got %g.' % cv)
+  if not cs > 0:
+    raise NotImplementedError('--gumbel: --gumbel_c_scale must be positive, got %g.' % cs)
+  if not sc >= 0:
+    raise NotImplementedError('--gumbel: --gumbel_scale must not be negative, got %g.' % sc)
+
+
+def gumbel_line(config):
+  """the printed line that names a configuration's search"""
+  if not getattr(config, 'gumbel', 0):
+    return 'Search: PUCT'
+  return 'Search: Gumbel, m = %d, c_visit = %g, c_scale = %g, gumbel_scale = %g' % gumbel_params(config)
+
+
 class DeviceGame(object):
   """A finished game of the device-environment path: what the summary and the CLI read, from the device's accumulators.
   With keep_history also the per-move lists under the host path's names (history.actions / rewards / to_play / dones /
@@ -230,6 +287,7 @@ class Evaluator(SummaryTools):
     refuse_grade(_with(self.config, device_env=True))
     refuse_grade_unroll(self.config)
     refuse_true_model(_with(self.config, device_env=True))
+    refuse_gumbel(_with(self.config, device_env=True))
     self.grade_report = None      # --grade: the report of the last play_games (solver.grade_games)
     self.grade_unroll_report = None      # --grade_unroll K: the model by unroll depth on the same games (solver.grade_unroll)
     if not torch.cuda.is_available():
@@ -255,17 +313,26 @@ class Evaluator(SummaryTools):
                            draws=None if draws is None else [draws])[0]
 
   def play_games(self, num_games, seeds=None, environments=None, draws=None, device_env=False, keep_history=False,
-                 start_states=None, true_model=False):
+                 start_states=None, true_model=False, gumbel=False):
     """num_games games, up to self.batch of them in lock-step per engine.  seeds: one per game, consecutive (seed + i); None
     draws a base seed.  draws (parity runs): per game a dict of recorded draws -- 'walk' [moves][M] uniforms, 'noise' [moves][A]
     Dirichlet draws at the legal positions, 'opp' the random opponent's choices (indices into the legal actions).
     device_env (or config.device_env): the games live on the device environments and come back as DeviceGame records, with
     keep_history (or config.keep_history) carrying the per-move lists; start_states [num_games][4]: CartPole's start states
     instead of the counter RNG's (device path only).  true_model (or config.true_model): the moves are searched on the true
-    rules (Engine.tm_search; device path, TicTacToe / ConnectFour)."""
+    rules (Engine.tm_search; device path, TicTacToe / ConnectFour).  gumbel (or config.gumbel): the moves are searched with the
+    Gumbel search (Engine.gz_search; device path; True: the config's gumbel_* parameters, else their defaults; or a dict of
+    Engine.set_gumbel's arguments)."""
     device_env = bool(device_env or getattr(self.config, 'device_env', False))
     true_model = bool(true_model or getattr(self.config, 'true_model', 0))
     refuse_true_model(_with(self.config, device_env=device_env, true_model=int(true_model)))
+    gumbel = gumbel or bool(getattr(self.config, 'gumbel', 0))
+    if gumbel:
+      m, cv, cs, sc = gumbel_params(self.config)
+      given = gumbel if isinstance(gumbel, dict) else {}
+      gumbel = dict(dict(max_considered=m, c_visit=cv, c_scale=cs, gumbel_scale=sc), **given)
+      refuse_gumbel(_with(self.config, device_env=device_env, gumbel=1, true_model=int(true_model), gumbel_considered=gumbel['max_considered'],
+                          gumbel_c_visit=gumbel['c_visit'], gumbel_c_scale=gumbel['c_scale'], gumbel_scale=gumbel['gumbel_scale']))
     grade = bool(getattr(self.config, 'grade', False))
     keep_history = bool(keep_history or grade or getattr(self.config, 'keep_history', False))
     refuse_opp_playouts(_with(self.config, device_env=device_env))
@@ -287,7 +354,7 @@ class Evaluator(SummaryTools):
       hi = min(num_games, lo + self.batch)
       if device_env:
         games += self._play_batch_device(seeds[lo:hi], None if draws is None else draws[lo:hi],
-                                         None if start_states is None else start_states[lo:hi], keep_history, true_model)
+                                         None if start_states is None else start_states[lo:hi], keep_history, true_model, gumbel)
         continue
       envs = environments[lo:hi] if environments is not None else [get_environment(self.config) for _ in range(lo, hi)]
       games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
@@ -339,11 +406,12 @@ class Evaluator(SummaryTools):
     report['seconds'] = time.perf_counter() - t0
     return report
 
-  def _play_batch_device(self, seeds, draws, start_states, keep_history, true_model=False):
+  def _play_batch_device(self, seeds, draws, start_states, keep_history, true_model=False, gumbel=None):
     """_play_batch with the games on the device environments: whole moves are enqueued MOVES_PER_SYNC at a time
     (Engine.eval_env_moves: observe, initial inference, root, search + walk or lookahead, finalize, apply), and the host
     only reads the number of games still live after each chunk.  true_model: the engine searches the games' real positions
-    (Engine.set_true_model); everything around the search is the same."""
+    (Engine.set_true_model); gumbel: Engine.set_gumbel's arguments, the engine searches with the Gumbel search; everything
+    around the search is the same."""
     cfg = self.config
     refuse_device_env(_with(cfg, device_env=True))
     refuse_opp_playouts(_with(cfg, device_env=True))
@@ -363,6 +431,8 @@ class Evaluator(SummaryTools):
     eng.set_weights(self.weights)
     if true_model:
       eng.set_true_model(cfg.environment)
+    if gumbel:
+      eng.set_gumbel(True, **gumbel)
     eng.eval_env_reset(cfg.environment, int(cfg.max_steps), CARTPOLE_TIME_LIMITS.get(cfg.environment, 0),
                        getattr(cfg, 'random_opp', None) if two else None, keep_history)
     if opp_playouts:
@@ -580,6 +650,8 @@ def get_label(state, detailed=False, path_idx=None):
         label_parts.append('with noise')
       if getattr(state['config'], 'true_model', 0):
         label_parts.append('true rules')
+      if getattr(state['config'], 'gumbel', 0):
+        label_parts.append('gumbel')
   return ', '.join(label_parts)
 
 
@@ -594,7 +666,8 @@ def state_generator(args):
           for only_prior in args.only_prior:
             for only_value in args.only_value:
               for use_exploration_noise in args.use_exploration_noise:
-                for apply_mcts_actions, true_model in ((m, t) for m in args.apply_mcts_actions for t in getattr(args, 'true_model', [0])):
+                for apply_mcts_actions, true_model, gumbel in ((m, t, g) for m in args.apply_mcts_actions for t in getattr(args, 'true_model', [0])
+                                                               for g in getattr(args, 'gumbel', [0])):
                   if not (only_prior and only_value):
                     state = copy.deepcopy(meta_state)
                     c = state['config']
@@ -607,6 +680,8 @@ def state_generator(args):
                     c.use_exploration_noise = use_exploration_noise
                     c.apply_mcts_actions = apply_mcts_actions
                     c.true_model = int(true_model)
+                    c.gumbel = int(gumbel)
+                    c.gumbel_considered, c.gumbel_c_visit, c.gumbel_c_scale, c.gumbel_scale = gumbel_params(args)
                     c.render = args.render
                     c.save_mcts = args.save_mcts
                     c.save_mcts_after_step = args.save_mcts_after_step
@@ -639,6 +714,7 @@ def main(argv=None):
   refuse_grade(args, match=args.match)
   refuse_grade_unroll(args)
   refuse_true_model(args, match=args.match)
+  refuse_gumbel(args, match=args.match)
   if args.match:      # checkpoint against checkpoint (match.py); implies the device path
     from . import match
     return match.main(args)
@@ -660,6 +736,11 @@ def main(argv=None):
     s['true_model'] = int(getattr(evaluator.config, 'true_model', 0))
     if args.device_env:
       print("Search below the root: {}\n".format('the true rules of the game (--true_model)' if s['true_model'] else 'the learned model'))
+    s['gumbel'] = int(getattr(evaluator.config, 'gumbel', 0))
+    if s['gumbel']:
+      s['gumbel_params'] = dict(zip(('max_considered', 'c_visit', 'c_scale', 'gumbel_scale'), gumbel_params(evaluator.config)))
+    if args.device_env:
+      print(gumbel_line(evaluator.config) + "\n")
     if evaluator.config.two_players and args.random_opp is not None:
       returns = np.array([game_return(g) for g in games])
       s['wins'], s['draws'], s['losses'] = int((returns > 0).sum()), int((returns == 0).sum()), int((returns < 0).sum())

@@ -12,7 +12,8 @@ game's seed alone (MZ_RNG_OPEN): both seatings of a seed start from the same pos
 
 Per-side settings come from each state's config: num_simulations, temperature, only_prior, only_value,
 use_exploration_noise, true_model (that side searches the true rules of the game, Engine.tm_search: the same checkpoint on
-both sides with true_model (0, 1) prices its learned model in Elo).  One action is applied per ply, on FCNetwork checkpoints."""
+both sides with true_model (0, 1) prices its learned model in Elo), gumbel (that side searches with the Gumbel search,
+Engine.gz_search, with its config's gumbel_* parameters).  One action is applied per ply, on FCNetwork checkpoints."""
 import copy
 import json
 import math
@@ -174,15 +175,18 @@ def _records(r, seeds, seating, opening, sides, sims, keep_history):
 
 
 def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=None, keep_history=False, batch=None,
-               device=None, stats=None, true_model=None):
+               device=None, stats=None, true_model=None, gumbel=None):
   """num_games seeds, each played in both seatings (2 * num_games games), up to `batch` games of one seating in lock-step.
   seeds: consecutive, one per game; None draws a base seed.  draws (parity runs): per seed a dict of given draws -- 'walk'
   [plies] uniforms and 'noise' [plies][A] Dirichlet draws, both indexed by the ply with the opening plies counted, and
   'opening' [k] indices into the legal actions of the opening positions -- used in both seatings.  Returns (games, summary):
   MatchGame records in the order (batch, seating, seed) and summarize(games).  stats: a dict that receives plies (game plies
   played), device_seconds and syncs.  true_model: (a, b), whether that side searches the true rules of the game instead
-  of its learned model (Engine.tm_search; evaluate --true_model); None: each state's config.true_model."""
-  from .evaluate import refuse_true_model
+  of its learned model (Engine.tm_search; evaluate --true_model); None: each state's config.true_model.  gumbel: (a, b), whether that side
+  searches with the Gumbel search instead of PUCT (Engine.gz_search; evaluate --gumbel) -- a true value takes the parameters
+  of that side's config (gumbel_considered, gumbel_c_visit, gumbel_c_scale, gumbel_scale; their defaults where it has none), a
+  dict gives Engine.set_gumbel's arguments; None: each state's config.gumbel."""
+  from .evaluate import gumbel_params, refuse_gumbel, refuse_true_model
   ca, cb = state_a['config'], state_b['config']
   refuse_match(ca, cb)
   if true_model is None:
@@ -192,6 +196,22 @@ def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=N
     raise ValueError('play_match: true_model takes one value per side, got %r' % (true_model,))
   for c, t in zip((ca, cb), true_model):
     refuse_true_model(_with_true_model(c, t), match=True)
+  if gumbel is None:
+    gumbel = (getattr(ca, 'gumbel', 0), getattr(cb, 'gumbel', 0))
+  if len(gumbel) != 2:
+    raise ValueError('play_match: gumbel takes one value per side, got %r' % (gumbel,))
+  gz = []
+  for c, t, g in zip((ca, cb), true_model, gumbel):
+    if not g:
+      gz.append(None)
+      continue
+    m, cv, cs, sc = gumbel_params(c)
+    kw = dict(dict(max_considered=m, c_visit=cv, c_scale=cs, gumbel_scale=sc), **(g if isinstance(g, dict) else {}))
+    c1 = _with_true_model(c, t)
+    c1.gumbel, c1.gumbel_considered, c1.gumbel_c_visit, c1.gumbel_c_scale, c1.gumbel_scale = (
+        1, kw['max_considered'], kw['c_visit'], kw['c_scale'], kw['gumbel_scale'])
+    refuse_gumbel(c1, match=True)
+    gz.append(kw)
   if not torch.cuda.is_available():
     raise RuntimeError('a match needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
   device = torch.device(device if device is not None else 'cuda')
@@ -216,10 +236,12 @@ def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=N
     B = len(sd)
     # the device RNG's key: (engine seed 0, env id = the game's seed, ply, step)
     engines = [Engine.from_config(c, B, device=device, seed=0, env_id_offset=sd[0]) for c in (ca, cb)]
-    for e, w, t in zip(engines, weights, true_model):
+    for e, w, t, g in zip(engines, weights, true_model, gz):
       e.set_weights(w)
       if t:
         e.set_true_model(ca.environment)
+      if g:
+        e.set_gumbel(True, **g)
     match = Match(engines[0], engines[1], ca.environment, max_steps, keep_history)
     packed = None if draws is None else _pack_draws(draws[lo:lo + batch], B, A)
     for seating in (0, 1):
@@ -243,7 +265,7 @@ def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=N
       e.close()
   if stats is not None:
     stats.update(plies=plies, device_seconds=t_dev, syncs=syncs)
-  return games, dict(summarize(games), true_model=list(true_model))
+  return games, dict(summarize(games), true_model=list(true_model), gumbel=[int(bool(g)) for g in gz])
 
 
 def _with_true_model(cfg, t):
@@ -280,6 +302,7 @@ def match_states(args):
 
 def side_state(state, args, side):
   """a checkpoint's state with side `side`'s settings of the command line in its config"""
+  from .evaluate import gumbel_params
   state = dict(state, config=copy.copy(state['config']))
   c = state['config']
   ns = _pick(args.num_simulations, side)
@@ -289,6 +312,8 @@ def side_state(state, args, side):
   c.only_prior, c.only_value = int(_pick(args.only_prior, side)), int(_pick(args.only_value, side))
   c.use_exploration_noise = int(_pick(args.use_exploration_noise, side))
   c.true_model = int(_pick(getattr(args, 'true_model', [0]), side))
+  c.gumbel = int(_pick(getattr(args, 'gumbel', [0]), side))
+  c.gumbel_considered, c.gumbel_c_visit, c.gumbel_c_scale, c.gumbel_scale = gumbel_params(args)
   c.apply_mcts_actions = 1
   c.random_opp = c.human_opp = None
   c.batch = args.batch
@@ -297,14 +322,15 @@ def side_state(state, args, side):
 
 def _side_label(label, cfg):
   mode = 'only prior' if cfg.only_prior else 'only value' if cfg.only_value else 'sims:%d' % cfg.num_simulations
-  return '%s, %s%s%s%s' % (label, mode, ', temp:%g' % cfg.temperature if cfg.temperature else '',
-                           ', with noise' if cfg.use_exploration_noise else '',
-                           ', true rules' if getattr(cfg, 'true_model', 0) else '')
+  return '%s, %s%s%s%s%s' % (label, mode, ', temp:%g' % cfg.temperature if cfg.temperature else '',
+                             ', with noise' if cfg.use_exploration_noise else '',
+                             ', true rules' if getattr(cfg, 'true_model', 0) else '',
+                             ', gumbel' if getattr(cfg, 'gumbel', 0) else '')
 
 
 def main(args):
   """evaluate --match: every pair of --nets (round robin when more than two), the score table printed and written"""
-  from .evaluate import refuse_unsupported
+  from .evaluate import gumbel_line, gumbel_params, refuse_unsupported
   refuse_match(args)
   refuse_unsupported(args)
   states = match_states(args)
@@ -320,6 +346,7 @@ def main(args):
       sa, sb = side_state(states[i][1], args, 0), side_state(states[j][1], args, 1)
       la, lb = _side_label(labels[i], sa['config']), _side_label(labels[j], sb['config'])
       print("\n\033[92mMatch\033[0m ({}) against ({}): {} seeds, both seatings".format(la, lb, args.num_games))
+      print("  A {}; B {}".format(gumbel_line(sa['config']), gumbel_line(sb['config'])))
       stats = {}
       t0 = time.perf_counter()
       games, s = play_match(sa, sb, args.num_games, seeds, opening_plies=args.opening_plies, batch=args.batch, stats=stats)

@@ -6,7 +6,7 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
 
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
-                                       [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]] [--true_model]
+                                       [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]] [--true_model] [--gumbel]
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --symmetry adds train's flag (every sample trained on one of the equivalent images of its position, symmetry.py) to the training run.
@@ -56,14 +56,15 @@ def play_vs_random(weights, agent_side, games=512, sims=30, seed=0, no_support=F
 
 
 def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_playouts=0, grade=None, grade_table=False,
-                          grade_unroll=None, true_model=False):
+                          grade_unroll=None, true_model=False, gumbel=False):
   """the same match through the evaluator's device-environment path (any environment with a device form); `weights` a
   state_dict.  Returns (wins, draws, losses) of the agent.  agent_side: +1 moves first, -1 second.  opp_playouts > 0: the
   opponent is the playout search of that budget (evaluate --opp_playouts) instead of the random mover.  grade: a list that
   receives the report of the agent's moves graded against the exact solver (evaluate --grade), or None: no grading;
   grade_table: with the table search (evaluate --grade_table); grade_unroll: K, the report then carries the model by unroll
   depth under 'unroll' (evaluate --grade_unroll K); true_model: the agent searches the true rules of the game instead of its
-  learned model (evaluate --true_model)."""
+  learned model (evaluate --true_model); gumbel: the agent searches with the Gumbel search instead of PUCT (evaluate --gumbel,
+  its default parameters)."""
   import copy
   from model_based_rl_amd.evaluate import Evaluator, game_return
   cfg = copy.copy(config)
@@ -71,7 +72,7 @@ def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_pl
                    random_opp=-agent_side, human_opp=None, render=False, save_mcts=False, save_gif_as='', label='vs random',
                    verbose=False, batch=games, device_env=True, keep_history=False, opp_playouts=int(opp_playouts), grade=grade is not None,
                    grade_table=bool(grade_table) and grade is not None,
-                   grade_unroll=int(grade_unroll) if grade_unroll and grade is not None else None, true_model=int(bool(true_model))).items():
+                   grade_unroll=int(grade_unroll) if grade_unroll and grade is not None else None, true_model=int(bool(true_model)), gumbel=int(bool(gumbel))).items():
     setattr(cfg, k, v)
   ev = Evaluator({'config': cfg, 'weights': weights, 'training_step': 0})
   ev.load_network()
@@ -104,6 +105,9 @@ def main():
   ap.add_argument('--true_model', action='store_true',
                   help='also play (and with --grade, grade) the 512 games per side with the search on the true rules of the game '
                        '(evaluate --true_model): next to the plain games, the difference is what the learned model costs')
+  ap.add_argument('--gumbel', action='store_true',
+                  help='also play (and with --grade, grade) the 512 games per side with the Gumbel search (evaluate --gumbel, default '
+                       'parameters) at the same number of simulations: next to the plain games, what the search rule changes')
   a = ap.parse_args()
   if a.grade_table and not a.grade:
     ap.error('--grade_table: it chooses the search that --grade solves with and grades nothing without --grade.')
@@ -161,6 +165,15 @@ def main():
                                                                      true_model=True)
         if a.grade:
           graded_true.setdefault(name, {})[key] = got[0]
+  if a.gumbel:      # the same weights and simulations under the Gumbel search
+    gumbel_res, graded_gumbel = {}, {}
+    for name, sd in (('untrained', untrained_sd), ('trained', state['weights'])):
+      for side_, key in ((1, 'agent_first'), (-1, 'agent_second')):
+        got = [] if a.grade else None
+        gumbel_res.setdefault(name, {})[key] = play_vs_random_device(make_config(base), sd, side_, grade=got, grade_table=a.grade_table,
+                                                                     gumbel=True)
+        if a.grade:
+          graded_gumbel.setdefault(name, {})[key] = got[0]
   # the last checkpoint against the first kept one, from both seats (match.play_match); where the run kept a single
   # checkpoint, against the untrained network
   from model_based_rl_amd.match import play_match
@@ -193,6 +206,10 @@ def main():
     out['true_model_vs_random_512_games (win, draw, loss)'] = true_rules
     if a.grade:
       out['true_model_graded_vs_random_512_games'] = graded_true
+  if a.gumbel:
+    out['gumbel_vs_random_512_games (win, draw, loss)'] = gumbel_res
+    if a.grade:
+      out['gumbel_graded_vs_random_512_games'] = graded_gumbel
   if a.keep_checkpoint:
     torch.save({'weights': state['weights'], 'training_step': int(state['training_step'])}, a.keep_checkpoint)
   if a.match_against:
