@@ -890,6 +890,44 @@ static int launch_search(mz_engine *e, const SearchOpts &o, bool selection_valid
 
 
 // ---------------------------------------------------------------- ABI
+// ---- the step protocol of the stepwise searches (the plain entry points below, mz_tm_* in mz_truemodel_abi.inc, mz_gz_* in
+// mz_gumbel_abi.inc) over selection_valid (a descent is pending) and sims_done.  A variant brings its readiness condition
+// (`ready`; `first`: the call its message asks for), its kernels (`launch`) and its leaf outputs.
+// the pending descent, launched if there is none
+template <class LAUNCH>
+static int step_pending(mz_engine *e, const char *fn, bool ready, const char *first, LAUNCH launch) {
+  if (!ready) return fail("%s: call %s first", fn, first);
+  if (e->sims_done >= e->sims) return fail("%s: all %d simulations already done", fn, e->sims);
+  if (!e->selection_valid) {
+    launch();
+    HIPCHECK(hipGetLastError());
+    e->selection_valid = true;
+  }
+  return 0;
+}
+// does a descent follow this simulation?  (the move's last simulation: nothing to descend for)
+static bool step_more(const mz_engine *e) { return e->sims_done + 1 < e->sims; }
+// one simulation's expand + backup of the pending descent: launch(more), more = the same launch makes the next descent
+template <class LAUNCH>
+static int step_advance(mz_engine *e, const char *fn, bool ready, const char *select, bool more, LAUNCH launch) {
+  if (!ready || !e->selection_valid) return fail("%s: call %s first", fn, select);
+  if (e->sims_done >= e->sims) return fail("%s: all %d simulations already done", fn, e->sims);
+  launch(more);
+  HIPCHECK(hipGetLastError());
+  e->sims_done += 1;
+  e->selection_valid = more;
+  return 0;
+}
+
+// what the last descent left, for the caller; any may be null (one launch: four D2D blits cost 4 x 4 us per simulation)
+static int export_selection(mz_engine *e, int32_t *leaf_node, int32_t *parent_slot, int32_t *action, int32_t *depth, hipStream_t s) {
+  if (leaf_node || parent_slot || action || depth) {
+    hipLaunchKernelGGL(k_export_selection, dim3((e->B + 255) / 256), dim3(256), 0, s, e->tv, leaf_node, parent_slot, action, depth);
+    HIPCHECK(hipGetLastError());
+  }
+  return 0;
+}
+
 extern "C" {
 
 const char *mz_last_error(void) { return g_err.c_str(); }
@@ -958,13 +996,8 @@ int mz_create(const mz_config *cfg, mz_engine **out) {
   DM(sqrttab, e->sims + 2) DM(pbctab, (size_t)(e->sims + 2) * (e->sims + 2)) DM(logtab, e->sims + 2)
 #undef DM
   {
-    // mcts.py:116-117: math.log((N + base + 1) / base) + init and math.sqrt(N), for every N a parent
-    // can have inside one search -- libm on the host, the values CPython computes.
-    std::vector<double> lt(e->sims + 2), st(e->sims + 2);
-    for (int i = 0; i < e->sims + 2; ++i) {
-      lt[i] = log(((double)i + cfg->pb_c_base + 1) / cfg->pb_c_base) + cfg->pb_c_init;
-      st[i] = sqrt((double)i);
-    }
+    std::vector<double> lt, st;
+    mz_host_tables(*cfg, lt, st);
     // pb_c for every (parent visits, child visits) pair, in the reference's operation order
     // (pb_c = log(..) + init; pb_c *= sqrt(Np) / (Nc + 1)); IEEE double on the host, no contraction
     const int T = e->sims + 2;
@@ -1471,19 +1504,9 @@ int mz_search_phase_spread(const mz_engine *e, double *out3) {
 int mz_select(mz_engine *e, int32_t *leaf_node, int32_t *parent_slot, int32_t *action, int32_t *depth, void *stream) {
   if (!e) return fail("mz_select: null engine");
   MZ_ENTER(e);
-  if (!e->root_ready) return fail("mz_select: call mz_root_prepare first");
-  if (e->sims_done >= e->sims) return fail("mz_select: all %d simulations already done", e->sims);
   hipStream_t s = (hipStream_t)stream;
-  if (!e->selection_valid) {
-    TREE_LAUNCH(k_tree_select, s, e->tv);
-    HIPCHECK(hipGetLastError());
-    e->selection_valid = true;
-  }
-  if (leaf_node || parent_slot || action || depth) {      // one launch (four D2D blits cost 4 x 4 us per simulation)
-    hipLaunchKernelGGL(k_export_selection, dim3((e->B + 255) / 256), dim3(256), 0, s, e->tv, leaf_node, parent_slot, action, depth);
-    HIPCHECK(hipGetLastError());
-  }
-  return 0;
+  if (step_pending(e, "mz_select", e->root_ready, "mz_root_prepare", [&] { TREE_LAUNCH(k_tree_select, s, e->tv); })) return -1;
+  return export_selection(e, leaf_node, parent_slot, action, depth, s);
 }
 
 int mz_tree_pair_timed(mz_engine *e, const float *value, const float *reward, const float *logits, float *ms_out, void *stream) {
@@ -1520,40 +1543,32 @@ int mz_gather_hidden(mz_engine *e, float *hidden_out, void *stream) {
   return 0;
 }
 
+// one simulation's tree step on the caller's outputs: more = also the next descent, with mz_select's outputs
+static int plain_step(mz_engine *e, const char *fn, const float *value, const float *reward, const float *logits, const float *hidden,
+                      bool more, int32_t *leaf_node, int32_t *parent_slot, int32_t *action, int32_t *depth, hipStream_t s) {
+  return step_advance(e, fn, true, "mz_select", more, [&](bool m) {
+    if (hidden) {
+      const int n = e->B * MZ_HS;
+      hipLaunchKernelGGL(k_scatter_hidden, dim3((n + 255) / 256), dim3(256), 0, s, e->tv, hidden, 0);
+    }
+    if (m) TREE_LAUNCH(k_tree_step_ext, s, e->tv, value, reward, logits, leaf_node, parent_slot, action, depth);
+    else TREE_LAUNCH(k_tree_expand_backup, s, e->tv, value, reward, logits);
+  });
+}
+
 int mz_expand_backup(mz_engine *e, const float *value, const float *reward, const float *logits,
                      const float *hidden, void *stream) {
   if (!e || !value || !reward || !logits) return fail("mz_expand_backup: null argument");
   MZ_ENTER(e);
-  if (!e->selection_valid) return fail("mz_expand_backup: call mz_select first");
-  hipStream_t s = (hipStream_t)stream;
-  if (hidden) {
-    const int n = e->B * MZ_HS;
-    hipLaunchKernelGGL(k_scatter_hidden, dim3((n + 255) / 256), dim3(256), 0, s, e->tv, hidden, 0);
-  }
-  TREE_LAUNCH(k_tree_expand_backup, s, e->tv, value, reward, logits);
-  HIPCHECK(hipGetLastError());
-  e->sims_done += 1;
-  e->selection_valid = false;
-  return 0;
+  return plain_step(e, "mz_expand_backup", value, reward, logits, hidden, false, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int mz_expand_backup_select(mz_engine *e, const float *value, const float *reward, const float *logits, const float *hidden,
                             int32_t *leaf_node, int32_t *parent_slot, int32_t *action, int32_t *depth, void *stream) {
   if (!e || !value || !reward || !logits) return fail("mz_expand_backup_select: null argument");
   MZ_ENTER(e);
-  if (!e->selection_valid) return fail("mz_expand_backup_select: call mz_select first");
-  if (e->sims_done + 1 >= e->sims)        // the move's last simulation: nothing to descend for
-    return mz_expand_backup(e, value, reward, logits, hidden, stream);
-  hipStream_t s = (hipStream_t)stream;
-  if (hidden) {
-    const int n = e->B * MZ_HS;
-    hipLaunchKernelGGL(k_scatter_hidden, dim3((n + 255) / 256), dim3(256), 0, s, e->tv, hidden, 0);
-  }
-  TREE_LAUNCH(k_tree_step_ext, s, e->tv, value, reward, logits, leaf_node, parent_slot, action, depth);
-  HIPCHECK(hipGetLastError());
-  e->sims_done += 1;
-  e->selection_valid = true;
-  return 0;
+  return plain_step(e, "mz_expand_backup_select", value, reward, logits, hidden, step_more(e), leaf_node, parent_slot, action, depth,
+                    (hipStream_t)stream);
 }
 
 int mz_recurrent_inference(mz_engine *e, const float *hidden_in, const int32_t *action, int n, float *hidden_out,

@@ -15,6 +15,7 @@
 #include "mz_common.h"
 #include "mz_rng.h"
 #include "mz_tree.hip.h"
+#include "mz_tree_host.h"      // (the host twin's trees, mz_gumbel_host.inc)
 
 #define MZ_RNG_GUMBEL 11u    // the root's Gumbel draws (k_gz_root): counter (env, move, action)
 
@@ -87,18 +88,8 @@ struct GzLanes {
     const int x = v[0] ? 1 : 0;
     return max_i(&x) != 0;
   }
-  // tuple max over (score, action): ties go to the largest action, as everywhere in these trees; -1: no candidate
   __device__ __forceinline__ int argmax(const double *score, const bool *cand) const {
-    double s = cand[0] ? score[0] : 0.0;
-    int best = cand[0] ? lane : -1;
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-      const double os = __shfl_xor(s, off, G);
-      const int ob = __shfl_xor(best, off, G);
-      const bool take = ob >= 0 && (best < 0 || os > s || (os == s && ob > best));
-      if (take) { s = os; best = ob; }
-    }
-    return best;
+    return mz_group_argmax<G>(cand[0] ? score[0] : 0.0, cand[0] ? lane : -1);
   }
 };
 
@@ -195,58 +186,53 @@ __host__ __device__ __forceinline__ int mz_gz_considered(const GzPar &gp, uint32
   return gp.max_considered < nl ? gp.max_considered : nl;
 }
 
-// The descent of simulation `sim`: the root rule, then the rule below the root until a child that is not expanded.  Leaves
-// what mz_tree_select leaves (path, leaf, parent slot, action, depth, to_play at the leaf) and the next inference's row:
-// the parent's hidden state in gz.hid[b], the action in gz.act[b].
+// The rule of the descent (mz_tree_descend, mz_tree.hip.h): mz_gz_node at every level -- the root rule, then the rule below
+// the root -- over the legal actions at the root and every action below it; the chosen child's expansion index is fetched
+// from its lane.  At the leaf it copies the parent's hidden state into gz.hid[b], the next inference's row.
 template <int G>
-__device__ __forceinline__ void mz_gz_select(const TreeView &t, const GzState &gz, int b, int lane, int sim) {
-  const int A = t.A;
-  const size_t o = mz_slab(t, b);
-  int32_t *path = t.path + (size_t)b * t.PL;
-  const double mn = t.mn[b], mx = t.mx[b];
-  const uint32_t legal = t.legal[b];
-  const float *vh = gz.vhat + (size_t)b * (size_t)(t.sims + 1);
-  const int want = gz.seq[(size_t)mz_gz_considered(gz.par, legal, A) * t.sims + sim];
-  const double gl = lane < A ? gz.par.gumbel_scale * gz.G[(size_t)b * A + lane] + (double)t.root_logits[(size_t)b * A + lane] : 0.0;
-  const GzLanes<G> x{lane};
-  int node = 0, parent_e = 0, len = 1, a_sel = 0;
-  const MzNode root = mz_node_load(t, o);
-  int tp = root.TP;
-  if (lane == 0) path[0] = 0;
-  int e = root.E;
-  while (e >= 0) {
+struct GzRule {
+  const TreeView &t;
+  const GzState &gz;
+  int b, lane;
+  double mn, mx;
+  uint32_t legal;
+  int want;             // seq(m, sims)[sim]
+  double gl;            // g(a) + logit(a) of this lane's root action
+  __device__ __forceinline__ void begin(const MzNode &) {}
+  __device__ __forceinline__ bool choose(int e, int node, int &best, int &ce) {
+    const int A = t.A;
     const bool has = lane < A && (node != 0 || ((legal >> lane) & 1u));
-    const double vhat = (double)vh[e];      // (requested beside the children's records)
+    const double vhat = (double)gz.vhat[(size_t)b * (size_t)(t.sims + 1) + e];      // (requested beside the children's records)
     double cP = 0.0, cW = 0.0, pi, vmix;
     int cN = 0, cE = -1;
     float cR = 0.f;
     if (has) {
-      const MzNode c = mz_node_load(t, o + 1 + e * A + lane);
+      const MzNode c = mz_node_load(t, mz_slab(t, b) + 1 + e * A + lane);
       cP = c.P; cW = c.W; cN = c.N; cE = c.E; cR = c.R;
     }
-    int best = mz_gz_node(x, A, gz.par, t.two_players, t.discount, mn, mx, vhat, &has, &cP, &cW, &cN, &cR, node == 0, &gl, want,
-                          &pi, &vmix);
+    best = mz_gz_node(GzLanes<G>{lane}, A, gz.par, t.two_players, t.discount, mn, mx, vhat, &has, &cP, &cW, &cN, &cR, node == 0,
+                      &gl, want, &pi, &vmix);
     if (best < 0) best = 0;      // (a root without a legal action: stay inside the node pool)
-    const int ce = __shfl(cE, best, G);
-    a_sel = best;
-    parent_e = e;
-    node = 1 + e * A + a_sel;
-    if (lane == 0) path[len] = node;
-    ++len;
-    if (t.two_players) tp = -tp;
-    e = ce;
+    ce = __shfl(cE, best, G);
+    return true;
   }
-  const float *hp = t.hpool + ((size_t)b * (size_t)(t.sims + 1) + (size_t)parent_e) * MZ_HS;
-  for (int k = lane; k < MZ_H; k += G) gz.hid[(size_t)b * MZ_H + k] = hp[k];
-  if (lane == 0) {
-    t.plen[b] = len;
-    t.leaf_tp[b] = (int8_t)tp;
-    t.leaf[b] = node;
-    t.slot[b] = parent_e;
-    t.act[b] = a_sel;
-    t.depth[b] = len - 1;
-    gz.act[b] = a_sel;
+  __device__ __forceinline__ void leave(const MzDescent &d) {
+    const float *hp = t.hpool + ((size_t)b * (size_t)(t.sims + 1) + (size_t)d.slot) * MZ_HS;
+    for (int k = lane; k < MZ_H; k += G) gz.hid[(size_t)b * MZ_H + k] = hp[k];
   }
+};
+
+// The descent of simulation `sim`.  Leaves what every descent leaves and the next inference's row: the parent's hidden state
+// in gz.hid[b] (GzRule::leave), the action in gz.act[b].
+template <int G>
+__device__ __forceinline__ void mz_gz_select(const TreeView &t, const GzState &gz, int b, int lane, int sim) {
+  const int A = t.A;
+  const uint32_t legal = t.legal[b];
+  const int want = gz.seq[(size_t)mz_gz_considered(gz.par, legal, A) * t.sims + sim];
+  const double gl = lane < A ? gz.par.gumbel_scale * gz.G[(size_t)b * A + lane] + (double)t.root_logits[(size_t)b * A + lane] : 0.0;
+  GzRule<G> rule = {t, gz, b, lane, t.mn[b], t.mx[b], legal, want, gl};
+  const MzDescent d = mz_tree_descend<G>(t, b, lane, rule);
+  if (lane == 0) gz.act[b] = d.act;
 }
 
 // ------------------------------------------------------------------ kernels

@@ -43,25 +43,17 @@ int mz_gz_root(mz_engine *e, const double *gumbel, uint64_t move, void *stream) 
   return 0;
 }
 
-// the pending descent, launched if there is none
+// ---- the stepwise search: the step protocol of mz_engine.hip with this variant's readiness, kernels and leaf outputs
+static bool gz_ready(const mz_engine *e) { return e->gz.on && e->gz.root_set; }
+
 static int gz_pending(mz_engine *e, const char *fn, hipStream_t s) {
-  if (!e->gz.on || !e->gz.root_set) return fail("%s: call mz_gz_root first", fn);
-  if (e->sims_done >= e->sims) return fail("%s: all %d simulations already done", fn, e->sims);
-  if (!e->selection_valid) {
-    GZ_LAUNCH(k_gz_select, s, e->sims_done);
-    HIPCHECK(hipGetLastError());
-    e->selection_valid = true;
-  }
-  return 0;
+  return step_pending(e, fn, gz_ready(e), "mz_gz_root", [&] { GZ_LAUNCH(k_gz_select, s, e->sims_done); });
 }
 
-static int gz_leaf_out(mz_engine *e, int32_t *parent_slot, int32_t *action, hipStream_t s) {
-  if (parent_slot || action) {
-    hipLaunchKernelGGL(k_export_selection, dim3((e->B + 255) / 256), dim3(256), 0, s, e->tv, (int32_t *)nullptr, parent_slot, action,
-                       (int32_t *)nullptr);
-    HIPCHECK(hipGetLastError());
-  }
-  return 0;
+static int gz_step(mz_engine *e, const char *fn, const float *value, const float *reward, const float *logits, const float *hidden,
+                   bool more, hipStream_t s) {
+  return step_advance(e, fn, gz_ready(e), "mz_gz_select", more,
+                      [&](bool m) { GZ_LAUNCH(k_gz_step, s, value, reward, logits, hidden, m ? 1 : 0, e->sims_done + 1); });
 }
 
 int mz_gz_select(mz_engine *e, int32_t *parent_slot, int32_t *action, void *stream) {
@@ -69,19 +61,7 @@ int mz_gz_select(mz_engine *e, int32_t *parent_slot, int32_t *action, void *stre
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
   if (gz_pending(e, "mz_gz_select", s)) return -1;
-  return gz_leaf_out(e, parent_slot, action, s);
-}
-
-// one simulation's tree step on the given outputs: more = also the next descent
-static int gz_step(mz_engine *e, const char *fn, const float *value, const float *reward, const float *logits, const float *hidden,
-                   bool more, hipStream_t s) {
-  if (!e->gz.on || !e->gz.root_set || !e->selection_valid) return fail("%s: call mz_gz_select first", fn);
-  if (e->sims_done >= e->sims) return fail("%s: all %d simulations already done", fn, e->sims);
-  GZ_LAUNCH(k_gz_step, s, value, reward, logits, hidden, more ? 1 : 0, e->sims_done + 1);
-  HIPCHECK(hipGetLastError());
-  e->sims_done += 1;
-  e->selection_valid = more;
-  return 0;
+  return export_selection(e, nullptr, parent_slot, action, nullptr, s);
 }
 
 int mz_gz_expand_backup(mz_engine *e, const float *value, const float *reward, const float *logits, const float *hidden,
@@ -96,16 +76,16 @@ int mz_gz_expand_backup_select(mz_engine *e, const float *value, const float *re
   if (!e || !value || !reward || !logits) return fail("mz_gz_expand_backup_select: null argument");
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
-  const bool more = e->sims_done + 1 < e->sims;      // (the move's last simulation: nothing to descend for)
+  const bool more = step_more(e);
   if (gz_step(e, "mz_gz_expand_backup_select", value, reward, logits, hidden, more, s)) return -1;
-  return more ? gz_leaf_out(e, parent_slot, action, s) : 0;
+  return more ? export_selection(e, nullptr, parent_slot, action, nullptr, s) : 0;
 }
 
 int mz_gz_search(mz_engine *e, int num_simulations, void *stream) {
   if (!e) return fail("mz_gz_search: null engine");
   MZ_ENTER(e);
   if (!e->weights_set) return fail("mz_gz_search: weights not set (call mz_set_weights)");
-  if (!e->gz.on || !e->gz.root_set) return fail("mz_gz_search: call mz_gz_root first");
+  if (!gz_ready(e)) return fail("mz_gz_search: call mz_gz_root first");
   if (num_simulations < 1 || e->sims_done + num_simulations > e->sims)
     return fail("mz_gz_search: %d + %d simulations exceed the pool sized for num_simulations = %d", e->sims_done,
                 num_simulations, e->sims);
@@ -117,7 +97,7 @@ int mz_gz_search(mz_engine *e, int num_simulations, void *stream) {
     NET_LAUNCH(k_net_recurrent_rows, (e->B + MZ_ROWS - 1) / MZ_ROWS, s, e->nv, (const float *)gz.hid, (const int32_t *)gz.act, e->B,
                gz.hout, e->tv.reward, e->tv.value, e->tv.logits);
     HIPCHECK(hipGetLastError());
-    if (gz_step(e, "mz_gz_search", e->tv.value, e->tv.reward, e->tv.logits, gz.hout, e->sims_done + 1 < e->sims, s)) return -1;
+    if (gz_step(e, "mz_gz_search", e->tv.value, e->tv.reward, e->tv.logits, gz.hout, step_more(e), s)) return -1;
   }
   return 0;
 }

@@ -43,97 +43,176 @@ __device__ __forceinline__ void mz_node_fresh(const TreeView &t, size_t i, doubl
   dst[0] = u.q[0]; dst[1] = u.q[1];
 }
 
-// The descent of MCTS.run (mcts.py:83-94) with MCTS.select_child (104-113) and ucb_score (115-124).
+// The arg-max of a G-lane group: the maximum of the candidate lanes' (score, action) tuples, so ties go to the largest action
+// (mcts.py:106-112).  best: the lane's action, -1 of a lane that is no candidate (its score is not looked at); every lane
+// returns the winner, -1 when no lane is a candidate.  pay: integers that ride along -- every lane ends with the winner's,
+// at no further round of shuffles.
+template <int G, class... PAY>
+__device__ __forceinline__ int mz_group_argmax(double score, int best, PAY &...pay) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) {
+    const double os = __shfl_xor(score, off, G);
+    const int ob = __shfl_xor(best, off, G);
+    const bool take = ob >= 0 && (best < 0 || os > score || (os == score && ob > best));
+    // (every lane shuffles, whatever it takes: a lane that skipped the exchange would hand its partner nothing)
+    auto ride = [&](auto &p) { const auto op = __shfl_xor(p, off, G); p = take ? op : p; };
+    (ride(pay), ...);
+    if (take) { score = os; best = ob; }
+  }
+  return best;
+}
+
+// ucb_score (mcts.py:115-124) of a child (P, W, Nc, R) whose parent has Np visits, as select_child ranks it: a fresh root
+// (Np == 0) ranks by prior (mcts.py:105-108).  lgn = log((Np + base + 1) / base) + init and sqn = sqrt(Np) come from the
+// host-built libm tables (mz_host_tables, mz_tree_host.h); pb_c is then the reference's own two operations on them
+// (mcts.py:116-117: pb_c = log(..) + init; pb_c *= sqrt(Np) / (Nc + 1)), IEEE double like the host-built pb_c table of the
+// fused kernels.
+__host__ __device__ __forceinline__ double mz_puct_score(int Np, double lgn, double sqn, double P, double W, int Nc, float R,
+                                                         int two_players, double discount, double init_value_score,
+                                                         double mn, double mx) {
+  if (Np == 0) return P;
+  const double pb_c = lgn * (sqn / (double)(Nc + 1));
+  const double prior_score = pb_c * P;
+  double value_score;
+  if (Nc > 0) {
+    value_score = mz_normalize(mz_child_q(W, Nc, R, two_players, discount), mn, mx);
+  } else {
+    value_score = init_value_score;
+  }
+  return prior_score + value_score;
+}
+
+// The descent of MCTS.run (mcts.py:83-94), stated once for every search: the loop over levels, the path, the to_play flip
+// and what a descent leaves for expand + backup and for the caller (plen, leaf_tp, leaf, slot, act, depth).  A RULE says, for
+// the node in expansion slot e, which children exist and which one is taken:
+//   rule.begin(root)                  before the first level, with the root's record
+//   rule.choose(e, node, best, ce)    best = the action taken, ce = that child's expansion index (< 0: a leaf); false: the
+//                                     node has no child and the descent stops AT it (nothing will be expanded)
+//   rule.leave(d)                     at the leaf, before the descent is recorded: what the rule's search gathers there with
+//                                     every lane of the group (its loads ahead of lane 0's stores, not behind them)
+// The rules are MzPuctRule over MzLegalChildren (mz_tree_select, below), over the positions' child masks (mz_truemodel.hip.h)
+// and GzRule (mz_gumbel.hip.h).  A rule keeps what it carries from level to level itself, and its loads and shuffles are all
+// a level costs: the skeleton adds none.
+struct MzDescent {
+  int node, slot, act, tp;      // the leaf, its parent's expansion slot, the action into it, to_play at it
+  bool stopped;                 // rule.choose ended the descent
+};
+// what a descent leaves behind (lane 0): len nodes on the path, `node` the last
+__device__ __forceinline__ void mz_descent_store(const TreeView &t, int b, int len, const MzDescent &d) {
+  t.plen[b] = len;
+  t.leaf_tp[b] = (int8_t)d.tp;
+  t.leaf[b] = d.node;
+  t.slot[b] = d.slot;
+  t.act[b] = d.act;
+  t.depth[b] = len - 1;
+}
+template <int G, class RULE>
+__device__ __forceinline__ MzDescent mz_tree_descend(const TreeView &t, int b, int lane, RULE &rule) {
+  const int A = t.A;
+  int32_t *path = t.path + (size_t)b * t.PL;
+  MzDescent d = {0, 0, -1, 0, false};
+  int len = 1;
+  const MzNode root = mz_node_load(t, mz_slab(t, b));
+  d.tp = root.TP;
+  if (lane == 0) path[0] = 0;
+  int e = root.E;
+  rule.begin(root);
+  while (e >= 0) {
+    int best, ce;
+    if (!rule.choose(e, d.node, best, ce)) { d.stopped = true; break; }
+    d.act = best;
+    d.slot = e;
+    d.node = 1 + e * A + best;
+    if (lane == 0) path[len] = d.node;
+    ++len;
+    if (t.two_players) d.tp = -d.tp;
+    e = ce;
+  }
+  rule.leave(d);
+  if (lane == 0) mz_descent_store(t, b, len, d);
+  return d;
+}
+
+// MCTS.select_child (mcts.py:104-113) by ucb_score over the children CHILDREN names: children.exists(e, node, lane, none) =
+// the child `lane` of the node in slot e exists, none = no child of it does (the same in every lane of the group), which
+// ends the descent where CHILDREN::stops.
 // One dependent memory round trip per level: every child lane fetches its child's whole 32-byte record -- the A children of
 // a node are 32 A contiguous bytes -- and the winner's expansion index and visit count (the next level's `e` and parent
-// count) ride along in the arg-max instead of being fetched afterwards.
-template <int G>
-__device__ __forceinline__ void mz_tree_select(const TreeView &t, int b, int lane, int &slot_out, int &act_out) {
-  const int A = t.A;
-  const size_t o = mz_slab(t, b);
-  int32_t *path = t.path + (size_t)b * t.PL;
-  const double mn = t.mn[b], mx = t.mx[b];
-  const uint32_t legal = t.legal[b];
-  int node = 0, parent_e = 0, len = 1, a_sel = -1;
-  const MzNode root = mz_node_load(t, o);
-  int tp = root.TP;
-  if (lane == 0) path[0] = 0;
-  int e = root.E, Np = root.N;
-  while (e >= 0) {
-    const int ch = 1 + e * A + lane;
-    const bool valid = lane < A && (node != 0 || ((legal >> lane) & 1u));
-    double score = 0.0;
-    int best = -1, ce = -1, cn = 0;
-    // log((Np + base + 1) / base) + init and sqrt(Np) of THIS level's parent count (host libm tables): requested beside the
-    // children's records, not behind them -- pb_c is then the reference's own two operations on them (mcts.py:116-117:
-    // pb_c = log(..) + init; pb_c *= sqrt(Np) / (Nc + 1)), IEEE double like the host-built pb_c table of the fused kernels
+// count) ride along in the arg-max instead of being fetched afterwards.  The mask and the two table values of THIS level's
+// parent count are requested beside the children's records, not behind them.
+template <int G, class CHILDREN>
+struct MzPuctRule {
+  const TreeView &t;
+  size_t o;
+  int lane;
+  double mn, mx;
+  CHILDREN children;
+  int Np;
+  __device__ __forceinline__ void begin(const MzNode &root) { Np = root.N; }
+  __device__ __forceinline__ void leave(const MzDescent &) {}
+  __device__ __forceinline__ bool choose(int e, int node, int &best, int &ce) {
+    bool none;      // (asked by every lane of the group, those beyond A too: all of them must agree on `none`)
+    const bool has = children.exists(e, node, lane, none);
+    const bool valid = lane < t.A && has;
     const double lgn = t.logtab[Np], sqn = t.sqrttab[Np];
+    if (CHILDREN::stops && none) return false;
+    double score = 0.0;
+    int cn = 0;
+    best = ce = -1;
     if (valid) {
-      const MzNode c = mz_node_load(t, o + ch);
-      const int Nc = c.N;
-      const double p = c.P;
-      ce = c.E; cn = Nc;
-      if (Np == 0) {
-        score = p;                                     // fresh root: rank by prior (mcts.py:105-108)
-      } else {
-        const double pb_c = lgn * (sqn / (double)(Nc + 1));
-        const double prior_score = pb_c * p;
-        double value_score;
-        if (Nc > 0) {
-          value_score = mz_normalize(mz_child_q(c.W, Nc, c.R, t.two_players, t.discount), mn, mx);
-        } else {
-          value_score = t.init_value_score;
-        }
-        score = prior_score + value_score;
-      }
+      const MzNode c = mz_node_load(t, o + 1 + e * t.A + lane);
+      ce = c.E; cn = c.N;
+      score = mz_puct_score(Np, lgn, sqn, c.P, c.W, c.N, c.R, t.two_players, t.discount, t.init_value_score, mn, mx);
       best = lane;
     }
-    // tuple max over (score, action): ties go to the largest action (mcts.py:106-112)
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-      const double os = __shfl_xor(score, off, G);
-      const int ob = __shfl_xor(best, off, G), oe = __shfl_xor(ce, off, G), on = __shfl_xor(cn, off, G);
-      const bool take = ob >= 0 && (best < 0 || os > score || (os == score && ob > best));
-      if (take) { score = os; best = ob; ce = oe; cn = on; }
-    }
-    a_sel = best;
-    parent_e = e;
-    node = 1 + e * A + a_sel;
-    if (lane == 0) path[len] = node;
-    ++len;
-    if (t.two_players) tp = -tp;
-    e = ce;
+    best = mz_group_argmax<G>(score, best, ce, cn);
     Np = cn;
+    return true;
   }
-  slot_out = parent_e;
-  act_out = a_sel;
-  if (lane == 0) {
-    t.plen[b] = len;
-    t.leaf_tp[b] = (int8_t)tp;
-    t.leaf[b] = node;
-    t.slot[b] = slot_out;
-    t.act[b] = a_sel;
-    t.depth[b] = len - 1;
+};
+
+// the children of a learned-model tree: the legal actions at the root, every action below it (mcts.py:97)
+struct MzLegalChildren {
+  static constexpr bool stops = false;
+  uint32_t legal;
+  __device__ __forceinline__ bool exists(int, int node, int lane, bool &none) const {
+    none = false;
+    return node != 0 || ((legal >> lane) & 1u);
   }
-}
+};
 
 template <int G>
 __device__ __forceinline__ void mz_tree_select(const TreeView &t, int b, int lane) {
-  int s_, a_;
-  mz_tree_select<G>(t, b, lane, s_, a_);
+  MzPuctRule<G, MzLegalChildren> rule = {t, mz_slab(t, b), lane, t.mn[b], t.mx[b], {t.legal[b]}, 0};
+  mz_tree_descend<G>(t, b, lane, rule);
 }
 
 template <int G>
 __device__ __forceinline__ void mz_tree_backup_path(const TreeView &t, size_t o, const int32_t *path, int len, int tp,
                                                     int lane, float reward, double v, double &mn, double &mx);
 
-// Node.expand for the selected leaf (mcts.py:47-55, all actions: mcts.py:97) followed by
-// MCTS.backpropagate (mcts.py:126-143).  value/reward/logits: this tree's network outputs.
+// Which children a leaf's expansion creates, and whether it expands at all.  The learned model (mcts.py:97): every action,
+// always -- known at compile time.  MzExpandMask: the true-rules search, whose leaf is a position (mz_truemodel.hip.h).
+struct MzExpandAll {
+  __device__ __forceinline__ bool grow() const { return true; }
+  __device__ __forceinline__ bool exists(int) const { return true; }
+};
+struct MzExpandMask {
+  uint32_t mask;      // bit a = child a exists
+  bool grows;         // false: only back up (a finished node met again)
+  __device__ __forceinline__ bool grow() const { return grows; }
+  __device__ __forceinline__ bool exists(int a) const { return (mask >> a) & 1u; }
+};
+
+// Node.expand for the selected leaf (mcts.py:47-55) over the children `pol` names, followed by MCTS.backpropagate
+// (mcts.py:126-143).  value/reward/logits: this tree's network outputs.  Priors as at the root (mz_tree_root): a child that
+// does not exist is marked TP = 0, prior 0.  Returns the expansion slot the leaf took (the next free one when pol.grow() is
+// false: nothing is expanded, the leaf keeps what its first visit stored).
 // The path's nodes are fetched G at a time, one record per lane (one round trip per G nodes instead of one per node);
 // lane 0 then runs the reference's sequential recurrence on the shuffled fields and stores the results.
-template <int G>
-__device__ __forceinline__ void mz_tree_expand_backup(const TreeView &t, int b, int lane, float value,
-                                                      float reward, const float *logits) {
+template <int G, class POLICY = MzExpandAll>
+__device__ __forceinline__ int mz_tree_expand_backup(const TreeView &t, int b, int lane, float value, float reward,
+                                                     const float *logits, const POLICY pol = POLICY()) {
   const int A = t.A;
   const size_t o = mz_slab(t, b);
   const int32_t *path = t.path + (size_t)b * t.PL;
@@ -141,21 +220,28 @@ __device__ __forceinline__ void mz_tree_expand_backup(const TreeView &t, int b, 
   const int tp = t.leaf_tp[b];
   const int e = t.nexp[b];
   const int leafnode = path[len - 1];
-  // priors: exp(logit) in double, no max-shift, Python sum() order 0 + p0 + p1 + ...
-  const double p = (lane < A) ? exp((double)logits[lane]) : 0.0;
-  double sum = 0.0;
-  for (int a = 0; a < A; ++a) sum = sum + __shfl(p, a, G);
-  if (lane < A) mz_node_fresh(t, o + 1 + e * A + lane, p / sum, 1);
+  const bool grow = pol.grow();
+  if (grow) {
+    // priors: exp(logit) in double, no max-shift, Python sum() order 0 + p0 + p1 + ... (+ 0.0 for a missing child is exact)
+    const bool ok = lane < A && pol.exists(lane);
+    const double p = ok ? exp((double)logits[lane]) : 0.0;
+    double sum = 0.0;
+    for (int a = 0; a < A; ++a) sum = sum + __shfl(p, a, G);
+    if (lane < A) mz_node_fresh(t, o + 1 + e * A + lane, ok ? p / sum : 0.0, ok ? 1 : 0);
+  }
   double mn = 0.0, mx = 0.0, v = (double)value;
-  if (lane == 0) { mn = t.mn[b]; mx = t.mx[b]; t.nexp[b] = e + 1; }
+  if (lane == 0) { mn = t.mn[b]; mx = t.mx[b]; if (grow) t.nexp[b] = e + 1; }
   mz_tree_backup_path<G>(t, o, path, len, tp, lane, reward, v, mn, mx);
   if (lane == 0) {
-    t.E[o + leafnode] = e;
-    t.TP[o + leafnode] = (int8_t)tp;
-    t.R[o + leafnode] = reward;
+    if (grow) {
+      t.E[o + leafnode] = e;
+      t.TP[o + leafnode] = (int8_t)tp;
+      t.R[o + leafnode] = reward;
+    }
     t.mn[b] = mn;
     t.mx[b] = mx;
   }
+  return e;
 }
 
 // MCTS.backpropagate (mcts.py:126-143) along path[0 .. len), leaf last: the leaf takes `reward` and to_play tp, every node

@@ -13,6 +13,7 @@
 #include "mz_common.h"
 #include "mz_games.h"
 #include "mz_tree.hip.h"
+#include "mz_tree_host.h"      // (the host twin's trees, mz_truemodel_host.inc)
 
 // side state of one expansion slot, and (pend) of the leaf the last descent selected
 struct alignas(16) MzTmSlot {
@@ -65,132 +66,57 @@ __host__ __device__ inline void mz_tm_leaf(int kind, MzTmSlot &u, int action, in
   mz_game_observe(kind, u.bd, -mp, nullptr, mask != 0u, O, A, obs, legal);
 }
 
-// The descent of MCTS.run (mz_tree_select's arithmetic, operation for operation) over the children that exist: at every
-// expanded node the legal actions of its stored position.  It ends at a node that is not expanded, or at a finished one (a
-// slot with an empty child mask): that is a revisit, nothing will be expanded.  Lane 0 then leaves the leaf's record in
-// tm.pend[b] and its observation in tm.obs[b].
+// the children that exist in a true-rules tree: at every expanded node the legal actions of its stored position (slot 0 holds
+// the root's own mask); a finished node has none, and the descent stops at it
+struct MzTmChildren {
+  static constexpr bool stops = true;
+  const MzTmSlot *slots;
+  __device__ __forceinline__ bool exists(int e, int, int lane, bool &none) const {
+    const uint32_t mask = slots[e].mask;      // (the same word in every lane of the group)
+    none = mask == 0u;
+    return (mask >> lane) & 1u;
+  }
+};
+
+// The descent (mz_tree_descend by PUCT, mz_tree.hip.h) over those children.  It ends at a node that is not expanded, or at a
+// finished one: that is a revisit, nothing will be expanded.  Lane 0 then leaves the leaf's record in tm.pend[b] and its
+// observation in tm.obs[b].
 template <int G>
 __device__ __forceinline__ void mz_tm_select(const TreeView &t, const TmState &tm, int O, int b, int lane) {
-  const int A = t.A;
   const size_t o = mz_slab(t, b);
-  int32_t *path = t.path + (size_t)b * t.PL;
-  MzTmSlot *slots = tm.slots + (size_t)b * (size_t)(t.sims + 1);
-  const double mn = t.mn[b], mx = t.mx[b];
-  int node = 0, parent_e = 0, len = 1, a_sel = -1;
-  const MzNode root = mz_node_load(t, o);
-  int tp = root.TP;
-  if (lane == 0) path[0] = 0;
-  int e = root.E, Np = root.N;
-  bool revisit = false;
-  while (e >= 0) {
-    const uint32_t mask = slots[e].mask;      // (requested beside the children's records and the tables)
-    const int ch = 1 + e * A + lane;
-    const bool valid = lane < A && ((mask >> lane) & 1u);
-    double score = 0.0;
-    int best = -1, ce = -1, cn = 0;
-    const double lgn = t.logtab[Np], sqn = t.sqrttab[Np];
-    if (mask == 0u) { revisit = true; break; }      // a finished node: the same word in every lane of the group
-    if (valid) {
-      const MzNode c = mz_node_load(t, o + ch);
-      const int Nc = c.N;
-      const double p = c.P;
-      ce = c.E; cn = Nc;
-      if (Np == 0) {
-        score = p;                                     // fresh root: rank by prior (mcts.py:105-108)
-      } else {
-        const double pb_c = lgn * (sqn / (double)(Nc + 1));
-        const double prior_score = pb_c * p;
-        double value_score;
-        if (Nc > 0) {
-          value_score = mz_normalize(mz_child_q(c.W, Nc, c.R, t.two_players, t.discount), mn, mx);
-        } else {
-          value_score = t.init_value_score;
-        }
-        score = prior_score + value_score;
-      }
-      best = lane;
-    }
-    // tuple max over (score, action): ties go to the largest action (mcts.py:106-112)
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-      const double os = __shfl_xor(score, off, G);
-      const int ob = __shfl_xor(best, off, G), oe = __shfl_xor(ce, off, G), on = __shfl_xor(cn, off, G);
-      const bool take = ob >= 0 && (best < 0 || os > score || (os == score && ob > best));
-      if (take) { score = os; best = ob; ce = oe; cn = on; }
-    }
-    a_sel = best;
-    parent_e = e;
-    node = 1 + e * A + a_sel;
-    if (lane == 0) path[len] = node;
-    ++len;
-    if (t.two_players) tp = -tp;
-    e = ce;
-    Np = cn;
-  }
+  const MzTmSlot *slots = tm.slots + (size_t)b * (size_t)(t.sims + 1);
+  MzPuctRule<G, MzTmChildren> rule = {t, o, lane, t.mn[b], t.mx[b], {slots}, 0};
+  const MzDescent d = mz_tree_descend<G>(t, b, lane, rule);
   if (lane == 0) {
-    t.plen[b] = len;
-    t.leaf_tp[b] = (int8_t)tp;
-    t.leaf[b] = node;
-    t.slot[b] = parent_e;
-    t.act[b] = a_sel;
-    t.depth[b] = len - 1;
     float *obs = tm.obs + (size_t)b * O;
     MzTmSlotBits u;
-    if (revisit) {
+    if (d.stopped) {
       u.q[0] = u.q[1] = u.q[2] = u.q[3] = mz_i32x4{0, 0, 0, 0};
-      u.s.reward = t.R[o + node];      // stored at its first visit
-      u.s.mover = (int8_t)tp;
+      u.s.reward = t.R[o + d.node];      // stored at its first visit
+      u.s.mover = (int8_t)d.tp;
       u.s.fin = 1;
       u.s.revisit = 1;
       for (int k = 0; k < O; ++k) obs[k] = 0.f;
     } else {
-      mz_tm_slot_load(u, slots + parent_e);
-      mz_tm_leaf(tm.kind, u.s, a_sel, O, A, obs);
+      mz_tm_slot_load(u, slots + d.slot);
+      mz_tm_leaf(tm.kind, u.s, d.act, O, t.A, obs);
     }
     mz_tm_slot_store(tm.pend + b, u);
     tm.leaf_fin[b] = u.s.fin;
   }
 }
 
-// Node.expand over the leaf's legal actions (priors as mz_tree_root forms the root's: exp(logit) in double over the legal
-// actions in ascending order, no max-shift, divided by their sum; an illegal child is marked TP = 0, prior 0) + the
-// unchanged MCTS.backpropagate.  A finished leaf backs up value 0 with the true reward; at its first visit it takes its
-// slot with an empty child mask, a revisit expands nothing.  value / logits: this tree's network outputs (unused when
-// the leaf is finished).
+// expand + backup (mz_tree_expand_backup) of the pending leaf over its position's legal actions.  A finished leaf backs up
+// value 0 with the true reward; at its first visit it takes its slot with an empty child mask, a revisit expands nothing.
+// value / logits: this tree's network outputs (unused when the leaf is finished).
 template <int G>
 __device__ __forceinline__ void mz_tm_expand_backup(const TreeView &t, const TmState &tm, int b, int lane, float value,
                                                     const float *logits) {
-  const int A = t.A;
-  const size_t o = mz_slab(t, b);
-  const int32_t *path = t.path + (size_t)b * t.PL;
-  const int len = t.plen[b];
-  const int tp = t.leaf_tp[b];
-  const int e = t.nexp[b];
-  const int leafnode = path[len - 1];
   MzTmSlotBits u;
   mz_tm_slot_load(u, tm.pend + b);      // (one address for the group's lanes)
-  const bool revisit = u.s.revisit != 0, fin = u.s.fin != 0;
-  const float reward = u.s.reward;
-  if (!revisit) {
-    const bool ok = lane < A && ((u.s.mask >> lane) & 1u);
-    const double p = ok ? exp((double)logits[lane]) : 0.0;
-    double sum = 0.0;
-    for (int a = 0; a < A; ++a) sum = sum + __shfl(p, a, G);      // + 0.0 for illegal slots is exact
-    if (lane < A) mz_node_fresh(t, o + 1 + e * A + lane, ok ? p / sum : 0.0, ok ? 1 : 0);
-    if (lane < 4) ((mz_i32x4 *)(tm.slots + (size_t)b * (size_t)(t.sims + 1) + e))[lane] = u.q[lane];
-  }
-  double mn = 0.0, mx = 0.0, v = fin ? 0.0 : (double)value;
-  if (lane == 0) { mn = t.mn[b]; mx = t.mx[b]; if (!revisit) t.nexp[b] = e + 1; }
-  mz_tree_backup_path<G>(t, o, path, len, tp, lane, reward, v, mn, mx);
-  if (lane == 0) {
-    if (!revisit) {
-      t.E[o + leafnode] = e;
-      t.TP[o + leafnode] = (int8_t)tp;
-      t.R[o + leafnode] = reward;
-    }
-    t.mn[b] = mn;
-    t.mx[b] = mx;
-  }
+  const bool grow = u.s.revisit == 0;
+  const int e = mz_tree_expand_backup<G>(t, b, lane, u.s.fin != 0 ? 0.f : value, u.s.reward, logits, MzExpandMask{u.s.mask, grow});
+  if (grow && lane < 4) ((mz_i32x4 *)(tm.slots + (size_t)b * (size_t)(t.sims + 1) + e))[lane] = u.q[lane];
 }
 
 // ------------------------------------------------------------------ kernels

@@ -34,16 +34,15 @@ int mz_tm_root(mz_engine *e, const int8_t *boards, const int8_t *turn, const int
   return 0;
 }
 
-// the pending descent, launched if there is none
+// ---- the stepwise search: the step protocol of mz_engine.hip with this variant's readiness, kernels and leaf outputs
+static bool tm_ready(const mz_engine *e) { return e->tm.kind && e->tm.root_set; }
+
 static int tm_pending(mz_engine *e, const char *fn, hipStream_t s) {
-  if (!e->tm.kind || !e->tm.root_set) return fail("%s: call mz_tm_root first", fn);
-  if (e->sims_done >= e->sims) return fail("%s: all %d simulations already done", fn, e->sims);
-  if (!e->selection_valid) {
-    TREE_LAUNCH(k_tm_select, s, e->tv, e->tm, e->O);
-    HIPCHECK(hipGetLastError());
-    e->selection_valid = true;
-  }
-  return 0;
+  return step_pending(e, fn, tm_ready(e), "mz_tm_root", [&] { TREE_LAUNCH(k_tm_select, s, e->tv, e->tm, e->O); });
+}
+
+static int tm_step(mz_engine *e, const char *fn, const float *value, const float *logits, bool more, hipStream_t s) {
+  return step_advance(e, fn, tm_ready(e), "mz_tm_select", more, [&](bool m) { TM_LAUNCH(k_tm_step, s, value, logits, m ? 1 : 0); });
 }
 
 static int tm_leaf_out(mz_engine *e, float *obs_out, uint8_t *finished_out, hipStream_t s) {
@@ -63,37 +62,24 @@ int mz_tm_select(mz_engine *e, float *obs_out, uint8_t *finished_out, void *stre
 int mz_tm_expand_backup(mz_engine *e, const float *value, const float *logits, void *stream) {
   if (!e || !value || !logits) return fail("mz_tm_expand_backup: null argument");
   MZ_ENTER(e);
-  if (!e->tm.kind || !e->tm.root_set || !e->selection_valid) return fail("mz_tm_expand_backup: call mz_tm_select first");
-  if (e->sims_done >= e->sims) return fail("mz_tm_expand_backup: all %d simulations already done", e->sims);
-  hipStream_t s = (hipStream_t)stream;
-  TM_LAUNCH(k_tm_step, s, value, logits, 0);
-  HIPCHECK(hipGetLastError());
-  e->sims_done += 1;
-  e->selection_valid = false;
-  return 0;
+  return tm_step(e, "mz_tm_expand_backup", value, logits, false, (hipStream_t)stream);
 }
 
 int mz_tm_expand_backup_select(mz_engine *e, const float *value, const float *logits, float *obs_out, uint8_t *finished_out,
                                void *stream) {
   if (!e || !value || !logits) return fail("mz_tm_expand_backup_select: null argument");
   MZ_ENTER(e);
-  if (!e->tm.kind || !e->tm.root_set || !e->selection_valid) return fail("mz_tm_expand_backup_select: call mz_tm_select first");
-  if (e->sims_done >= e->sims) return fail("mz_tm_expand_backup_select: all %d simulations already done", e->sims);
-  if (e->sims_done + 1 >= e->sims)        // the move's last simulation: nothing to descend for
-    return mz_tm_expand_backup(e, value, logits, stream);
   hipStream_t s = (hipStream_t)stream;
-  TM_LAUNCH(k_tm_step, s, value, logits, 1);
-  HIPCHECK(hipGetLastError());
-  e->sims_done += 1;
-  e->selection_valid = true;
-  return tm_leaf_out(e, obs_out, finished_out, s);
+  const bool more = step_more(e);
+  if (tm_step(e, "mz_tm_expand_backup_select", value, logits, more, s)) return -1;
+  return more ? tm_leaf_out(e, obs_out, finished_out, s) : 0;
 }
 
 int mz_tm_search(mz_engine *e, int num_simulations, void *stream) {
   if (!e) return fail("mz_tm_search: null engine");
   MZ_ENTER(e);
   if (!e->weights_set) return fail("mz_tm_search: weights not set (call mz_set_weights)");
-  if (!e->tm.kind || !e->tm.root_set) return fail("mz_tm_search: call mz_tm_root first");
+  if (!tm_ready(e)) return fail("mz_tm_search: call mz_tm_root first");
   if (num_simulations < 1 || e->sims_done + num_simulations > e->sims)
     return fail("mz_tm_search: %d + %d simulations exceed the pool sized for num_simulations = %d", e->sims_done,
                 num_simulations, e->sims);
@@ -105,12 +91,8 @@ int mz_tm_search(mz_engine *e, int num_simulations, void *stream) {
   leaf_tv.root_value = e->tm.value;
   leaf_tv.root_logits = e->tm.logits;
   for (int i = 0; i < num_simulations; ++i) {
-    const int more = (e->sims_done + 1 < e->sims) ? 1 : 0;      // (the move's last simulation: nothing to descend for)
     if (launch_root(e, leaf_tv, e->tm.obs, false, s)) return -1;
-    TM_LAUNCH(k_tm_step, s, (const float *)e->tm.value, (const float *)e->tm.logits, more);
-    HIPCHECK(hipGetLastError());
-    e->sims_done += 1;
-    e->selection_valid = more != 0;
+    if (tm_step(e, "mz_tm_search", e->tm.value, e->tm.logits, step_more(e), s)) return -1;
   }
   return 0;
 }

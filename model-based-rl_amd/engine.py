@@ -447,7 +447,7 @@ class Engine(object):
     return tuple(float(x) for x in out)
 
   def select(self):
-    out = [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(4)]
+    out = self._selection_out(4)
     _abi.check(self.lib.mz_select(self._h, *[_ptr(o) for o in out], self.stream), 'mz_select')
     return out   # leaf_node, parent_slot, action, depth
 
@@ -463,22 +463,25 @@ class Engine(object):
     _abi.check(self.lib.mz_gather_hidden(self._h, _ptr(h), self.stream), 'mz_gather_hidden')
     return h
 
+  def _tree_step(self, name, inputs, outputs=None, n_out=0):
+    """the ABI call `name` of one simulation's tree step: inputs as float32 device tensors (None: NULL), then the n_out
+    pointers of an *_expand_backup_select -- of the tensors in `outputs`, or NULL each (None: the move's last simulation);
+    returns outputs"""
+    ins = [_ptr(self._dev(x, torch.float32)) for x in inputs]
+    outs = [None] * n_out if outputs is None else [_ptr(o) for o in outputs]
+    _abi.check(getattr(self.lib, name)(self._h, *ins, *outs, self.stream), name)
+    return outputs
+
+  def _selection_out(self, n):
+    return [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(n)]
+
   def expand_backup(self, value, reward, logits, hidden=None):
-    value = self._dev(value, torch.float32); reward = self._dev(reward, torch.float32)
-    logits = self._dev(logits, torch.float32); hidden = self._dev(hidden, torch.float32)
-    _abi.check(self.lib.mz_expand_backup(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), self.stream),
-               'mz_expand_backup')
+    self._tree_step('mz_expand_backup', (value, reward, logits, hidden))
 
   def expand_backup_select(self, value, reward, logits, hidden=None, last=False):
     """expand_backup of this simulation and select of the next in one launch (mz_expand_backup_select); returns what
     select() returns, or None after the move's last simulation (`last`: the caller's count of simulations)"""
-    value = self._dev(value, torch.float32); reward = self._dev(reward, torch.float32)
-    logits = self._dev(logits, torch.float32); hidden = self._dev(hidden, torch.float32)
-    out = None if last else [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(4)]
-    ptrs = [None] * 4 if last else [_ptr(o) for o in out]
-    _abi.check(self.lib.mz_expand_backup_select(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), *ptrs, self.stream),
-               'mz_expand_backup_select')
-    return out
+    return self._tree_step('mz_expand_backup_select', (value, reward, logits, hidden), None if last else self._selection_out(4), 4)
 
   # ---- the true-rules search (mz_set_true_model, mz_tm_*, include/mz_engine.h; DESIGN s7g)
   def set_true_model(self, kind):
@@ -506,18 +509,12 @@ class Engine(object):
     return obs, fin
 
   def tm_expand_backup(self, value, logits):
-    value = self._dev(value, torch.float32); logits = self._dev(logits, torch.float32)
-    _abi.check(self.lib.mz_tm_expand_backup(self._h, _ptr(value), _ptr(logits), self.stream), 'mz_tm_expand_backup')
+    self._tree_step('mz_tm_expand_backup', (value, logits))
 
   def tm_expand_backup_select(self, value, logits, last=False):
     """tm_expand_backup of this simulation and tm_select of the next in one launch; returns what tm_select returns, or None
     after the move's last simulation (`last`: the caller's count of simulations)"""
-    value = self._dev(value, torch.float32); logits = self._dev(logits, torch.float32)
-    out = None if last else self._tm_leaf_out()
-    ptrs = [None, None] if last else [_ptr(o) for o in out]
-    _abi.check(self.lib.mz_tm_expand_backup_select(self._h, _ptr(value), _ptr(logits), *ptrs, self.stream),
-               'mz_tm_expand_backup_select')
-    return out
+    return self._tree_step('mz_tm_expand_backup_select', (value, logits), None if last else self._tm_leaf_out(), 2)
 
   def tm_search(self, num_simulations=None):
     n = self.sims if num_simulations is None else int(num_simulations)
@@ -547,31 +544,19 @@ class Engine(object):
     g = None if gumbel is None else self._dev(gumbel, torch.float64).reshape(self.B, self.A)
     _abi.check(self.lib.mz_gz_root(self._h, _ptr(g), int(move), self.stream), 'mz_gz_root')
 
-  def _gz_leaf_out(self):
-    return [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(2)]
-
   def gz_select(self):
     """mz_gz_select -> (parent_slot [B], action [B]) int32; gather_hidden() gives the parents' hidden states"""
-    out = self._gz_leaf_out()
+    out = self._selection_out(2)
     _abi.check(self.lib.mz_gz_select(self._h, _ptr(out[0]), _ptr(out[1]), self.stream), 'mz_gz_select')
     return out
 
   def gz_expand_backup(self, value, reward, logits, hidden=None):
-    value = self._dev(value, torch.float32); reward = self._dev(reward, torch.float32)
-    logits = self._dev(logits, torch.float32); hidden = self._dev(hidden, torch.float32)
-    _abi.check(self.lib.mz_gz_expand_backup(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), self.stream),
-               'mz_gz_expand_backup')
+    self._tree_step('mz_gz_expand_backup', (value, reward, logits, hidden))
 
   def gz_expand_backup_select(self, value, reward, logits, hidden=None, last=False):
     """gz_expand_backup of this simulation and gz_select of the next in one launch; returns what gz_select returns, or None
     after the move's last simulation (`last`: the caller's count of simulations)"""
-    value = self._dev(value, torch.float32); reward = self._dev(reward, torch.float32)
-    logits = self._dev(logits, torch.float32); hidden = self._dev(hidden, torch.float32)
-    out = None if last else self._gz_leaf_out()
-    ptrs = [None, None] if last else [_ptr(o) for o in out]
-    _abi.check(self.lib.mz_gz_expand_backup_select(self._h, _ptr(value), _ptr(reward), _ptr(logits), _ptr(hidden), *ptrs,
-                                                   self.stream), 'mz_gz_expand_backup_select')
-    return out
+    return self._tree_step('mz_gz_expand_backup_select', (value, reward, logits, hidden), None if last else self._selection_out(2), 2)
 
   def gz_search(self, num_simulations=None):
     n = self.sims if num_simulations is None else int(num_simulations)

@@ -82,6 +82,21 @@ def test_host_twin_equals_the_restatement(searched, name, scale):
 
 
 @pytest.mark.parametrize('name', list(gp.SETS))
+@pytest.mark.parametrize('scale', [1.0, 0.0], ids=['given_G', 'no_noise'])
+def test_host_twin_reproduces_the_pinned_outputs(searched, name, scale):
+  """Every output array of mz_gz_search_host on the committed sets, bit for bit, as the twin gave it before its tree code
+  moved into csrc/mz_tree_host.h -- vhat, paths, plens and min_gap included.  The digests and the snippet that writes them:
+  tests/golden/search_twins_sha256.json, test_truemodel_cpu.test_host_twin_reproduces_the_pinned_outputs."""
+  import os
+  from tests.test_truemodel_cpu import array_digests
+  with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'search_twins_sha256.json')) as f:
+    want = json.load(f)['gz/%s/%g' % (name, scale)]
+  got = array_digests(searched[name, scale][0])
+  assert sorted(got) == sorted(want)
+  assert [k for k in sorted(got) if got[k] != want[k]] == []
+
+
+@pytest.mark.parametrize('name', list(gp.SETS))
 def test_the_sets_reach_the_cases_that_can_go_wrong(searched, name):
   c = gp.case(name)
   assert sorted(c['legal'].sum(1).tolist())[:3] == [1, 2, 3]

@@ -61,6 +61,44 @@ def test_host_twin_equals_the_restatement(searched, kind, with_noise):
     assert (host['E'][b][gone] == -1).all()
 
 
+def array_digests(d):
+  """SHA-256 of every array a host twin returns (C order, its own dtype)"""
+  import hashlib
+  return {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in d.items()}
+
+
+@pytest.mark.parametrize('kind', [1, 3], ids=['tictactoe', 'connect_four'])
+@pytest.mark.parametrize('with_noise', [False, True], ids=['plain', 'noise'])
+def test_host_twin_reproduces_the_pinned_outputs(searched, kind, with_noise):
+  """Every output array of mz_tm_search_host on the committed positions, bit for bit, as the twin gave it before its tree
+  code moved into csrc/mz_tree_host.h -- leaf_depth and the slot records included, which the restatement does not all
+  cover.  tests/golden/search_twins_sha256.json holds the digests of both twins (keys tm/<kind>/<plain|noise> and
+  gz/<set>/<scale>); from a checkout of the commit to pin, built, in the repository root:
+
+    import json
+    from tests import gumbel_py as gp, truemodel_py as tp
+    from tests.test_gumbel_cpu import host_search
+    from tests.test_truemodel_cpu import _cfg, array_digests
+    from model_based_rl_amd.engine import tm_search_host
+    out = {}
+    for kind in (1, 3):
+      A = 9 if kind == 1 else 7
+      bd, tn, st, lg, noise = tp.case_positions(kind)
+      for name, nz in (('plain', None), ('noise', noise)):
+        host = tm_search_host(_cfg(kind, len(bd)), kind, bd, tn, st, lg, lambda obs: tp.fake_network(obs, A), noise=nz)
+        out['tm/%d/%s' % (kind, name)] = array_digests(host)
+    for name in gp.SETS:
+      for scale in (1.0, 0.0):
+        out['gz/%s/%g' % (name, scale)] = array_digests(host_search(gp.case(name), scale))
+    json.dump(out, open('tests/golden/search_twins_sha256.json', 'w'), indent=1, sort_keys=True)"""
+  import os
+  with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'search_twins_sha256.json')) as f:
+    want = json.load(f)['tm/%d/%s' % (kind, 'noise' if with_noise else 'plain')]
+  got = array_digests(searched[kind, with_noise][0])
+  assert sorted(got) == sorted(want)
+  assert [k for k in sorted(got) if got[k] != want[k]] == []
+
+
 @pytest.mark.parametrize('kind', [1, 3], ids=['tictactoe', 'connect_four'])
 def test_the_positions_reach_the_cases_that_can_go_wrong(searched, kind):
   host, _, (bd, tn, st) = searched[kind, False]
