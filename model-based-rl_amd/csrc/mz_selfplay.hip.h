@@ -49,6 +49,13 @@ struct SelfplayState {
 // Gamma(alpha) by Marsaglia-Tsang (alpha < 1: boost with U^(1/alpha)); counter-based draws.  float32 on the hardware's
 // own log2 / exp2 / cos / sqrt: this is a noise source, not a parity quantity (parity runs pass numpy's draw in), and
 // the float64 libm version of the same sampler cost 5.5 us of every move (a quarter of the root kernel).
+// Definition (restated in float64 by tests/dirichlet_py.py, which tests/test_gpu_dirichlet.py holds every caller to): alpha
+// rounded to float32; alpha' = alpha + 1 where alpha < 1; d = alpha' - 1/3, c = 1 / sqrt(9 d).  Iteration ctr = 0, 1, .. (at
+// most 64; ctr advances on every iteration, the v <= 0 ones included) draws the block of counter
+// (env, (uint32)move, a | ctr << 8, MZ_RNG_DIRICHLET << 24 | (move >> 32 & 0xFFFFFF)): u1 = 1 - (x >> 8) / 2^24,
+// u2 = (y >> 8) / 2^24, u = 1 - (z >> 8) / 2^24, normal = sqrt(-2 ln u1) cos(2 pi u2), v = (1 + c normal)^3, accepted when
+// 1 + c normal > 0 and ln u < normal^2 / 2 + d - d v + d ln v: g = d v.  alpha < 1: g *= U^(1/alpha), U = 1 - (x >> 8) / 2^24
+// of the block at ctr = 0xFFFFFF.
 __device__ inline float mz_u01f(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }      // [0, 1)
 __device__ inline double mz_gamma(double alpha, uint64_t seed, uint32_t env, uint64_t move, uint32_t a) {
   const float al = (float)alpha;
@@ -57,6 +64,7 @@ __device__ inline double mz_gamma(double alpha, uint64_t seed, uint32_t env, uin
   const float LN2 = 0.69314718f;
   const uint32_t c1 = (uint32_t)move, c3 = (MZ_RNG_DIRICHLET << 24) | ((uint32_t)(move >> 32) & 0xFFFFFFu);
   float g = d;
+  int k = 0;
   uint32_t ctr = 0;
   for (int it = 0; it < 64; ++it) {
     const mz_u4 r0 = mz_philox(seed, env, c1, a | (ctr++ << 8), c3);
@@ -70,9 +78,17 @@ __device__ inline double mz_gamma(double alpha, uint64_t seed, uint32_t env, uin
   }
   if (al < 1.0f) {
     const mz_u4 r = mz_philox(seed, env, c1, a | (0xFFFFFFu << 8), c3);
-    g *= __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(1.0f - mz_u01f(r.x)) / al);
+    // U^(1/alpha) = 2^e, e = log2(U) / alpha <= 0.  The power leaves float32 long before the draw stops mattering: at
+    // alpha = 0.03 e < -126 in 7 % of the draws, and a row whose legal actions ALL flushed to 0 came out uniform (the
+    // sum == 0 guard of the callers) where Dirichlet(0.03) is nearly one-hot: 0.8 % of the rows with two legal actions.
+    // So only the fractional part of e goes through exp2 (e - k in (-1, 0]); the integer part k scales the double, which
+    // holds it to 2^-1022.  (One exit and the truncating conversion: the form that keeps the headline kernel's scratch,
+    // tests/test_abi.py; floorf and a second return cost it 24 bytes a lane more.)
+    const float e = fmaxf(__builtin_amdgcn_logf(1.0f - mz_u01f(r.x)) / al, -2048.0f);
+    k = (int)e;
+    g *= __builtin_amdgcn_exp2f(e - (float)k);
   }
-  return (double)g;
+  return ldexp((double)g, k);
 }
 
 // noise[b] ~ Dirichlet(alpha * 1_legal)  (the draw of np.random.dirichlet in mcts.py:59, from the
