@@ -17,11 +17,14 @@ The host-environment path is the default.
 With --match the nets play each other instead of being evaluated one by one (match.py): every pair of --nets, every seed
 from both seats, on the device games.
 
+What a configuration's move rule is (Side) and what each option refuses (refuse, the refuse_* names) is stated in sides.py.
+
 FCNetwork checkpoints on host environments (envs.get_environment) only; the interactive tools of the reference (rendering,
 GIFs, plots, human play, MCTS PNG dumps) are refused.  One departure from the reference's output: its '[Game done]' line after
 every game (evaluate.py:376-379) is printed only with --verbose -- thousands of games are played per configuration here, and
 the summary block carries the same numbers."""
 import copy
+import itertools
 import json
 import os
 import sys
@@ -32,194 +35,13 @@ import torch
 
 from .config import CARTPOLE_TIME_LIMITS, get_evaluation_args
 from .engine import Engine, flatten_weights
-from .envs import BOARD_ENVS, DEVICE_ENVS, get_environment
+from .envs import DEVICE_ENVS, get_environment      # noqa: F401  (DEVICE_ENVS: read from here by callers)
 from .game import History
+from .sides import (Side, gumbel_params, refuse, refuse_device_env, refuse_gumbel, refuse_grade, refuse_grade_unroll,      # noqa: F401
+                    refuse_opp_playouts, refuse_true_model, refuse_unsupported)      # (the per-option entry points: importable from here)
 
 MAX_BATCH = 4096
 MOVES_PER_SYNC = 8      # --device_env: whole moves enqueued per host synchronisation
-
-REFUSED = (
-    ('render', 'rendering is an interactive tool and is not part of this evaluator (no display on the GPU machines).'),
-    ('save_gif_as', 'saving GIFs needs rendered frames, which this evaluator does not produce.'),
-    ('save_mcts', 'MCTS PNG dumps (pydot) are an interactive tool and are not part of this evaluator.'),
-    ('human_opp', 'human play is an interactive tool and is not part of this evaluator; use --random_opp.'),
-    ('plot_summary', 'plots are an interactive tool and are not part of this evaluator; use --out for a JSON summary.'),
-)
-
-
-def refuse_unsupported(args_or_config):
-  """one sentence per interactive flag the evaluator leaves out (NotImplementedError)"""
-  for name, why in REFUSED:
-    if getattr(args_or_config, name, None):
-      raise NotImplementedError('--%s: %s' % (name, why))
-
-
-def refuse_device_env(args_or_config):
-  """one sentence per configuration --device_env leaves out (NotImplementedError); nothing to refuse without the flag"""
-  c = args_or_config
-  if not getattr(c, 'device_env', False):
-    return
-  env = getattr(c, 'environment', None)
-  if env is not None and env not in DEVICE_ENVS:
-    raise NotImplementedError('--device_env: %s has no device form; the device environments are %s.' % (env, ', '.join(DEVICE_ENVS)))
-  if getattr(c, 'norm_obs', False):
-    raise NotImplementedError('--device_env: --norm_obs is not applied by the device environments; use the host path.')
-  m = getattr(c, 'apply_mcts_actions', 1)
-  if env == 'ConnectFour' and any(int(x) != 1 for x in (m if isinstance(m, (list, tuple)) else [m])):
-    raise NotImplementedError('--device_env: ConnectFour takes --apply_mcts_actions 1 only; below the root the walk offers full '
-                              'columns, which the host class refuses and a device game cannot.')
-
-
-PLAYOUT_ENVS = BOARD_ENVS
-
-
-def refuse_opp_playouts(args_or_config, match=False):
-  """one sentence per configuration --opp_playouts (the playout-search opponent of the device games) leaves out
-  (NotImplementedError); nothing to refuse at 0"""
-  c = args_or_config
-  n = int(getattr(c, 'opp_playouts', 0) or 0)
-  if n == 0:
-    return
-  if match:
-    raise NotImplementedError('--opp_playouts: --match plays two networks against each other and seats no playout opponent.')
-  if n < 64 or n > 65536 or n % 64:
-    raise NotImplementedError('--opp_playouts: the budget is a multiple of 64 in 64 to 65536 playouts per move, got %d.' % n)
-  if not getattr(c, 'device_env', False):
-    raise NotImplementedError('--opp_playouts: the playout opponent is planned on the device and needs --device_env.')
-  if getattr(c, 'random_opp', None) is None:
-    raise NotImplementedError('--opp_playouts: --random_opp names the seat the playout opponent takes and is missing.')
-  env = getattr(c, 'environment', None)
-  if env is not None and env not in PLAYOUT_ENVS:
-    raise NotImplementedError('--opp_playouts: %s has no playout opponent; it plays %s.' % (env, ' and '.join(PLAYOUT_ENVS)))
-  m = getattr(c, 'apply_mcts_actions', 1)
-  if any(int(x) != 1 for x in (m if isinstance(m, (list, tuple)) else [m])):
-    raise NotImplementedError('--opp_playouts: the playout opponent answers every move and takes --apply_mcts_actions 1 only.')
-
-
-GRADE_ENVS = BOARD_ENVS
-
-
-def refuse_grade(args_or_config, match=False):
-  """one sentence per configuration --grade (moves graded against the exact solver, solver.py) leaves out
-  (NotImplementedError, starting '--grade: '); nothing to refuse without the flag, but --grade_table, which only chooses
-  the grading's search (a sentence starting '--grade_table: ')"""
-  c = args_or_config
-  if not getattr(c, 'grade', False):
-    if getattr(c, 'grade_table', False):
-      raise NotImplementedError('--grade_table: it chooses the search that --grade solves with and grades nothing without --grade.')
-    return
-  if match:
-    raise NotImplementedError('--grade: the games of --match are not graded; grade each network with evaluate --device_env --grade.')
-  if not getattr(c, 'device_env', False):
-    raise NotImplementedError('--grade: the graded games are the device environments\' and need --device_env.')
-  env = getattr(c, 'environment', None)
-  if env is not None and env not in GRADE_ENVS:
-    raise NotImplementedError('--grade: %s has no exact solver; it solves %s.' % (env, ' and '.join(GRADE_ENVS)))
-  m = getattr(c, 'apply_mcts_actions', 1)
-  if any(int(x) != 1 for x in (m if isinstance(m, (list, tuple)) else [m])):
-    raise NotImplementedError('--grade: a graded decision is one searched move and takes --apply_mcts_actions 1 only.')
-
-
-def refuse_grade_unroll(args_or_config):
-  """one sentence per configuration --grade_unroll K (the model by unroll depth, solver.grade_unroll) leaves out
-  (NotImplementedError, starting '--grade_unroll: '); nothing to refuse without the flag.  What --grade refuses stays
-  refused by --grade's own sentence (refuse_grade runs first).  --no_support checkpoints are served: the unroll goes through
-  mz_initial_inference and mz_recurrent_inference, which read the heads' single outputs."""
-  c = args_or_config
-  K = getattr(c, 'grade_unroll', None)
-  if K is None or K is False:
-    return
-  if not getattr(c, 'grade', False):
-    raise NotImplementedError('--grade_unroll: it unrolls the model along the games --grade keeps and does nothing without --grade.')
-  if int(K) < 1 or int(K) > Engine.UNROLL_MAX_K:
-    raise NotImplementedError('--grade_unroll: the depth is 1 to %d dynamics steps, got %d.' % (Engine.UNROLL_MAX_K, int(K)))
-
-
-TRUE_MODEL_ENVS = BOARD_ENVS
-
-
-def refuse_true_model(args_or_config, match=False):
-  """one sentence per configuration --true_model (the search on the true rules of the device games, Engine.tm_search) leaves
-  out (NotImplementedError, starting '--true_model: '); nothing to refuse while every value is 0.  The lists of the command
-  line are read per side with --match (one value: both sides) and as alternatives without it."""
-  c = args_or_config
-  alls = lambda x: list(x) if isinstance(x, (list, tuple)) else [x]
-  tm = [int(x or 0) for x in alls(getattr(c, 'true_model', 0))]
-  if not any(tm):
-    return
-  if any(x not in (0, 1) for x in tm):
-    raise NotImplementedError('--true_model: the values are 0 (the learned model) and 1 (the true rules), got %r.' % (tm,))
-  if not match and not getattr(c, 'device_env', False):
-    raise NotImplementedError('--true_model: the true-rules search reads the device games\' positions and needs --device_env (or --match).')
-  env = getattr(c, 'environment', None)
-  if env is not None and env not in TRUE_MODEL_ENVS:
-    raise NotImplementedError('--true_model: %s has no true-rules search; it searches %s.' % (env, ' and '.join(TRUE_MODEL_ENVS)))
-  if any(int(x) != 1 for x in alls(getattr(c, 'apply_mcts_actions', 1))):
-    raise NotImplementedError('--true_model: a move of the true-rules search applies one action and takes --apply_mcts_actions 1 only.')
-  prior, value = [int(x or 0) for x in alls(getattr(c, 'only_prior', 0))], [int(x or 0) for x in alls(getattr(c, 'only_value', 0))]
-  pick = lambda v, k: v[k if len(v) == 2 else 0]
-  sides = range(2) if match else [0]
-  if any(pick(tm, k) and ((pick(prior, k) or pick(value, k)) if match else (any(prior) or any(value))) for k in sides):
-    raise NotImplementedError('--true_model: --only_prior / --only_value run no search; a side takes one of them or the true-rules search.')
-  if getattr(c, 'architecture', 'FCNetwork') != 'FCNetwork':
-    raise NotImplementedError('--true_model: the architecture %s has no engine path; FCNetwork checkpoints only.' % c.architecture)
-
-
-GUMBEL_DEFAULTS = dict(gumbel_considered=16, gumbel_c_visit=50.0, gumbel_c_scale=1.0, gumbel_scale=0.0)
-
-
-def gumbel_params(args_or_config):
-  """(max_considered, c_visit, c_scale, gumbel_scale) of a command line or a config, the defaults where it has none"""
-  g = lambda k: getattr(args_or_config, k, None)
-  return tuple(type(v)(v if g(k) is None else g(k)) for k, v in GUMBEL_DEFAULTS.items())
-
-
-def refuse_gumbel(args_or_config, match=False):
-  """one sentence per configuration --gumbel (the Gumbel MuZero search, Engine.gz_search) leaves out (NotImplementedError,
-  starting '--gumbel: '); nothing to refuse while every value is 0.  The lists of the command line are read per side with
-  --match (one value: both sides) and as alternatives without it."""
-  c = args_or_config
-  alls = lambda x: list(x) if isinstance(x, (list, tuple)) else [x]
-  gz = [int(x or 0) for x in alls(getattr(c, 'gumbel', 0))]
-  if not any(gz):
-    return
-  if any(x not in (0, 1) for x in gz):
-    raise NotImplementedError('--gumbel: the values are 0 (PUCT) and 1 (the Gumbel search), got %r.' % (gz,))
-  if not match and not getattr(c, 'device_env', False):
-    raise NotImplementedError('--gumbel: the Gumbel search is served by the device games\' move loop and needs --device_env (or --match).')
-  if any(int(x) != 1 for x in alls(getattr(c, 'apply_mcts_actions', 1))):
-    raise NotImplementedError('--gumbel: a move of the Gumbel search applies one action and takes --apply_mcts_actions 1 only.')
-  pick = lambda v, k: v[k if len(v) == 2 else 0]
-  on_side = lambda v: any(pick(gz, k) and pick(v, k) for k in range(2)) if match else any(v)
-  if on_side([int(x or 0) for x in alls(getattr(c, 'use_exploration_noise', 0))]):
-    raise NotImplementedError('--gumbel: the Gumbel draw replaces the exploration noise at the root; a side takes --use_exploration_noise or the Gumbel search (--gumbel_scale is its stochastic setting).')
-  temps = getattr(c, 'temperatures', None)
-  temps = [float(x or 0) for x in alls(getattr(c, 'temperature', 0) if temps is None else temps)]
-  if on_side([t != 0 for t in temps]):
-    raise NotImplementedError('--gumbel: the move is chosen by the rule of the search, not sampled from the visits; a side takes temperature 0 (--gumbel_scale is the stochastic setting).')
-  prior, value = [int(x or 0) for x in alls(getattr(c, 'only_prior', 0))], [int(x or 0) for x in alls(getattr(c, 'only_value', 0))]
-  if on_side(prior) or on_side(value):
-    raise NotImplementedError('--gumbel: --only_prior / --only_value run no search; a side takes one of them or the Gumbel search.')
-  if on_side([int(x or 0) for x in alls(getattr(c, 'true_model', 0))]):
-    raise NotImplementedError('--gumbel: an engine searches the true rules or with the Gumbel search; a side takes --true_model or --gumbel.')
-  if getattr(c, 'architecture', 'FCNetwork') != 'FCNetwork':
-    raise NotImplementedError('--gumbel: the architecture %s has no engine path; FCNetwork checkpoints only.' % c.architecture)
-  m, cv, cs, sc = gumbel_params(c)
-  if m < 2:
-    raise NotImplementedError('--gumbel: --gumbel_considered must be at least 2, got %d.' % m)
-  if not cv >= 0:
-    raise NotImplementedError('--gumbel: --gumbel_c_visit must not be negative, got %g.' % cv)
-  if not cs > 0:
-    raise NotImplementedError('--gumbel: --gumbel_c_scale must be positive, got %g.' % cs)
-  if not sc >= 0:
-    raise NotImplementedError('--gumbel: --gumbel_scale must not be negative, got %g.' % sc)
-
-
-def gumbel_line(config):
-  """the printed line that names a configuration's search"""
-  if not getattr(config, 'gumbel', 0):
-    return 'Search: PUCT'
-  return 'Search: Gumbel, m = %d, c_visit = %g, c_scale = %g, gumbel_scale = %g' % gumbel_params(config)
 
 
 class DeviceGame(object):
@@ -281,13 +103,7 @@ class Evaluator(SummaryTools):
     if getattr(self.config, 'architecture', 'FCNetwork') != 'FCNetwork':
       raise NotImplementedError('the evaluator runs FCNetwork checkpoints only (%s has no batched evaluation path here)'
                                 % self.config.architecture)
-    refuse_unsupported(self.config)
-    refuse_device_env(self.config)
-    refuse_opp_playouts(_with(self.config, device_env=True))      # (play_games(device_env=True) may still name the device path)
-    refuse_grade(_with(self.config, device_env=True))
-    refuse_grade_unroll(self.config)
-    refuse_true_model(_with(self.config, device_env=True))
-    refuse_gumbel(_with(self.config, device_env=True))
+    refuse(self.config, lenient=True)      # (play_games(device_env=True) may still name the device path)
     self.grade_report = None      # --grade: the report of the last play_games (solver.grade_games)
     self.grade_unroll_report = None      # --grade_unroll K: the model by unroll depth on the same games (solver.grade_unroll)
     if not torch.cuda.is_available():
@@ -324,126 +140,94 @@ class Evaluator(SummaryTools):
     Gumbel search (Engine.gz_search; device path; True: the config's gumbel_* parameters, else their defaults; or a dict of
     Engine.set_gumbel's arguments)."""
     device_env = bool(device_env or getattr(self.config, 'device_env', False))
-    true_model = bool(true_model or getattr(self.config, 'true_model', 0))
-    refuse_true_model(_with(self.config, device_env=device_env, true_model=int(true_model)))
-    gumbel = gumbel or bool(getattr(self.config, 'gumbel', 0))
-    if gumbel:
-      m, cv, cs, sc = gumbel_params(self.config)
-      given = gumbel if isinstance(gumbel, dict) else {}
-      gumbel = dict(dict(max_considered=m, c_visit=cv, c_scale=cs, gumbel_scale=sc), **given)
-      refuse_gumbel(_with(self.config, device_env=device_env, gumbel=1, true_model=int(true_model), gumbel_considered=gumbel['max_considered'],
-                          gumbel_c_visit=gumbel['c_visit'], gumbel_c_scale=gumbel['c_scale'], gumbel_scale=gumbel['gumbel_scale']))
+    side = Side.of(self.config, true_model or None, gumbel or None)
+    refuse(self.config, device_env=device_env, side=side)
     grade = bool(getattr(self.config, 'grade', False))
     keep_history = bool(keep_history or grade or getattr(self.config, 'keep_history', False))
-    refuse_opp_playouts(_with(self.config, device_env=device_env))
-    refuse_grade(_with(self.config, device_env=device_env))
-    refuse_grade_unroll(self.config)
     assert self.weights is not None, '.load_network() needs to be called before playing.'
     if device_env and environments is not None:
       raise ValueError('play_games: a device-environment run builds no host environment')
     if start_states is not None and not device_env:
       raise ValueError('play_games: start_states are the device path\'s; give the host path environments that hold them')
-    if seeds is None:
-      base = int(np.random.randint(0, 2 ** 30))
-      seeds = list(range(base, base + num_games))
-    seeds = [int(s) for s in seeds]
-    if len(seeds) != num_games or any(s != seeds[0] + i for i, s in enumerate(seeds)):
-      raise ValueError('play_games takes consecutive seeds, one per game (evaluate.py:476-479)')
+    seeds = consecutive_seeds(seeds, num_games, 'play_games takes consecutive seeds, one per game (evaluate.py:476-479)')
     games = []
     for lo in range(0, num_games, self.batch):
       hi = min(num_games, lo + self.batch)
       if device_env:
         games += self._play_batch_device(seeds[lo:hi], None if draws is None else draws[lo:hi],
-                                         None if start_states is None else start_states[lo:hi], keep_history, true_model, gumbel)
+                                         None if start_states is None else start_states[lo:hi], keep_history, side)
         continue
       envs = environments[lo:hi] if environments is not None else [get_environment(self.config) for _ in range(lo, hi)]
-      games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi])
+      games += self._play_batch(envs, seeds[lo:hi], None if draws is None else draws[lo:hi], side)
     if grade:
       self.grade_report = self.grade(games)
       if getattr(self.config, 'grade_unroll', None):
         self.grade_unroll_report = self.grade_unroll(games)
     return games
 
-  def grade(self, games):
-    """--grade: the keep_history games graded against the exact solver (solver.grade_games) -- the network's moves where
-    --random_opp seats an opponent, both sides' otherwise; TicTacToe every position, ConnectFour those with at most
-    config.grade_empties empty cells"""
+  def _graded(self, games, solve, weights=False):
+    """a solver's report on the keep_history games, from an engine that lives as long as the call; solve(solver, engine,
+    **the keyword arguments grade_games and grade_unroll share)"""
     from . import solver
     cfg = self.config
     t0 = time.perf_counter()
     opp = getattr(cfg, 'random_opp', None)
     eng = Engine.from_config(cfg, min(len(games), self.batch), device=self.device, seed=0)
     try:
-      report = solver.grade_games(games, cfg.environment, eng,
-                                  max_empties=None if cfg.environment == 'TicTacToe' else int(getattr(cfg, 'grade_empties', solver.DEFAULT_EMPTIES)),
-                                  graded_seat=None if opp is None else -int(opp),
-                                  max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)),
-                                  table=bool(getattr(cfg, 'grade_table', False)))
+      if weights:
+        eng.set_weights(self.weights)
+      report = solve(solver, eng,
+                     max_empties=None if cfg.environment == 'TicTacToe' else int(getattr(cfg, 'grade_empties', solver.DEFAULT_EMPTIES)),
+                     graded_seat=None if opp is None else -int(opp),
+                     max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)),
+                     table=bool(getattr(cfg, 'grade_table', False)))
     finally:
       eng.close()
     report['seconds'] = time.perf_counter() - t0
     return report
+
+  def grade(self, games):
+    """--grade: the keep_history games graded against the exact solver (solver.grade_games) -- the network's moves where
+    --random_opp seats an opponent, both sides' otherwise; TicTacToe every position, ConnectFour those with at most
+    config.grade_empties empty cells"""
+    return self._graded(games, lambda solver, eng, **kw: solver.grade_games(games, self.config.environment, eng, **kw))
 
   def grade_unroll(self, games):
     """--grade_unroll K: the model unrolled K steps along the moves of the same keep_history games, against the real
     positions and the exact solver (solver.grade_unroll), in --grade's scope: the positions where the network is to move
     where --random_opp seats an opponent, both seats' otherwise; truth for TicTacToe everywhere, for ConnectFour at
     positions with at most config.grade_empties empty cells"""
-    from . import solver
-    cfg = self.config
-    t0 = time.perf_counter()
-    opp = getattr(cfg, 'random_opp', None)
-    eng = Engine.from_config(cfg, min(len(games), self.batch), device=self.device, seed=0)
-    try:
-      eng.set_weights(self.weights)
-      report = solver.grade_unroll(games, cfg.environment, eng, int(cfg.grade_unroll),
-                                   max_empties=None if cfg.environment == 'TicTacToe' else int(getattr(cfg, 'grade_empties', solver.DEFAULT_EMPTIES)),
-                                   graded_seat=None if opp is None else -int(opp),
-                                   max_nodes=int(getattr(cfg, 'grade_nodes', solver.DEFAULT_NODES)),
-                                   table=bool(getattr(cfg, 'grade_table', False)))
-    finally:
-      eng.close()
-    report['seconds'] = time.perf_counter() - t0
-    return report
+    return self._graded(games, lambda solver, eng, **kw: solver.grade_unroll(games, self.config.environment, eng,
+                                                                             int(self.config.grade_unroll), **kw), weights=True)
 
-  def _play_batch_device(self, seeds, draws, start_states, keep_history, true_model=False, gumbel=None):
+  def _play_batch_device(self, seeds, draws, start_states, keep_history, side=None):
     """_play_batch with the games on the device environments: whole moves are enqueued MOVES_PER_SYNC at a time
     (Engine.eval_env_moves: observe, initial inference, root, search + walk or lookahead, finalize, apply), and the host
-    only reads the number of games still live after each chunk.  true_model: the engine searches the games' real positions
-    (Engine.set_true_model); gumbel: Engine.set_gumbel's arguments, the engine searches with the Gumbel search; everything
-    around the search is the same."""
+    only reads the number of games still live after each chunk.  side: the move rule (default: the config's); whichever
+    search it names, everything around the search is the same."""
     cfg = self.config
-    refuse_device_env(_with(cfg, device_env=True))
-    refuse_opp_playouts(_with(cfg, device_env=True))
+    side = side or Side.of(cfg)
+    refuse(cfg, device_env=True, side=side)
     opp_playouts = int(getattr(cfg, 'opp_playouts', 0) or 0)
     B, A = len(seeds), int(cfg.action_space)
-    only_prior, only_value = bool(getattr(cfg, 'only_prior', 0)), bool(getattr(cfg, 'only_value', 0))
-    mode = 1 if only_prior else 2 if only_value else 0
-    noise_on = bool(getattr(cfg, 'use_exploration_noise', 0))
     two = bool(cfg.two_players)
-    M = int(getattr(cfg, 'apply_mcts_actions', 1))
-    if M <= 0:
-      M = int(cfg.num_simulations) + 1
-    T = float(getattr(cfg, 'temperature', 0) or 0)
     t_batch = time.perf_counter()
     # the device RNG's key: (engine seed 0, env id = the game's seed, move, step)
     eng = Engine.from_config(cfg, B, device=self.device, seed=0, env_id_offset=seeds[0])
     eng.set_weights(self.weights)
-    if true_model:
-      eng.set_true_model(cfg.environment)
-    if gumbel:
-      eng.set_gumbel(True, **gumbel)
+    side.configure(eng, cfg.environment)
     eng.eval_env_reset(cfg.environment, int(cfg.max_steps), CARTPOLE_TIME_LIMITS.get(cfg.environment, 0),
                        getattr(cfg, 'random_opp', None) if two else None, keep_history)
     if opp_playouts:
       eng.eval_env_set_opponent(opp_playouts)
     if draws is not None or start_states is not None:
-      eng.eval_env_set_draws(**_pack_draws(draws, B, A, M, mode, noise_on, start_states))
+      eng.eval_env_set_draws(start_states=None if start_states is None else np.ascontiguousarray(start_states, np.float64).reshape(B, 4),
+                             **_pack_draws(draws, B, A, side.max_actions, 'opp', walk=side.mode == 0, noise=side.noise_on))
     live, moves, t_dev = B, 0, 0.0
     while live > 0 and moves < eng.eval_log_cap:      # (every move applies at least one action: at most cap moves)
       n = min(MOVES_PER_SYNC, eng.eval_log_cap - moves)
       t0 = time.perf_counter()
-      live = eng.eval_env_moves(n, mode, M, T, noise_on)
+      live = eng.eval_env_moves(n, side.mode, side.max_actions, side.temperature, side.noise_on)
       t_dev += time.perf_counter() - t0
       self.device_syncs += 1
       moves += n
@@ -456,19 +240,9 @@ class Evaluator(SummaryTools):
                      r['sum_root_value'][i] / nm, r['depth_mean'][i])
       g.seed = seeds[i]
       if keep_history:
-        n, k = g.step, int(r['n_moves'][i])
-        h = g.history = History()
-        h.actions = [int(x) for x in r['actions'][i, :n]]
-        h.rewards = [float(x) for x in r['rewards'][i, :n]]
-        h.to_play = [int(np.sign(x)) for x in r['mover'][i, :n]]
-        h.steps = list(range(n))
-        h.dones = [abs(int(x)) == 2 for x in r['mover'][i, :n]]      # (env.step's done: not the cut at max_steps)
-        h.child_visits = [[float(x) for x in row] for row in r['child_visits'][i, :k]]
-        h.root_values = [float(x) for x in r['root_values'][i, :k]]
-        g.pred_values = [float(x) for x in r['pred_values'][i, :k]]
-        g.pred_rewards = [float(x) for x in r['pred_rewards'][i, :n]]
+        k = int(r['n_moves'][i])
+        decode_history(g, r, i, range(k), [side] * k, range(g.step))
         g.n_actions = [int(x) for x in r['n_actions'][i, :k]]
-        g.search_depths = [[0] if only_prior else [1] if only_value else [int(x) for x in row] for row in r['depths'][i, :k]]
       if getattr(cfg, 'verbose', False):
         msg = "\033[92m[Game done]\033[0m --> "
         msg += "length: {:.1f}, return: {:.1f}, pred return: {:.1f}, pred value: {:.1f}, mcts value: {:.1f}"
@@ -478,18 +252,15 @@ class Evaluator(SummaryTools):
     self.host_seconds += time.perf_counter() - t_batch - t_dev
     return games
 
-  def _play_batch(self, envs, seeds, draws):
+  def _play_batch(self, envs, seeds, draws, side=None):
     cfg = self.config
+    side = side or Side.of(cfg)
     B, A = len(envs), int(cfg.action_space)
     O = int(np.prod(cfg.obs_space))
-    only_prior, only_value = bool(getattr(cfg, 'only_prior', 0)), bool(getattr(cfg, 'only_value', 0))
-    noise_on = bool(getattr(cfg, 'use_exploration_noise', 0))
+    only_prior, only_value, noise_on = side.mode == 1, side.mode == 2, side.noise_on
     two = bool(cfg.two_players)
     random_opp = getattr(cfg, 'random_opp', None)
-    M = int(getattr(cfg, 'apply_mcts_actions', 1))
-    if M <= 0:        # (the reference's loop then runs until an unexpanded node: at most num_simulations + 1 actions)
-      M = int(cfg.num_simulations) + 1
-    T = float(getattr(cfg, 'temperature', 0) or 0)
+    M, T = side.max_actions, side.temperature
     # the device RNG's key: (engine seed 0, env id = the game's seed, move, step)
     eng = Engine.from_config(cfg, B, device=self.device, seed=0, env_id_offset=seeds[0])
     eng.set_weights(self.weights)
@@ -600,34 +371,60 @@ def _with(cfg, **kv):
   return c
 
 
-def _pack_draws(draws, B, A, M, mode, noise_on, start_states):
-  """the per-game draw dicts of play_games as the dense arrays Engine.eval_env_set_draws uploads: walk [B][moves][M], noise
-  [B][moves][A], opp [B][n], each padded with zeros past a game's own draws"""
-  out = dict(start_states=None if start_states is None else np.ascontiguousarray(start_states, np.float64).reshape(B, 4))
+def consecutive_seeds(seeds, num_games, refusal):
+  """one seed per game as ints, consecutive (seed + i; ValueError(refusal) otherwise); None draws a base seed"""
+  if seeds is None:
+    base = int(np.random.randint(0, 2 ** 30))
+    seeds = range(base, base + num_games)
+  seeds = [int(s) for s in seeds]
+  if len(seeds) != num_games or any(s != seeds[0] + i for i, s in enumerate(seeds)):
+    raise ValueError(refusal)
+  return seeds
+
+
+def decode_history(g, r, i, searched, sides, predicted):
+  """the keep_history logs of game i (Engine.eval_env_results, Match.results) as g's per-move lists.  Over its g.step
+  actions history.actions / rewards / steps, and from the doubled `mover` log (+-1: who moved, +-2: and the rules ended the
+  game there -- not the cut at max_steps) history.to_play / dones.  Over `searched`, the log indices of the searched moves,
+  history.child_visits / root_values, pred_values and search_depths (sides: the Side that searched each); pred_rewards at
+  the indices `predicted`."""
+  n = g.step
+  h = g.history = History()
+  h.actions = [int(x) for x in r['actions'][i, :n]]
+  h.rewards = [float(x) for x in r['rewards'][i, :n]]
+  h.to_play = [int(np.sign(x)) for x in r['mover'][i, :n]]
+  h.steps = list(range(n))
+  h.dones = [abs(int(x)) == 2 for x in r['mover'][i, :n]]
+  h.child_visits = [[float(x) for x in r['child_visits'][i, p]] for p in searched]
+  h.root_values = [float(r['root_values'][i, p]) for p in searched]
+  g.pred_values = [float(r['pred_values'][i, p]) for p in searched]
+  g.pred_rewards = [float(r['pred_rewards'][i, p]) for p in predicted]
+  g.search_depths = [side.depths(r['depths'][i, p]) for p, side in zip(searched, sides)]
+
+
+def _pack_draws(draws, B, A, width, third, walk=True, noise=True):
+  """the per-game draw dicts of play_games / play_match as the dense arrays Engine.eval_env_set_draws / Match.set_draws
+  upload: walk [B][moves][width], noise [B][moves][A] and `third` ('opp' or 'opening') [B][n], each padded with zeros past a
+  game's own draws; walk / noise: whether the side reads them"""
+  out = {}
   if draws is None:
     return out
-  if mode == 0 and any('walk' in d for d in draws):
-    mv = max(1, max(len(d['walk']) for d in draws))
-    walk = np.zeros((B, mv, M), np.float64)
+  if walk and any('walk' in d for d in draws):
+    out['walk'] = np.zeros((B, max(1, max(len(d.get('walk', ())) for d in draws)), width), np.float64)
     for i, d in enumerate(draws):
-      for m, w in enumerate(d['walk']):
-        w = np.asarray(w, np.float64).reshape(-1)[:M]
-        walk[i, m, :len(w)] = w
-    out['walk'] = walk
-  if noise_on and any('noise' in d for d in draws):
-    mv = max(1, max(len(d['noise']) for d in draws))
-    noise = np.zeros((B, mv, A), np.float64)
+      for m, w in enumerate(d.get('walk', ())):
+        w = np.asarray(w, np.float64).reshape(-1)[:width]
+        out['walk'][i, m, :len(w)] = w
+  if noise and any('noise' in d for d in draws):
+    out['noise'] = np.zeros((B, max(1, max(len(d.get('noise', ())) for d in draws)), A), np.float64)
     for i, d in enumerate(draws):
-      for m, nz in enumerate(d['noise']):
-        noise[i, m] = np.asarray(nz, np.float64)
-    out['noise'] = noise
-  if any(len(d.get('opp', ())) for d in draws):
-    n = max(len(d.get('opp', ())) for d in draws)
-    opp = np.zeros((B, n), np.int32)
+      for m, nz in enumerate(d.get('noise', ())):
+        out['noise'][i, m] = np.asarray(nz, np.float64)
+  if any(len(d.get(third, ())) for d in draws):
+    out[third] = np.zeros((B, max(len(d.get(third, ())) for d in draws)), np.int32)
     for i, d in enumerate(draws):
-      o = np.asarray(d.get('opp', ()), np.int32).reshape(-1)
-      opp[i, :len(o)] = o
-    out['opp'] = opp
+      o = np.asarray(d.get(third, ()), np.int32).reshape(-1)
+      out[third][i, :len(o)] = o
   return out
 
 
@@ -636,70 +433,39 @@ def get_label(state, detailed=False, path_idx=None):
   if detailed:
     if path_idx is not None:
       label_parts.append('path:{}'.format(path_idx))
-    if state['config'].only_value:
-      label_parts.append('only value')
-    elif state['config'].only_prior:
-      label_parts.append('only prior')
-    else:
-      label_parts.append('sims:{}'.format(state['config'].num_simulations))
-      if state['config'].apply_mcts_actions > 1:
-        label_parts.append('mcts-actions:{}'.format(state['config'].apply_mcts_actions))
-      if state['config'].temperature:
-        label_parts.append('temp:{}'.format(state['config'].temperature))
-      if state['config'].use_exploration_noise:
-        label_parts.append('with noise')
-      if getattr(state['config'], 'true_model', 0):
-        label_parts.append('true rules')
-      if getattr(state['config'], 'gumbel', 0):
-        label_parts.append('gumbel')
+    label_parts += Side.of(state['config']).label_parts()
   return ', '.join(label_parts)
 
 
+# what state_generator copies from the command line into every state's config as it stands
+COPIED = ('render', 'save_mcts', 'save_mcts_after_step', 'save_gif_as', 'sleep', 'random_opp', 'human_opp', 'verbose', 'batch',
+          'device_env', 'keep_history', 'opp_playouts', 'grade', 'grade_empties', 'grade_nodes', 'grade_table', 'grade_unroll')
+
+
 def state_generator(args):
-  """evaluate.py:406-439: one state per (checkpoint, temperature, simulations, only_prior, only_value, noise, mcts actions),
-  only_prior together with only_value excluded"""
+  """evaluate.py:406-439: one state per (checkpoint, temperature, simulations, only_prior, only_value, noise, mcts actions,
+  true_model, gumbel), only_prior together with only_value excluded"""
+  lists = (args.temperatures, args.num_simulations, args.only_prior, args.only_value, args.use_exploration_noise,
+           args.apply_mcts_actions, getattr(args, 'true_model', [0]), getattr(args, 'gumbel', [0]))
   for path_idx, saves_dir in enumerate(args.saves_dir):
     for net in args.nets:
       meta_state = torch.load(saves_dir + net, map_location=torch.device('cpu'), weights_only=False)
-      for temperature in args.temperatures:
-        for num_simulations in args.num_simulations:
-          for only_prior in args.only_prior:
-            for only_value in args.only_value:
-              for use_exploration_noise in args.use_exploration_noise:
-                for apply_mcts_actions, true_model, gumbel in ((m, t, g) for m in args.apply_mcts_actions for t in getattr(args, 'true_model', [0])
-                                                               for g in getattr(args, 'gumbel', [0])):
-                  if not (only_prior and only_value):
-                    state = copy.deepcopy(meta_state)
-                    c = state['config']
-                    c.saves_dir = saves_dir
-                    if num_simulations is not None:
-                      c.num_simulations = num_simulations
-                    c.temperature = temperature
-                    c.only_value = only_value
-                    c.only_prior = only_prior
-                    c.use_exploration_noise = use_exploration_noise
-                    c.apply_mcts_actions = apply_mcts_actions
-                    c.true_model = int(true_model)
-                    c.gumbel = int(gumbel)
-                    c.gumbel_considered, c.gumbel_c_visit, c.gumbel_c_scale, c.gumbel_scale = gumbel_params(args)
-                    c.render = args.render
-                    c.save_mcts = args.save_mcts
-                    c.save_mcts_after_step = args.save_mcts_after_step
-                    c.save_gif_as = args.save_gif_as
-                    c.sleep = args.sleep
-                    c.random_opp = args.random_opp
-                    c.human_opp = args.human_opp
-                    c.label = get_label(state, args.detailed_label, path_idx)
-                    c.use_gpu = True
-                    c.verbose = args.verbose
-                    c.batch = args.batch
-                    c.device_env = args.device_env
-                    c.keep_history = args.keep_history
-                    c.opp_playouts = args.opp_playouts
-                    c.grade, c.grade_empties, c.grade_nodes = args.grade, args.grade_empties, args.grade_nodes
-                    c.grade_table = args.grade_table
-                    c.grade_unroll = args.grade_unroll
-                    yield state
+      for temperature, num_simulations, only_prior, only_value, noise, apply_mcts_actions, true_model, gumbel in itertools.product(*lists):
+        if only_prior and only_value:
+          continue
+        state = copy.deepcopy(meta_state)
+        c = state['config']
+        c.saves_dir = saves_dir
+        if num_simulations is not None:
+          c.num_simulations = num_simulations
+        c.temperature, c.only_prior, c.only_value, c.use_exploration_noise = temperature, only_prior, only_value, noise
+        c.apply_mcts_actions, c.true_model, c.gumbel = apply_mcts_actions, int(true_model), int(gumbel)
+        c.gumbel_considered, c.gumbel_c_visit, c.gumbel_c_scale, c.gumbel_scale = gumbel_params(args)
+        for name in COPIED:
+          setattr(c, name, getattr(args, name))
+        c.label = get_label(state, args.detailed_label, path_idx)
+        c.use_gpu = True
+        yield state
 
 
 def run(evaluator, seed=None):
@@ -710,16 +476,10 @@ def run(evaluator, seed=None):
 
 def main(argv=None):
   args = get_evaluation_args(argv)
-  refuse_opp_playouts(args, match=args.match)
-  refuse_grade(args, match=args.match)
-  refuse_grade_unroll(args)
-  refuse_true_model(args, match=args.match)
-  refuse_gumbel(args, match=args.match)
   if args.match:      # checkpoint against checkpoint (match.py); implies the device path
     from . import match
     return match.main(args)
-  refuse_unsupported(args)
-  refuse_device_env(args)
+  refuse(args)
   evaluators = [Evaluator(state) for state in state_generator(args)]
   print("\n\033[92mStarting a {} episode evaluation of {} configurations\033[0m...".format(args.num_games, len(evaluators)))
   seeds = list(range(args.seed, args.num_games + args.seed)) if args.seed is not None else None
@@ -733,14 +493,13 @@ def main(argv=None):
     s = evaluator.print_summary(games)
     s['label'] = evaluator.config.label
     s['num_games'] = len(games)
-    s['true_model'] = int(getattr(evaluator.config, 'true_model', 0))
+    side = Side.of(evaluator.config)
+    s['true_model'], s['gumbel'] = int(side.true_model), int(bool(side.gumbel))
+    if side.gumbel:
+      s['gumbel_params'] = dict(side.gumbel)
     if args.device_env:
-      print("Search below the root: {}\n".format('the true rules of the game (--true_model)' if s['true_model'] else 'the learned model'))
-    s['gumbel'] = int(getattr(evaluator.config, 'gumbel', 0))
-    if s['gumbel']:
-      s['gumbel_params'] = dict(zip(('max_considered', 'c_visit', 'c_scale', 'gumbel_scale'), gumbel_params(evaluator.config)))
-    if args.device_env:
-      print(gumbel_line(evaluator.config) + "\n")
+      print("Search below the root: {}\n".format('the true rules of the game (--true_model)' if side.true_model else 'the learned model'))
+      print(side.search_line() + "\n")
     if evaluator.config.two_players and args.random_opp is not None:
       returns = np.array([game_return(g) for g in games])
       s['wins'], s['draws'], s['losses'] = int((returns > 0).sum()), int((returns == 0).sum()), int((returns < 0).sum())

@@ -23,46 +23,11 @@ import numpy as np
 import torch
 
 from .engine import Engine, Match, flatten_weights
-from .envs import BOARD_ENVS as MATCH_ENVS
-from .game import History
+from .evaluate import _pack_draws, consecutive_seeds, decode_history
+from .sides import MATCH_ENVS, Side, gumbel_params, per_side, refuse, refuse_match      # noqa: F401  (refuse_match: importable from here)
 
 MAX_BATCH = 4096
 PLIES_PER_SYNC = 8      # whole plies enqueued per host synchronisation (evaluate.MOVES_PER_SYNC)
-
-
-def _all(x):
-  return list(x) if isinstance(x, (list, tuple)) else [x]
-
-
-def refuse_match(args_or_config, other=None):
-  """one sentence per configuration --match leaves out (NotImplementedError, starting '--match: '); other: the second
-  checkpoint's config, for what the two must share.  Host arithmetic only: no device is touched."""
-  c = args_or_config
-  env = getattr(c, 'environment', None)
-  if env is not None and env not in MATCH_ENVS:
-    raise NotImplementedError('--match: the environment %s is not a two-player device game; matches are played on %s.'
-                              % (env, ' and '.join(MATCH_ENVS)))
-  if any(int(x) != 1 for x in _all(getattr(c, 'apply_mcts_actions', 1))):
-    raise NotImplementedError('--match: --apply_mcts_actions must be 1; a ply of a match applies exactly one action.')
-  if getattr(c, 'norm_obs', False):
-    raise NotImplementedError('--match: --norm_obs is not applied by the device games.')
-  if getattr(c, 'random_opp', None):
-    raise NotImplementedError('--match: --random_opp has no place in a match; both sides are networks (give --nets two names).')
-  if getattr(c, 'human_opp', None):
-    raise NotImplementedError('--match: --human_opp is an interactive tool; both sides of a match are networks.')
-  if getattr(c, 'architecture', 'FCNetwork') != 'FCNetwork':
-    raise NotImplementedError('--match: the architecture %s has no device match path; FCNetwork checkpoints only.' % c.architecture)
-  if other is not None:
-    refuse_match(other)
-    if getattr(c, 'environment', None) != getattr(other, 'environment', None):
-      raise NotImplementedError('--match: the two checkpoints play a different environment (%s and %s).'
-                                % (getattr(c, 'environment', None), getattr(other, 'environment', None)))
-    if bool(getattr(c, 'no_support', False)) != bool(getattr(other, 'no_support', False)):
-      raise NotImplementedError('--match: the two checkpoints differ in no_support; their value heads are not comparable.')
-    for key in ('value_support', 'reward_support'):
-      if tuple(getattr(c, key, (-15, 15))) != tuple(getattr(other, key, (-15, 15))):
-        raise NotImplementedError('--match: the two checkpoints have different supports (%s %s and %s).'
-                                  % (key, tuple(getattr(c, key, (-15, 15))), tuple(getattr(other, key, (-15, 15)))))
 
 
 def elo_difference(score):
@@ -109,39 +74,12 @@ def summarize(games):
 
 
 def _side(cfg):
-  only_prior, only_value = bool(getattr(cfg, 'only_prior', 0)), bool(getattr(cfg, 'only_value', 0))
-  if only_prior and only_value:
-    raise ValueError('only_prior and only_value exclude each other')
-  return (1 if only_prior else 2 if only_value else 0, float(getattr(cfg, 'temperature', 0) or 0),
-          bool(getattr(cfg, 'use_exploration_noise', 0)))
+  """(mode, temperature, noise_on) of a config's Side"""
+  return Side.of(cfg).plies_args
 
 
-def _pack_draws(draws, B, A):
-  """the per-game draw dicts as the dense arrays Match.set_draws uploads, padded with zeros past a game's own draws"""
-  out = {}
-  if any('walk' in d for d in draws):
-    n = max(1, max(len(d.get('walk', ())) for d in draws))
-    out['walk'] = np.zeros((B, n), np.float64)
-    for i, d in enumerate(draws):
-      w = np.asarray([np.asarray(x, np.float64).reshape(-1)[0] for x in d.get('walk', ())], np.float64)
-      out['walk'][i, :len(w)] = w
-  if any('noise' in d for d in draws):
-    n = max(1, max(len(d.get('noise', ())) for d in draws))
-    out['noise'] = np.zeros((B, n, A), np.float64)
-    for i, d in enumerate(draws):
-      for p, nz in enumerate(d.get('noise', ())):
-        out['noise'][i, p] = np.asarray(nz, np.float64)
-  if any(len(d.get('opening', ())) for d in draws):
-    n = max(len(d.get('opening', ())) for d in draws)
-    out['opening'] = np.zeros((B, n), np.int32)
-    for i, d in enumerate(draws):
-      o = np.asarray(d.get('opening', ()), np.int32).reshape(-1)
-      out['opening'][i, :len(o)] = o
-  return out
-
-
-def _records(r, seeds, seating, opening, sides, sims, keep_history):
-  """Match.results() of one seating as MatchGame records"""
+def _records(r, seeds, seating, opening, sides, keep_history):
+  """Match.results() of one seating as MatchGame records; sides: the two nets' Sides"""
   colour_a = 1 if (seating == 0) == (opening % 2 == 0) else -1      # the player net A is: +1 moves first
   games = []
   for i, seed in enumerate(seeds):
@@ -153,23 +91,10 @@ def _records(r, seeds, seating, opening, sides, sims, keep_history):
     g.mcts_value = tuple(float(r['sum_root_value'][k, i]) / nm[k] for k in (0, 1))
     g.search_depth = tuple(float(r['depth_mean'][k, i]) for k in (0, 1))
     if keep_history:
-      n = g.step
-      h = g.history = History()
-      h.actions = [int(x) for x in r['actions'][i, :n]]
-      h.rewards = [float(x) for x in r['rewards'][i, :n]]
-      h.to_play = [int(np.sign(x)) for x in r['mover'][i, :n]]
-      h.steps = list(range(n))
-      h.dones = [abs(int(x)) == 2 for x in r['mover'][i, :n]]      # (the rules' done: not the cut at max_steps)
-      g.nets = [int(x) for x in r['net'][i, :n]]
-      ply = [p for p in range(n) if g.nets[p] >= 0]
-      g.searched_plies = ply
-      g.searched_by = [g.nets[p] for p in ply]
-      h.child_visits = [[float(x) for x in r['child_visits'][i, p]] for p in ply]
-      h.root_values = [float(r['root_values'][i, p]) for p in ply]
-      g.pred_values = [float(r['pred_values'][i, p]) for p in ply]
-      g.pred_rewards = [float(r['pred_rewards'][i, p]) for p in ply]
-      g.search_depths = [[0] if sides[g.nets[p]][0] == 1 else [1] if sides[g.nets[p]][0] == 2 else
-                         [int(x) for x in r['depths'][i, p, :sims[g.nets[p]]]] for p in ply]
+      g.nets = [int(x) for x in r['net'][i, :g.step]]
+      g.searched_plies = [p for p in range(g.step) if g.nets[p] >= 0]
+      g.searched_by = [g.nets[p] for p in g.searched_plies]
+      decode_history(g, r, i, g.searched_plies, [sides[k] for k in g.searched_by], g.searched_plies)
     games.append(g)
   return games
 
@@ -186,99 +111,58 @@ def play_match(state_a, state_b, num_games, seeds=None, opening_plies=0, draws=N
   searches with the Gumbel search instead of PUCT (Engine.gz_search; evaluate --gumbel) -- a true value takes the parameters
   of that side's config (gumbel_considered, gumbel_c_visit, gumbel_c_scale, gumbel_scale; their defaults where it has none), a
   dict gives Engine.set_gumbel's arguments; None: each state's config.gumbel."""
-  from .evaluate import gumbel_params, refuse_gumbel, refuse_true_model
   ca, cb = state_a['config'], state_b['config']
-  refuse_match(ca, cb)
-  if true_model is None:
-    true_model = (getattr(ca, 'true_model', 0), getattr(cb, 'true_model', 0))
-  true_model = tuple(int(bool(x)) for x in true_model)
-  if len(true_model) != 2:
-    raise ValueError('play_match: true_model takes one value per side, got %r' % (true_model,))
-  for c, t in zip((ca, cb), true_model):
-    refuse_true_model(_with_true_model(c, t), match=True)
-  if gumbel is None:
-    gumbel = (getattr(ca, 'gumbel', 0), getattr(cb, 'gumbel', 0))
-  if len(gumbel) != 2:
-    raise ValueError('play_match: gumbel takes one value per side, got %r' % (gumbel,))
-  gz = []
-  for c, t, g in zip((ca, cb), true_model, gumbel):
-    if not g:
-      gz.append(None)
-      continue
-    m, cv, cs, sc = gumbel_params(c)
-    kw = dict(dict(max_considered=m, c_visit=cv, c_scale=cs, gumbel_scale=sc), **(g if isinstance(g, dict) else {}))
-    c1 = _with_true_model(c, t)
-    c1.gumbel, c1.gumbel_considered, c1.gumbel_c_visit, c1.gumbel_c_scale, c1.gumbel_scale = (
-        1, kw['max_considered'], kw['c_visit'], kw['c_scale'], kw['gumbel_scale'])
-    refuse_gumbel(c1, match=True)
-    gz.append(kw)
+  for name, given in (('true_model', true_model), ('gumbel', gumbel)):
+    if given is not None and len(given) != 2:
+      raise ValueError('play_match: %s takes one value per side, got %r' % (name, tuple(given)))
+  sides = tuple(Side.of(c, None if true_model is None else bool(true_model[k]), None if gumbel is None else gumbel[k] or False)
+                for k, c in enumerate((ca, cb)))
+  refuse(ca, match=True, side=sides[0], other=cb)
+  refuse(cb, match=True, side=sides[1])
   if not torch.cuda.is_available():
     raise RuntimeError('a match needs a HIP device (torch.cuda.is_available() is False); there is no CPU path.')
   device = torch.device(device if device is not None else 'cuda')
-  sides = (_side(ca), _side(cb))
-  sims = (int(ca.num_simulations), int(cb.num_simulations))
   max_steps = min(int(ca.max_steps), int(cb.max_steps))
   opening_plies = int(opening_plies)
   if not 0 <= opening_plies < max_steps:
     raise ValueError('play_match: opening_plies %d outside [0, max_steps = %d)' % (opening_plies, max_steps))
   batch = int(batch or getattr(ca, 'batch', None) or MAX_BATCH)
-  if seeds is None:
-    base = int(np.random.randint(0, 2 ** 30))
-    seeds = list(range(base, base + num_games))
-  seeds = [int(s) for s in seeds]
-  if len(seeds) != num_games or any(s != seeds[0] + i for i, s in enumerate(seeds)):
-    raise ValueError('play_match takes consecutive seeds, one per game')
+  seeds = consecutive_seeds(seeds, num_games, 'play_match takes consecutive seeds, one per game')
   weights = [flatten_weights(s['weights']) for s in (state_a, state_b)]
-  A = int(ca.action_space)
+  A, rules = int(ca.action_space), [side.plies_args for side in sides]
   games, t_dev, syncs, plies = [], 0.0, 0, 0
   for lo in range(0, num_games, batch):
     sd = seeds[lo:lo + batch]
     B = len(sd)
     # the device RNG's key: (engine seed 0, env id = the game's seed, ply, step)
     engines = [Engine.from_config(c, B, device=device, seed=0, env_id_offset=sd[0]) for c in (ca, cb)]
-    for e, w, t, g in zip(engines, weights, true_model, gz):
+    for e, w, side in zip(engines, weights, sides):
       e.set_weights(w)
-      if t:
-        e.set_true_model(ca.environment)
-      if g:
-        e.set_gumbel(True, **g)
+      side.configure(e, ca.environment)
     match = Match(engines[0], engines[1], ca.environment, max_steps, keep_history)
-    packed = None if draws is None else _pack_draws(draws[lo:lo + batch], B, A)
+    packed = None if draws is None else _pack_draws(draws[lo:lo + batch], B, A, 1, 'opening')
     for seating in (0, 1):
       match.reset(first_net=seating, opening_plies=opening_plies)
       if packed:
         match.set_draws(**packed)
       live, done = B, opening_plies
       t0 = time.perf_counter()
-      live = match.plies(0, *zip(*sides))      # (the opening alone may end games)
+      live = match.plies(0, *zip(*rules))      # (the opening alone may end games)
       while live > 0 and done < match.log_cap:      # (every ply applies one action: at most cap plies)
         n = min(PLIES_PER_SYNC, match.log_cap - done)
-        live = match.plies(n, *zip(*sides))
+        live = match.plies(n, *zip(*rules))
         syncs += 1
         done += n
       t_dev += time.perf_counter() - t0
       r = match.results()
       plies += int(r['length'].sum())
-      games += _records(r, sd, seating, opening_plies, sides, sims, keep_history)
+      games += _records(r, sd, seating, opening_plies, sides, keep_history)
     match.close()
     for e in engines:
       e.close()
   if stats is not None:
     stats.update(plies=plies, device_seconds=t_dev, syncs=syncs)
-  return games, dict(summarize(games), true_model=list(true_model), gumbel=[int(bool(g)) for g in gz])
-
-
-def _with_true_model(cfg, t):
-  c = copy.copy(cfg)
-  c.true_model = int(t)
-  return c
-
-
-def _pick(values, side):
-  values = _all(values)
-  if len(values) not in (1, 2):
-    raise ValueError('--match takes per-side lists of length one (both sides) or two, got %r' % (values,))
-  return values[side if len(values) == 2 else 0]
+  return games, dict(summarize(games), true_model=[int(x.true_model) for x in sides], gumbel=[int(bool(x.gumbel)) for x in sides])
 
 
 def match_states(args):
@@ -300,19 +184,20 @@ def match_states(args):
   return out
 
 
+# (a side's config attribute, the command-line list it is picked from, its type)
+PER_SIDE = (('temperature', 'temperatures', float), ('only_prior', 'only_prior', int), ('only_value', 'only_value', int),
+            ('use_exploration_noise', 'use_exploration_noise', int), ('true_model', 'true_model', int), ('gumbel', 'gumbel', int))
+
+
 def side_state(state, args, side):
   """a checkpoint's state with side `side`'s settings of the command line in its config"""
-  from .evaluate import gumbel_params
   state = dict(state, config=copy.copy(state['config']))
   c = state['config']
-  ns = _pick(args.num_simulations, side)
+  ns = per_side(args.num_simulations, side, strict=True)
   if ns is not None:
     c.num_simulations = int(ns)
-  c.temperature = float(_pick(args.temperatures, side))
-  c.only_prior, c.only_value = int(_pick(args.only_prior, side)), int(_pick(args.only_value, side))
-  c.use_exploration_noise = int(_pick(args.use_exploration_noise, side))
-  c.true_model = int(_pick(getattr(args, 'true_model', [0]), side))
-  c.gumbel = int(_pick(getattr(args, 'gumbel', [0]), side))
+  for name, flag, kind in PER_SIDE:
+    setattr(c, name, kind(per_side(getattr(args, flag, [0]), side, strict=True)))
   c.gumbel_considered, c.gumbel_c_visit, c.gumbel_c_scale, c.gumbel_scale = gumbel_params(args)
   c.apply_mcts_actions = 1
   c.random_opp = c.human_opp = None
@@ -321,18 +206,12 @@ def side_state(state, args, side):
 
 
 def _side_label(label, cfg):
-  mode = 'only prior' if cfg.only_prior else 'only value' if cfg.only_value else 'sims:%d' % cfg.num_simulations
-  return '%s, %s%s%s%s%s' % (label, mode, ', temp:%g' % cfg.temperature if cfg.temperature else '',
-                             ', with noise' if cfg.use_exploration_noise else '',
-                             ', true rules' if getattr(cfg, 'true_model', 0) else '',
-                             ', gumbel' if getattr(cfg, 'gumbel', 0) else '')
+  return ', '.join([label] + Side.of(cfg).label_parts('temp:{:g}', lookahead_alone=False))
 
 
 def main(args):
   """evaluate --match: every pair of --nets (round robin when more than two), the score table printed and written"""
-  from .evaluate import gumbel_line, gumbel_params, refuse_unsupported
-  refuse_match(args)
-  refuse_unsupported(args)
+  refuse(args, match=True)
   states = match_states(args)
   for _, s in states:
     refuse_match(s['config'], states[0][1]['config'])
@@ -346,7 +225,7 @@ def main(args):
       sa, sb = side_state(states[i][1], args, 0), side_state(states[j][1], args, 1)
       la, lb = _side_label(labels[i], sa['config']), _side_label(labels[j], sb['config'])
       print("\n\033[92mMatch\033[0m ({}) against ({}): {} seeds, both seatings".format(la, lb, args.num_games))
-      print("  A {}; B {}".format(gumbel_line(sa['config']), gumbel_line(sb['config'])))
+      print("  A {}; B {}".format(Side.of(sa['config']).search_line(), Side.of(sb['config']).search_line()))
       stats = {}
       t0 = time.perf_counter()
       games, s = play_match(sa, sb, args.num_games, seeds, opening_plies=args.opening_plies, batch=args.batch, stats=stats)
