@@ -77,6 +77,22 @@ int mz_fcl_read_grad(mz_fcl *c, float *host_out, size_t n);
  * losses; [position][row / 16][feature][16 rows] each, heads [head][position]...); host_out null: returns the float count. */
 long long mz_fcl_read_tape(mz_fcl *c, int which, float *host_out, size_t n);
 
+/* test hooks: the plan of a learner step (csrc/mz_fcl_plan.inc) as integers.  the host variant: no handle, no device -- the plan of the
+ * handle that create would make for this shape (value_bins / reward_bins: the supports' sizes) on a device of `cus` compute units under
+ * the knobs knobs5 [host] = what the variables MZ_FCL_GROUPS, MZ_FCL_SLABS (their integer), MZ_FCL_FUSE_FWD, MZ_FCL_FUSE_FB,
+ * MZ_FCL_FB_JOBS (1 where the value starts with '1', else 0) say, -1 each where not set (null: none set); it refuses what create
+ * refuses, with its words.  The other: the plan of a created handle.
+ * out [host][MZ_FCL_PLAN_FIELDS] = G, S, nwg, nln, fuse_fwd, fuse_fb, fb_jobs, KP, lds_bytes, lds_bwd_dw, njobs, njobs_heads,
+ * stage_bytes, forward form (0 one launch with the backward chain, 1 one launch, 2 chain + heads), backward form (0 in the forward's
+ * launch, 1 beside the heads' jobs, 2 row slabs), the LDS bytes of the last launch, cus, the tapes' floats, whether buffer descriptors
+ * reach all of them, arrival counters.
+ * names [host] (may be null): the kernels a step of that plan can launch under optimiser opt_kind (0 Adam, 1 SGD, 2 RMSprop; + 4 with a
+ * momentum buffer) and loss form scalar_loss (0 categorical, else scalar), with their template arguments, one per line. */
+#define MZ_FCL_PLAN_FIELDS 20
+int mz_fcl_plan_host(int batch, int unroll_steps, int obs_dim, int action_space, int value_bins, int reward_bins, int cus, const int *knobs5,
+                     int opt_kind, int scalar_loss, long long *out, char *names, size_t names_cap);
+int mz_fcl_plan(mz_fcl *c, int opt_kind, int scalar_loss, long long *out, char *names, size_t names_cap);
+
 /* development hook: s_memtime stamps (shader clock) at the phase boundaries of k_fcl_heads, workgroup 0 of every head at unroll
  * position 1 (3 x 16 slots), and of k_fcl_chain_fwd4's position 2 (slots 48..53); slots 12..15, 28..31, 44..47, 59..66: the two-launch
  * step's timeline on the constant 100 MHz clock (chain workgroup 0's passes, its last two positions' value units, the last unit / job /

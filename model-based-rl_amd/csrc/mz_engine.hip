@@ -30,6 +30,7 @@
 #include "mz_fused_h2.hip.h"
 #include "mz_learner.hip.h"
 #include "mz_fcl.hip.h"
+#include "mz_fcl_plan.inc"
 #include "mz_eval.hip.h"
 #include "mz_eval_env.hip.h"
 #include "mz_match.hip.h"

@@ -38,9 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define FCL_NW 8                    // waves per workgroup of the chain and heads kernels
-#define FCL_THREADS (FCL_NW * 64)
-#define FCL_MAXP 8                  // unroll positions K + 1
+#include "mz_fcl_sizes.h"           // FCL_NW, FCL_THREADS, FCL_MAXP and the launches' LDS sizes: shared with the host's plan
 #define FCL_LN_EPS 1e-5f
 
 struct FclPack {          // float offsets into the packed buffer
@@ -173,9 +171,7 @@ __device__ __forceinline__ void fcl_reduce(const f32x4 *red, int nt, const float
   }
 }
 
-// LDS of the heads kernel (floats): X [1024] | A1 [8192] | red [8192] | Y [1024] | S [1024] | PV [576] (PV: the small
-// parameter vectors, read once per launch): two workgroups per CU
-#define FCL_LDS_HEADS (1024 + 8192 + 8192 + 1024 + 1024 + 576)
+// LDS of the heads kernel: FCL_LDS_HEADS floats (mz_fcl_sizes.h)
 
 // Config.scalar_transform + scalar_to_support (config.py:51-68): bin s of the two-hot target of scalar x
 struct FclTwoHot { int lo_i, hi_i; float p_hi; };
@@ -603,9 +599,7 @@ __device__ __forceinline__ f32x4 fcl_quad_stream(const float *__restrict__ pk, i
   return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
 
-// LDS of the chain kernels (floats), G groups of 4 samples, activations SAMPLE-major: X [4 G][xq + 4] | A1 [4 G][516] | red [G][2048] | misc [16] | PV [1408] | S [4 G][64]
-#define FCL_LDS4_FLOATS(xq, G) (4 * (G) * ((xq) + 4) + 4 * (G) * 516 + (G) * 2048 + 16 + 1408 + 256 * (G))
-#define FCL_LDA 516
+// LDS of the chain kernels: FCL_LDS4_FLOATS(xq, G) floats, rows of FCL_LDA (mz_fcl_sizes.h)
 
 // Split-K partials of a 64-row x 4-sample product in LDS: a wave's 64 lanes (b, j) = (lane >> 2, lane & 3) each leave one f32x4 (rows
 // 4 b + i of sample j); the reducing wave reads them as lane (j, b) = (lane >> 4, lane & 15).  Slot of (j, b) among the wave's 64
@@ -1198,8 +1192,7 @@ __device__ __forceinline__ void fcl_bias_corr(const FclDw &a, float *dst) {
 // work = one row chunk of one position: NA + NI loads of 16 bytes per lane feed 4 NA NI MFMAs.  Small batches want MANY small
 // jobs (a job lives on one CU: its MFMAs bound its duration) -- NA = 1, NI = 2 or 4; large batches want few loads per MFMA (the
 // kernel is bound by the tapes' way through L2: 16 x 64 strips re-read the input tape once per 16 rows of dW) -- NA up to 4.
-#define FCL_DW_Q(NA, NI) ((NA) * (4 * (NI) + 1))                                   // floats per lane a wave leaves in LDS
-#define FCL_DW_LDS(NW, NA, NI) (((NW) * FCL_DW_Q(NA, NI) * 64 + 4) * 4)            // bytes: the waves' partial tiles + the two bias corrections
+// (FCL_DW_Q, FCL_DW_LDS: mz_fcl_sizes.h)
 
 // WT: a job of k_fcl_fb -- its tapes were written (through) by heads units and chain workgroups of the SAME launch: the job has its
 // optimiser operands requested, then one lane waits for the head's counter of finished units (`wait_flag` >= `wait_for`), a barrier, and
