@@ -3,6 +3,7 @@
 // every entry point launches HIP kernels on the stream it is given.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -25,6 +26,7 @@
 #include "mz_rng.h"
 #include "mz_tree.hip.h"
 #include "mz_selfplay.hip.h"
+#include "mz_selfplay_ring.inc"   // MZ_GRAPH_MOVES, RecordRing
 #include "mz_fused.hip.h"
 #include "mz_root.hip.h"
 #include "mz_fused_h2.hip.h"
@@ -99,8 +101,6 @@ static int fail(const char *fmt, ...) {
     if (err_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(err_), __FILE__, __LINE__); \
   } while (0)
 
-#define MZ_GRAPH_MOVES 16    // most self-play moves captured into one hipGraph (3 kernel nodes per move)
-
 // offsets of the 22 tensors inside the flat weight vector (flat_layout below)
 struct FlatLayout {
   size_t rep_w1, rep_b1, rep_w2, rep_b2, val_w1, val_b1, val_w2, val_b2, pol_w1, pol_b1, pol_w2, pol_b2, rew_w1,
@@ -140,17 +140,9 @@ struct mz_engine {
   bool use_lds_hybrid = true;
   std::vector<const void *> lds_attr_done;   // kernels whose hipFuncAttributeMaxDynamicSharedMemorySize is set (per device: once per engine)
   bool use_persist = true;          // self-play loop: whole moves inside ONE launch of the search kernel (its HEAD instantiation)
-  // record drain on a copy stream (mz_selfplay_drain): event behind the last copy, and how far the compute stream
-  // has been ordered behind the copies
-  hipEvent_t drain_ev = nullptr;    // the LATEST drain's copy (chains drains issued on different streams)
-  hipStream_t drain_stream = nullptr;
-  bool drain_pending = false;
-  // every drain whose copy may still be reading the ring: (first move not covered = sp.drained after it, its event),
-  // oldest first; events come from / go back to drain_ev_pool (mz_selfplay_steps waits for the OLDEST drain that still
-  // covers the slots it is about to overwrite, not for the latest one)
-  std::deque<std::pair<unsigned long long, hipEvent_t>> drain_q;
-  std::vector<hipEvent_t> drain_ev_pool;
-  unsigned long long drain_q_start = 0;     // first move covered by drain_q.front()
+  // the experience ring's counters and the drains that read it (mz_selfplay_ring.inc; its tokens are hipEvent_t).  Of sp the
+  // kernels read ring, ring_moves and rec_floats; sp.moves_host, sp.drained and sp.host_ring are unused (the layout stays)
+  RecordRing ring;
   double prof_spread[3] = {0, 0, 0};   // mean / min / max over workgroups of the last phase profile's total cycles
   bool split_f16 = false;           // FCNetwork GEMMs as float16 high/low splits (mz_fused_h2.hip.h)
   int32_t *pack_idx_h2 = nullptr;   // gather table of the split-f16 weight stream (bit 30: low part)
@@ -240,6 +232,12 @@ __global__ __launch_bounds__(256) void k_affine_relu(float4 *__restrict__ y, con
 // kernel's weight stream could be scaled for its clamp ReLU (mz_set_weights; the split-f16 kernel has its own stream)
 static inline bool fused_usable(const mz_engine *e) {
   return e->use_fused && e->sims + 2 <= MZ_FUSED_MAXPL && (e->split_f16 || e->stream_scaled || !e->weights_set);
+}
+
+// captured graphs hold kernel arguments and the launches of one kernel set: whatever changes either drops them
+static void drop_graphs(mz_engine *e, bool also_search) {
+  if (also_search && e->search_graph) { hipGraphExecDestroy(e->search_graph); e->search_graph = nullptr; }
+  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
 }
 
 template <typename T>
@@ -1036,10 +1034,9 @@ int mz_destroy(mz_engine *e) {
   if (!e) return 0;
   hipSetDevice(e->device);
   hipDeviceSynchronize();
-  for (auto &q : e->drain_q) hipEventDestroy(q.second);
-  for (hipEvent_t ev : e->drain_ev_pool) hipEventDestroy(ev);
-  if (e->search_graph) hipGraphExecDestroy(e->search_graph);
-  for (auto &g : e->move_graph) if (g) hipGraphExecDestroy(g);
+  e->ring.forget(0);
+  for (void *ev : e->ring.pool) hipEventDestroy((hipEvent_t)ev);
+  drop_graphs(e, true);
   if (e->cap_stream) hipStreamDestroy(e->cap_stream);
   for (void *p : e->allocs) hipFree(p);
   for (int w = 0; w < 2; ++w) {
@@ -1145,10 +1142,7 @@ int mz_set_weights(mz_engine *e, const float *flat, size_t n, int on_device, voi
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(s));     // (also: a host buffer may be freed by the caller)
   const bool scaled = e->relu_scale_host[3] != 0.f;
-  if (scaled != e->stream_scaled) {      // captured graphs hold the launches of the other kernel set
-    if (e->search_graph) { hipGraphExecDestroy(e->search_graph); e->search_graph = nullptr; }
-    for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
-  }
+  if (scaled != e->stream_scaled) drop_graphs(e, true);      // captured graphs hold the launches of the other kernel set
   e->stream_scaled = scaled;
   e->scale_host_valid = true;
   e->weights_set = true;
@@ -1231,8 +1225,7 @@ int mz_set_weights_async(mz_engine *e, const float *flat, size_t n, int on_devic
   const bool scaled = scale_ok != 0;
   if (scaled != e->stream_scaled) {      // (rare: captured graphs hold the launches of the other kernel set)
     HIPCHECK(hipStreamSynchronize(s));
-    if (e->search_graph) { hipGraphExecDestroy(e->search_graph); e->search_graph = nullptr; }
-    for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+    drop_graphs(e, true);
   }
   e->stream_scaled = scaled;
   e->scale_host_valid = false;

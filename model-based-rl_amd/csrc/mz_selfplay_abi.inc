@@ -17,11 +17,7 @@ static int selfplay_alloc(mz_engine *e) {
   DM(sp.child_visits, nb * e->A) DM(sp.root_value, nb) DM(sp.error, nb) DM(sp.movecnt, nb)
   sp.obs_slots = sp.obs_u8 == 2 ? (e->O + 3) / 4 : e->O;
   sp.rec_floats = e->O + e->A + MZ_REC_EXTRA;      // (the ring is sized for unpacked observations; set_obs may shrink the record)
-  size_t per_move = (size_t)e->B * sp.rec_floats * sizeof(float);
-  size_t moves = ((size_t)128 << 20) / per_move;
-  // at least two graph launches' worth of moves, so that a drain on a copy stream and the next chunk's moves use
-  // different slots (where they cannot, mz_selfplay_steps orders itself behind the drain's event)
-  sp.ring_moves = (int)(moves < 2 * MZ_GRAPH_MOVES ? 2 * MZ_GRAPH_MOVES : (moves > 256 ? 256 : moves));
+  sp.ring_moves = e->ring.capacity = RecordRing::capacity_for((size_t)e->B * sp.rec_floats * sizeof(float));
   DM(sp.ring, (size_t)sp.ring_moves * e->B * sp.rec_floats)
 #undef DM
   sp.env_offset = e->cfg.env_id_offset;
@@ -67,18 +63,13 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
   HIPCHECK(hipMemcpyAsync(sp.temp, temp.data(), temp.size() * 8, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemcpyAsync(sp.temp_next, temp.data(), 8, hipMemcpyHostToDevice, s));
   HIPCHECK(hipStreamSynchronize(s));
-  sp.moves_host = 0;
-  sp.drained = 0;
   // drains issued on COPY streams may still be reading the ring (only the compute stream was synchronised above): wait
   // for the latest one -- drains are chained, so it covers every earlier copy -- before the ordering state is dropped
   // and the next moves may overwrite any slot
-  if (e->drain_pending && e->drain_ev) HIPCHECK(hipEventSynchronize(e->drain_ev));
-  for (auto &q : e->drain_q) e->drain_ev_pool.push_back(q.second);
-  e->drain_q.clear();
-  e->drain_ev = nullptr;
-  e->drain_pending = false;
+  if (e->ring.latest()) HIPCHECK(hipEventSynchronize((hipEvent_t)e->ring.latest()));
+  e->ring.forget(0);
   sp.ready = true;
-  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  drop_graphs(e, false);
   return 0;
 }
 
@@ -144,13 +135,11 @@ int mz_selfplay_set_moves(mz_engine *e, unsigned long long moves) {
   MZ_ENTER(e);
   SelfplayState &sp = e->sp;
   if (!sp.ready) return fail("mz_selfplay_set_moves: call mz_selfplay_reset first");
-  if (sp.moves_host != sp.drained) return fail("mz_selfplay_set_moves: %llu moves wait in the device ring; drain them first", sp.moves_host - sp.drained);
+  if (e->ring.undrained()) return fail("mz_selfplay_set_moves: %llu moves wait in the device ring; drain them first", e->ring.undrained());
   HIPCHECK(hipDeviceSynchronize());        // (moves in flight still read the counters; drains still read the ring)
   std::vector<unsigned long long> m((size_t)e->Bp, moves);
   HIPCHECK(hipMemcpy(sp.movecnt, m.data(), m.size() * 8, hipMemcpyHostToDevice));
-  sp.moves_host = sp.drained = moves;
-  for (auto &q : e->drain_q) e->drain_ev_pool.push_back(q.second);
-  e->drain_q.clear(); e->drain_pending = false;
+  e->ring.forget(moves);
   return 0;
 }
 
@@ -169,7 +158,7 @@ int mz_selfplay_set_obs(mz_engine *e, int uint8_obs, const float *obs_min, const
   if ((sp.env_kind == 2 || sp.env_kind == 3) && (uint8_obs || obs_min))
     return fail("mz_selfplay_set_obs: the %s environment has neither byte observations nor --norm_obs", mz_game_info(sp.env_kind).name);
   if (selfplay_alloc(e)) return -1;
-  if (sp.moves_host != sp.drained) return fail("mz_selfplay_set_obs: drain the ring first (the record layout may change)");
+  if (e->ring.undrained()) return fail("mz_selfplay_set_obs: drain the ring first (the record layout may change)");
   sp.obs_u8 = uint8_obs;
   sp.obs_slots = uint8_obs == 2 ? (e->O + 3) / 4 : e->O;
   sp.rec_floats = sp.obs_slots + e->A + MZ_REC_EXTRA;
@@ -185,7 +174,7 @@ int mz_selfplay_set_obs(mz_engine *e, int uint8_obs, const float *obs_min, const
   } else {
     sp.obs_min = sp.obs_rng = nullptr;
   }
-  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }   // kernel arguments are baked into graphs
+  drop_graphs(e, false);
   return 0;
 }
 
@@ -196,7 +185,7 @@ int mz_selfplay_export_trees(mz_engine *e, int keep) {
   MZ_ENTER(e);
   HIPCHECK(hipDeviceSynchronize());
   e->sp.export_trees = keep ? 1 : 0;
-  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  drop_graphs(e, false);
   return 0;
 }
 
@@ -231,7 +220,7 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
   }
   sp.env_kind = kind;
   sp.ready = false;                // the environment state is (re)made by mz_selfplay_reset
-  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  drop_graphs(e, false);
   return 0;
 }
 
@@ -263,10 +252,10 @@ int mz_selfplay_noise_log(mz_engine *e, int keep) {
   HIPCHECK(hipDeviceSynchronize());
   SelfplayState &sp = e->sp;
   if (keep && !e->noise_log) {
-    if (dmalloc(e, &e->noise_log, (size_t)sp.ring_moves * e->B * e->A)) return -1;
+    if (dmalloc(e, &e->noise_log, (size_t)e->ring.capacity * e->B * e->A)) return -1;
   }
   sp.noise_log = keep ? e->noise_log : nullptr;
-  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }   // kernel arguments are baked into graphs
+  drop_graphs(e, false);
   return 0;
 }
 
@@ -286,9 +275,7 @@ int mz_sim_io(mz_engine *e, int mode, float *buf, int keep_moves) {
   HIPCHECK(hipDeviceSynchronize());
   e->tv.sim_io = mode ? buf : nullptr;
   e->tv.sim_io_keep = mode == 2 ? -keep_moves : (mode == 1 ? keep_moves : 0);
-  // kernel arguments are baked into graphs
-  if (e->search_graph) { hipGraphExecDestroy(e->search_graph); e->search_graph = nullptr; }
-  for (auto &g : e->move_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  drop_graphs(e, true);
   return 0;
 }
 
@@ -299,56 +286,95 @@ int mz_selfplay_read_noise(mz_engine *e, uint64_t move, double *out) {
   MZ_ENTER(e);
   SelfplayState &sp = e->sp;
   if (!sp.noise_log) return fail("mz_selfplay_read_noise: the noise log is off (mz_selfplay_noise_log)");
-  if (move >= sp.moves_host || sp.moves_host - move > (unsigned long long)sp.ring_moves)
+  const RecordRing &ring = e->ring;
+  if (move >= ring.produced || ring.produced - move > (unsigned long long)ring.capacity)
     return fail("mz_selfplay_read_noise: move %llu is not among the last %d of %llu moves played", (unsigned long long)move,
-                sp.ring_moves, sp.moves_host);
+                ring.capacity, ring.produced);
   HIPCHECK(hipDeviceSynchronize());
   if (move >> 32) return fail("mz_selfplay_read_noise: the log is indexed by the low 32 bits of the move counter");
-  HIPCHECK(hipMemcpy(out, sp.noise_log + (size_t)((uint32_t)move % (uint32_t)sp.ring_moves) * e->B * e->A,
-                     (size_t)e->B * e->A * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(out, sp.noise_log + (size_t)ring.slot(move) * e->B * e->A, (size_t)e->B * e->A * sizeof(double),
+                     hipMemcpyDeviceToHost));
   return 0;
 }
 
-// The slots the coming moves write may still be the source of a drain's D2H copy on another stream: order this stream
-// behind the copies that read them -- the drains covering moves below moves_host + moves - ring_moves, i.e. up to the
-// OLDEST queued drain that reaches that far (drains complete in order: they are chained when issued on different
-// streams).  Waiting for the latest drain instead, as this did until r03_j, exposed a whole chunk's copy every time the
-// ring wrapped: with 16-move chunks of 2.4 MB records (Pong-ram shapes, a 53-move ring) every third launch stood behind
-// the copy of the chunk just before it -- 272 us per launch, 2.2 % of the loop.
-static int selfplay_order_behind_drain(mz_engine *e, int moves, hipStream_t s) {
-  SelfplayState &sp = e->sp;
-  const unsigned long long end = sp.moves_host + (unsigned long long)moves;
-  if (end <= (unsigned long long)sp.ring_moves) return 0;
-  const unsigned long long need = end - (unsigned long long)sp.ring_moves;    // moves below this index lose their slots
-  hipEvent_t wait_for = nullptr;
-  while (!e->drain_q.empty()) {
-    // the front drain covers moves [previous front's end, front.first): relevant if it starts below `need`
-    const unsigned long long start = e->drain_q_start;
-    if (start >= need) break;
-    wait_for = e->drain_q.front().second;
-    e->drain_q_start = e->drain_q.front().first;
-    e->drain_ev_pool.push_back(wait_for);          // (re-recorded only by a later drain, i.e. after this wait is enqueued)
-    e->drain_q.pop_front();
+// ---- producing moves.  mz_selfplay_steps, mz_selfplay_steps_into, mz_selfplay_steps_timed and mz_selfplay_phase_profile all go
+// produce_begin -> launch_moves under a ProduceGuard (mz_selfplay_ring.inc) -> produce_finish.
+
+// The preconditions the producers share, in fn's name -- reset, weights, `own` (the caller's own refusal, or null), 1 <= moves <=
+// most and, for moves into the device ring (into_ring), the ring's room -- then the stream is ordered behind the drains whose
+// copies still read the slots about to be written.  < 0: failed; PRODUCE_RANGE / PRODUCE_FULL: refused in the caller's words
+// (the sentences differ).
+enum { PRODUCE_RANGE = 1, PRODUCE_FULL = 2 };
+static int produce_begin(mz_engine *e, const char *fn, const char *own, int moves, int most, bool into_ring, hipStream_t s) {
+  if (!e->sp.ready) return fail("%s: call mz_selfplay_reset first", fn);
+  if (!e->weights_set) return fail("%s: weights not set (call mz_set_weights)", fn);
+  if (own) return fail("%s: %s", fn, own);
+  if (moves < 1 || moves > most) return PRODUCE_RANGE;
+  if (!into_ring) return 0;
+  if (!e->ring.fits(moves)) return PRODUCE_FULL;
+  if (void *ev = e->ring.order_behind_drains(moves)) HIPCHECK(hipStreamWaitEvent(s, (hipEvent_t)ev, 0));
+  return 0;
+}
+
+// k moves on stream s (or into a capture): ONE launch of the search kernel where the loop runs as whole moves (no root kernel),
+// else k times a move's kernels.  o: each launch's search (the timed and profiled runs add events / counters)
+static int launch_moves(mz_engine *e, int k, SearchOpts o, hipStream_t s) {
+  if (search_plan(e).persist) {
+    o.moves = k;
+    return launch_search(e, o, true, s);
   }
-  if (wait_for) HIPCHECK(hipStreamWaitEvent(s, wait_for, 0));
-  if (e->drain_q.empty()) { e->drain_pending = false; }
+  for (int i = 0; i < k; ++i)
+    if (launch_move(e, o, s)) return -1;
   return 0;
 }
 
-static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, float *direct);
+static int produce_finish(mz_engine *e, int moves, ProduceGuard &guard) {
+  guard.ok = true;
+  e->ring.produced += (unsigned long long)moves;
+  e->root_ready = true;
+  e->sims_done = e->sims;
+  e->selection_valid = false;
+  return 0;
+}
 
-// mz_selfplay_steps_into without touching the kernels (k_search_fused's register allocation is tuned to the last scratch byte:
-// a slot argument cost it 1 % of the headline): the kernels keep computing slot = move % ring_moves, and the host hands them a
-// "ring" of ~2^30 slots whose origin lies (first_move % ring_moves) slots BEFORE the caller's buffer, so that the k moves from
-// first_move on land in its slots 0 .. k-1.  Of the two moduli one never wraps inside the k moves.
-static void selfplay_point_ring_at(mz_engine *e, float *dst, unsigned long long first_move, int k) {
+// direct: device mapping of the caller's pinned record buffer (mz_selfplay_steps_into), or null (the device ring)
+static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, float *direct) {
   SelfplayState &sp = e->sp;
-  int R = 1 << 30;
-  if (first_move % (unsigned long long)R + (unsigned long long)k > (unsigned long long)R) R -= 4096;
-  const size_t per_move = (size_t)e->B * sp.rec_floats;
-  // (an address computed in integers: the origin itself is never dereferenced, slot first_move % R is dst again)
-  sp.ring = (float *)((uintptr_t)dst - (uintptr_t)((size_t)(first_move % (unsigned long long)R) * per_move * sizeof(float)));
-  sp.ring_moves = R;
+  hipStream_t s = (hipStream_t)stream;
+  const char *inject = e->tv.sim_io_keep < 0 ? "mz_sim_io's inject mode applies to mz_search only (switch it off or to log mode)" : nullptr;
+  const int rc = produce_begin(e, "mz_selfplay_steps", inject, moves, INT_MAX, !direct, s);
+  if (rc == PRODUCE_RANGE) return fail("mz_selfplay_steps: moves must be >= 1");
+  if (rc == PRODUCE_FULL)
+    return fail("mz_selfplay_steps: experience ring holds %d moves; drain before producing %d more", e->ring.capacity, moves);
+  if (rc) return -1;
+  ProduceGuard guard{sp.ready};
+  // up to MZ_GRAPH_MOVES moves go out as ONE launch: whole moves inside the search kernel, else a hipGraph of the moves' kernels
+  // (one graph per distinct count, built on first use): back-to-back nodes inside a graph start without a gap, between graph
+  // launches the GPU idles ~9 us.  No graph for a direct launch (a captured one holds the device ring's address)
+  const bool graph = !direct && e->use_graph && !e->draws_set && !search_plan(e).persist;
+  for (int done = 0, k; done < moves; done += k) {
+    k = moves - done < MZ_GRAPH_MOVES ? moves - done : MZ_GRAPH_MOVES;
+    if (direct) {      // the kernels' "ring": RecordRing::direct_origin
+      const size_t bytes = (size_t)e->B * sp.rec_floats * sizeof(float);
+      const DirectOrigin at = RecordRing::direct_origin(e->ring.produced + (unsigned long long)done, k, bytes);
+      // (an address computed in integers: the origin itself is never dereferenced, slot first_move % R is the buffer again)
+      sp.ring = (float *)((uintptr_t)direct + (uintptr_t)((size_t)done * bytes) - (uintptr_t)at.back_bytes);
+      sp.ring_moves = at.R;
+    }
+    if (graph && !e->move_graph[k]) {
+      hipGraph_t g = nullptr;
+      HIPCHECK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
+      const int lrc = launch_moves(e, k, {e->sims}, e->cap_stream);
+      hipError_t ce = hipStreamEndCapture(e->cap_stream, &g);
+      if (lrc || ce != hipSuccess) return fail("mz_selfplay_steps: graph capture failed");
+      HIPCHECK(hipGraphInstantiate(&e->move_graph[k], g, nullptr, nullptr, 0));
+      hipGraphDestroy(g);
+    }
+    guard.attempted += k;
+    if (graph) HIPCHECK(hipGraphLaunch(e->move_graph[k], s));
+    else if (launch_moves(e, k, {e->sims}, s)) return -1;
+  }
+  return produce_finish(e, moves, guard);
 }
 
 int mz_selfplay_steps(mz_engine *e, int moves, void *stream) {
@@ -363,13 +389,15 @@ int mz_selfplay_steps(mz_engine *e, int moves, void *stream) {
 // complete when work recorded on `stream` behind this call is.  No ring slot, no D2H copy, no copy stream: the copy
 // engine's cross-stream dependency cost the host most of a core per rank (profiles/r05_host_threads.txt).  The device
 // ring must be empty (moves produced by mz_selfplay_steps are drained first); these moves count as drained.
+// The kernels stay untouched (k_search_fused's register allocation is tuned to the last scratch byte: a slot argument cost it
+// 1 % of the headline): the host points their ring at the buffer (selfplay_steps_impl) and back.
 int mz_selfplay_steps_into(mz_engine *e, int moves, float *host_records, void *stream) {
   if (!e || !host_records) return fail("mz_selfplay_steps_into: null argument");
   MZ_ENTER(e);
   if (!e->sp.ready) return fail("mz_selfplay_steps_into: call mz_selfplay_reset first");
   SelfplayState &sp = e->sp;
-  if (sp.moves_host != sp.drained)
-    return fail("mz_selfplay_steps_into: %llu moves wait in the device ring; drain them first", sp.moves_host - sp.drained);
+  if (e->ring.undrained())
+    return fail("mz_selfplay_steps_into: %llu moves wait in the device ring; drain them first", e->ring.undrained());
   if (moves < 1) return fail("mz_selfplay_steps_into: moves must be >= 1");
   void *dev = nullptr;
   if (hipHostGetDevicePointer(&dev, host_records, 0) != hipSuccess || !dev) {
@@ -378,77 +406,10 @@ int mz_selfplay_steps_into(mz_engine *e, int moves, float *host_records, void *s
   }
   if (sp.noise_log) return fail("mz_selfplay_steps_into: the Dirichlet log is indexed by ring slot (mz_selfplay_steps + mz_selfplay_drain)");
   float *ring = sp.ring;
-  const int ring_moves = sp.ring_moves;
   const int rc = selfplay_steps_impl(e, moves, stream, (float *)dev);
-  sp.ring = ring; sp.ring_moves = ring_moves;
+  sp.ring = ring; sp.ring_moves = e->ring.capacity;
   if (rc) return rc;
-  sp.drained = sp.moves_host;
-  return 0;
-}
-
-// direct: device mapping of the caller's pinned record buffer (mz_selfplay_steps_into), or null (the device ring)
-static int selfplay_steps_impl(mz_engine *e, int moves, void *stream, float *direct) {
-  if (!e->sp.ready) return fail("mz_selfplay_steps: call mz_selfplay_reset first");
-  if (!e->weights_set) return fail("mz_selfplay_steps: weights not set (call mz_set_weights)");
-  SelfplayState &sp = e->sp;
-  if (e->tv.sim_io_keep < 0) return fail("mz_selfplay_steps: mz_sim_io's inject mode applies to mz_search only (switch it off or to log mode)");
-  if (moves < 1) return fail("mz_selfplay_steps: moves must be >= 1");
-  if (!direct && sp.moves_host + moves - sp.drained > (unsigned long long)sp.ring_moves)
-    return fail("mz_selfplay_steps: experience ring holds %d moves; drain before producing %d more", sp.ring_moves,
-                moves);
-  hipStream_t s = (hipStream_t)stream;
-  if (!direct && selfplay_order_behind_drain(e, moves, s)) return -1;
-  // A failure AFTER some chunks went out leaves the device's move counters ahead of moves_host: the next call's ring origin
-  // (first_move % ring_moves) would disagree with the kernels' slot and a direct launch would write records outside the
-  // caller's pinned buffer (ADVICE r05).  Such a state is not resumed: the self-play state is marked not ready -- every later call
-  // fails with "call mz_selfplay_reset first"
-  struct Partial {
-    SelfplayState &sp; int launched = 0; bool ok = false;
-    ~Partial() { if (!ok && launched > 0) sp.ready = false; }
-  } partial{sp};
-  // up to MZ_GRAPH_MOVES moves go out as ONE graph launch (one graph per distinct count, built on first use):
-  // back-to-back nodes inside a graph start without a gap, between graph launches the GPU idles ~9 us
-  const bool persist = search_plan(e).persist;
-  for (int left = moves; left > 0; partial.launched = moves - left) {
-    const int k = left < MZ_GRAPH_MOVES ? left : MZ_GRAPH_MOVES;
-    if (direct) selfplay_point_ring_at(e, direct + (size_t)(moves - left) * e->B * sp.rec_floats,
-                                       sp.moves_host + (unsigned long long)(moves - left), k);
-    if (persist) {      // k whole moves inside one launch of the search kernel: no root kernel, no graph
-      SearchOpts o = {e->sims};
-      o.moves = k;
-      if (launch_search(e, o, true, s)) return -1;
-      left -= k;
-      continue;
-    }
-    if (direct) {       // (no graph: a captured one holds the device ring's address)
-      for (int i = 0; i < k; ++i)
-        if (launch_move(e, {e->sims}, s)) return -1;
-      left -= k;
-      continue;
-    }
-    if (e->use_graph && !e->draws_set && !e->move_graph[k]) {
-      hipGraph_t g = nullptr;
-      HIPCHECK(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-      int rc = 0;
-      for (int i = 0; i < k && !rc; ++i) rc = launch_move(e, {e->sims}, e->cap_stream);
-      hipError_t ce = hipStreamEndCapture(e->cap_stream, &g);
-      if (rc || ce != hipSuccess) return fail("mz_selfplay_steps: graph capture failed");
-      HIPCHECK(hipGraphInstantiate(&e->move_graph[k], g, nullptr, nullptr, 0));
-      hipGraphDestroy(g);
-    }
-    if (e->move_graph[k] && !e->draws_set) {
-      HIPCHECK(hipGraphLaunch(e->move_graph[k], s));
-    } else {
-      for (int i = 0; i < k; ++i)
-        if (launch_move(e, {e->sims}, s)) return -1;
-    }
-    left -= k;
-  }
-  partial.ok = true;
-  sp.moves_host += moves;
-  e->root_ready = true;
-  e->sims_done = e->sims;
-  e->selection_valid = false;
+  e->ring.drained = e->ring.produced;
   return 0;
 }
 
@@ -457,78 +418,60 @@ int mz_selfplay_moves_per_launch(const mz_engine *e) {
   return search_plan(e).persist ? MZ_GRAPH_MOVES : 0;
 }
 int mz_selfplay_rec_floats(const mz_engine *e) { return e ? (e->sp.t ? e->sp.rec_floats : e->O + e->A + MZ_REC_EXTRA) : -1; }
-int mz_selfplay_ring_moves(const mz_engine *e) { return (e && e->sp.t) ? e->sp.ring_moves : -1; }
+int mz_selfplay_ring_moves(const mz_engine *e) { return (e && e->sp.t) ? e->ring.capacity : -1; }
 
 int mz_selfplay_steps_timed(mz_engine *e, int k, float *ms_out, void *stream) {
   if (!e || !ms_out) return fail("mz_selfplay_steps_timed: null argument");
-  if (!e->sp.ready) return fail("mz_selfplay_steps_timed: call mz_selfplay_reset first");
-  if (!e->weights_set) return fail("mz_selfplay_steps_timed: weights not set (call mz_set_weights)");
-  if (!fused_usable(e)) return fail("mz_selfplay_steps_timed: fused kernel not in use");
-  if (k < 1 || (unsigned long long)k > (unsigned long long)e->sp.ring_moves - (e->sp.moves_host - e->sp.drained))
-    return fail("mz_selfplay_steps_timed: %d moves do not fit the undrained ring", k);
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
-  if (selfplay_order_behind_drain(e, k, s)) return -1;
-  // whole moves inside the launch (HEAD): one dispatch of up to MZ_GRAPH_MOVES moves, every move of it reported as
-  // its share of the dispatch's duration
-  const bool persist = search_plan(e).persist;
-  const int nl = persist ? (k + MZ_GRAPH_MOVES - 1) / MZ_GRAPH_MOVES : k;
+  const int brc = produce_begin(e, "mz_selfplay_steps_timed", fused_usable(e) ? nullptr : "fused kernel not in use", k, INT_MAX, true, s);
+  if (brc > 0) return fail("mz_selfplay_steps_timed: %d moves do not fit the undrained ring", k);
+  if (brc) return -1;
+  // eager launches, back to back, no synchronisation in between, events around every search dispatch; where the loop runs as
+  // whole moves one dispatch holds up to MZ_GRAPH_MOVES moves, every move of it reported as its share of the dispatch's duration
+  const int per = search_plan(e).persist ? MZ_GRAPH_MOVES : 1, nl = (k + per - 1) / per;
   std::vector<hipEvent_t> ev(2 * (size_t)nl, nullptr);
   for (auto &x : ev) HIPCHECK(hipEventCreate(&x));
+  ProduceGuard guard{e->sp.ready};
   int rc = 0;
-  for (int i = 0; i < nl && !rc; ++i) {        // eager launches, back to back, no synchronisation in between
-    if (persist) {
-      SearchOpts o = {e->sims};
-      o.moves = (k - i * MZ_GRAPH_MOVES) < MZ_GRAPH_MOVES ? (k - i * MZ_GRAPH_MOVES) : MZ_GRAPH_MOVES;
-      o.ev_start = ev[2 * i]; o.ev_stop = ev[2 * i + 1];
-      rc = launch_search(e, o, true, s);
-    } else {
-      SearchOpts o = {e->sims};
-      o.ev_start = ev[2 * i]; o.ev_stop = ev[2 * i + 1];
-      rc = launch_move(e, o, s);
-    }
+  for (int i = 0; i < nl && !rc; ++i) {
+    SearchOpts o = {e->sims};
+    o.ev_start = ev[2 * i]; o.ev_stop = ev[2 * i + 1];
+    ++guard.attempted;
+    rc = launch_moves(e, k - i * per < per ? k - i * per : per, o, s);
   }
   hipError_t se = hipStreamSynchronize(s);
   if (!rc && se == hipSuccess)
     for (int i = 0; i < nl; ++i) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) != hipSuccess) { rc = fail("mz_selfplay_steps_timed: event timing failed"); break; }
-      if (persist) {
-        const int m0 = i * MZ_GRAPH_MOVES, m1 = (m0 + MZ_GRAPH_MOVES < k) ? m0 + MZ_GRAPH_MOVES : k;
-        for (int m = m0; m < m1; ++m) ms_out[m] = ms / (float)(m1 - m0);
-      } else {
-        ms_out[i] = ms;
-      }
+      const int m0 = i * per, m1 = m0 + per < k ? m0 + per : k;
+      for (int m = m0; m < m1; ++m) ms_out[m] = ms / (float)(m1 - m0);
     }
   for (auto &x : ev) hipEventDestroy(x);
   if (rc) return -1;
   if (se != hipSuccess) return fail("mz_selfplay_steps_timed: %s", hipGetErrorString(se));
-  e->sp.moves_host += (unsigned long long)k;
-  e->root_ready = true;
-  e->sims_done = e->sims;
-  e->selection_valid = false;
-  return 0;
+  return produce_finish(e, k, guard);
 }
 
 int mz_selfplay_phase_profile(mz_engine *e, int moves, double *cycles_out, void *stream) {
   if (!e || !cycles_out) return fail("mz_selfplay_phase_profile: null argument");
-  if (!e->sp.ready) return fail("mz_selfplay_phase_profile: call mz_selfplay_reset first");
-  if (!e->weights_set) return fail("mz_selfplay_phase_profile: weights not set (call mz_set_weights)");
-  if (!search_plan(e).persist || e->split_f16)
-    return fail("mz_selfplay_phase_profile: the self-play loop of this configuration does not run as whole moves in one launch of the exact-f32 kernel");
-  if (moves < 1 || moves > MZ_GRAPH_MOVES ||
-      (unsigned long long)moves > (unsigned long long)e->sp.ring_moves - (e->sp.moves_host - e->sp.drained))
-    return fail("mz_selfplay_phase_profile: %d moves: at most %d per launch, and they must fit the undrained ring", moves, MZ_GRAPH_MOVES);
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
-  if (selfplay_order_behind_drain(e, moves, s)) return -1;
+  const char *own = search_plan(e).persist && !e->split_f16 ? nullptr :
+      "the self-play loop of this configuration does not run as whole moves in one launch of the exact-f32 kernel";
+  const int brc = produce_begin(e, "mz_selfplay_phase_profile", own, moves, MZ_GRAPH_MOVES, true, s);
+  if (brc > 0)
+    return fail("mz_selfplay_phase_profile: %d moves: at most %d per launch, and they must fit the undrained ring", moves, MZ_GRAPH_MOVES);
+  if (brc) return -1;
   const size_t n = (size_t)(e->Bp / MZ_ROWS) * 4 * 8;
   unsigned long long *buf = nullptr;
   HIPCHECK(hipMalloc((void **)&buf, n * 8));
+  ProduceGuard guard{e->sp.ready};
   SearchOpts o = {e->sims};
-  o.moves = moves;
   o.prof = buf;
-  const int rc = launch_search(e, o, true, s);
+  ++guard.attempted;
+  const int rc = launch_moves(e, moves, o, s);
   hipError_t se = hipStreamSynchronize(s);
   std::vector<unsigned long long> h(n);
   if (!rc && se == hipSuccess) se = hipMemcpy(h.data(), buf, n * 8, hipMemcpyDeviceToHost);
@@ -543,47 +486,33 @@ int mz_selfplay_phase_profile(mz_engine *e, int moves, double *cycles_out, void 
     for (size_t i = 0; i < n / 8; ++i) sum += (double)h[i * 8 + order[p]];
     cycles_out[p] = sum / (double)(n / 8) / (double)moves;
   }
-  e->sp.moves_host += (unsigned long long)moves;
-  e->root_ready = true;
-  e->sims_done = e->sims;
-  e->selection_valid = false;
-  return 0;
+  return produce_finish(e, moves, guard);
 }
 
 int mz_selfplay_drain(mz_engine *e, float *out, int max_moves, int *n_moves, void *stream) {
   if (!e || !out || !n_moves) return fail("mz_selfplay_drain: null argument");
+  MZ_ENTER(e);
   SelfplayState &sp = e->sp;
   if (!sp.ready) return fail("mz_selfplay_drain: call mz_selfplay_reset first");
-  MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
-  // drains on different streams: chain them, so that the one event recorded below covers every copy issued so far
-  if (e->drain_pending && e->drain_stream != s) HIPCHECK(hipStreamWaitEvent(s, e->drain_ev, 0));
-  unsigned long long avail = sp.moves_host - sp.drained;
-  int n = (int)(avail < (unsigned long long)max_moves ? avail : (unsigned long long)max_moves);
+  const RingDrain d = e->ring.plan_drain(max_moves, stream);
+  // drains on different streams: chained, so that the one event recorded below covers every copy issued so far
+  if (d.chain) HIPCHECK(hipStreamWaitEvent(s, (hipEvent_t)d.chain, 0));
   const size_t per_move = (size_t)e->B * sp.rec_floats;
-  for (int i = 0; i < n;) {
-    const int slot = (int)((sp.drained + i) % sp.ring_moves);
-    int run = sp.ring_moves - slot;
-    if (run > n - i) run = n - i;
-    HIPCHECK(hipMemcpyAsync(out + (size_t)i * per_move, sp.ring + (size_t)slot * per_move,
-                            (size_t)run * per_move * sizeof(float), hipMemcpyDeviceToHost, s));
-    i += run;
+  for (int r = 0; r < d.runs; ++r) {
+    HIPCHECK(hipMemcpyAsync(out, sp.ring + (size_t)d.run[r].slot * per_move, (size_t)d.run[r].moves * per_move * sizeof(float),
+                            hipMemcpyDeviceToHost, s));
+    out += (size_t)d.run[r].moves * per_move;
   }
-  if (n > 0) {
-    // `drained` advances when the copy is ENQUEUED: the slots are reusable only once the copy has read them.  The
-    // event marks that point; mz_selfplay_steps waits for it before it launches moves into slots not yet covered.
-    hipEvent_t ev = nullptr;
-    if (!e->drain_ev_pool.empty()) { ev = e->drain_ev_pool.back(); e->drain_ev_pool.pop_back(); }
-    else HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (d.moves > 0) {
+    // the event marks the point where the copies have read their slots: mz_selfplay_steps waits for it before it launches
+    // moves into slots not yet covered (RecordRing::note_drain, order_behind_drains)
+    hipEvent_t ev = (hipEvent_t)e->ring.take_token();
+    if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIPCHECK(hipEventRecord(ev, s));
-    if (e->drain_q.empty()) e->drain_q_start = sp.drained;
-    e->drain_q.emplace_back(sp.drained + (unsigned long long)n, ev);
-    e->drain_ev = ev;
-    e->drain_stream = s;
-    e->drain_pending = true;
+    e->ring.note_drain(d.moves, ev, stream);
   }
-  sp.drained += n;
-  *n_moves = n;
+  *n_moves = d.moves;
   return 0;
 }
 

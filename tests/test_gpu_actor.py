@@ -261,6 +261,44 @@ def test_timed_launches_are_the_same_moves():
     assert np.array_equal(trees[0][k], trees[1][k]), k
 
 
+def test_ring_room_at_its_boundary_for_the_three_producers():
+  """The experience ring's room, one move either side of full, as each of the three producers words it: with 250 of 256 moves
+  undrained mz_selfplay_steps, mz_selfplay_steps_timed and mz_selfplay_phase_profile refuse 7 moves, 6 are accepted, then 1 is
+  refused; the refusals leave nothing behind -- the drained 256 moves equal, bit for bit, those of an engine that drained every 16."""
+  import torch
+  from oracle import oracle as orc
+  from model_based_rl_amd.engine import Engine
+  w = orc.load_weights(np.load(os.path.join(G, 'g1_net_lunar.npz')))
+
+  def make():
+    eng = Engine(16, 8, 4, 2, seed=6)
+    eng.set_weights(w)
+    eng.selfplay_reset(7, 1.0, stagger=True)
+    return eng
+  full, ref = make(), make()
+  assert full.ring_moves == 256 and full.search_kernel_info()['kind'] == 'fused' and full.selfplay_moves_per_launch() == 16
+  for k in [16] * 15 + [10]:
+    full.selfplay_steps(k)
+  with pytest.raises(RuntimeError, match='experience ring holds 256 moves; drain before producing 7 more'):
+    full.selfplay_steps(7)
+  with pytest.raises(RuntimeError, match='mz_selfplay_steps_timed: 7 moves do not fit the undrained ring'):
+    full.selfplay_steps_timed(7)
+  with pytest.raises(RuntimeError, match='mz_selfplay_phase_profile: 7 moves: at most 16 per launch, and they must fit the undrained ring'):
+    full.selfplay_phase_profile(7)
+  full.selfplay_steps(6)
+  with pytest.raises(RuntimeError, match='experience ring holds 256 moves; drain before producing 1 more'):
+    full.selfplay_steps(1)
+  got, n = full.selfplay_drain(max_moves=256)
+  assert n == 256
+  want = torch.empty(256, 16, ref.rec_floats, dtype=torch.float32).pin_memory()
+  for i in range(0, 256, 16):
+    ref.selfplay_steps(16)
+    assert ref.selfplay_drain(want[i:i + 16], 16)[1] == 16
+  torch.cuda.synchronize()
+  assert np.array_equal(got.numpy()[:256].view(np.int32), want.numpy().view(np.int32))
+  full.close(); ref.close()
+
+
 @pytest.mark.parametrize('A,sims,T,temp,ns,split', [(4, 30, 5, 1.0, False, False), (6, 12, 4, 0.5, False, False),
                                                     (3, 9, 3, 0.0, False, False), (18, 8, 3, 1.0, False, False),
                                                     (4, 30, 5, 1.0, True, False), (4, 30, 5, 1.0, False, True),
