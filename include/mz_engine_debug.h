@@ -93,6 +93,19 @@ int mz_fcl_plan_host(int batch, int unroll_steps, int obs_dim, int action_space,
                      int opt_kind, int scalar_loss, long long *out, char *names, size_t names_cap);
 int mz_fcl_plan(mz_fcl *c, int opt_kind, int scalar_loss, long long *out, char *names, size_t names_cap);
 
+/* test hooks: the gather tables of the weight streams (csrc/mz_pack.inc).  mz_pack_host: no engine, no device -- the plan mz_create would
+ * build for this shape (value_bins / reward_bins: the supports' sizes, 1 / 1 for no_support; split_f16 != 0: with the split-f16 stream,
+ * action_space <= 13).  out [host][MZ_PACK_FIELDS] = floats of the flat vector, floats of the packed vector, the segments' offsets in it
+ * (w0o, b0o, w1, b1, w2, b2, w3, b3, w4, b4, lnw, lnb of the stand-alone kernels; the fused kernel's fc1 packs w1f, w3f, its stream ws,
+ * the small-MFMA packs h4, p4, the root's stream is), floats per wave of the fused stream, float16 of the split-f16 stream, ks0, ks1, ks3,
+ * steps per wave of the fused stream, first-stage steps and all steps of the root's, groups per wave of the split-f16 stream.
+ * which = 0 idx, 1 idx2 (out[1] entries each), 2 idx_h2 (out[21] entries): copied to table [host][cap] where table is not null (cap
+ * smaller than the table is refused).  mz_pack_indices: the same tables as engine e holds them on its device (synchronous). */
+#define MZ_PACK_FIELDS 29
+int mz_pack_host(int obs_dim, int action_space, int value_bins, int reward_bins, int split_f16, long long *out, int which, int32_t *table,
+                 size_t cap);
+int mz_pack_indices(mz_engine *e, int which, int32_t *out, size_t cap);
+
 /* development hook: s_memtime stamps (shader clock) at the phase boundaries of k_fcl_heads, workgroup 0 of every head at unroll
  * position 1 (3 x 16 slots), and of k_fcl_chain_fwd4's position 2 (slots 48..53); slots 12..15, 28..31, 44..47, 59..66: the two-launch
  * step's timeline on the constant 100 MHz clock (chain workgroup 0's passes, its last two positions' value units, the last unit / job /

@@ -2,10 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mz_stream_sizes.h"   // MZ_H, MZ_F
 
-#define MZ_H 50          // FCNetwork hidden_dim (reference networks.py:135)
 #define MZ_HS 52         // hidden-state row stride in the pool (16-byte aligned rows, pad = 0)
-#define MZ_F 512         // FC head width
 #define MZ_ROWS 16       // trees per workgroup = MFMA N dimension of v_mfma_f32_16x16x4_f32
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -33,6 +33,7 @@
 #include "mz_learner.hip.h"
 #include "mz_fcl.hip.h"
 #include "mz_fcl_plan.inc"
+#include "mz_pack.inc"            // FlatLayout, pack_plan
 #include "mz_eval.hip.h"
 #include "mz_eval_env.hip.h"
 #include "mz_match.hip.h"
@@ -100,12 +101,6 @@ static int fail(const char *fmt, ...) {
     hipError_t err_ = (x);                                                                 \
     if (err_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(err_), __FILE__, __LINE__); \
   } while (0)
-
-// offsets of the 22 tensors inside the flat weight vector (flat_layout below)
-struct FlatLayout {
-  size_t rep_w1, rep_b1, rep_w2, rep_b2, val_w1, val_b1, val_w2, val_b2, pol_w1, pol_b1, pol_w2, pol_b2, rew_w1,
-      rew_b1, rew_w2, rew_b2, tr_w1, tr_b1, tr_w2, tr_b2, ln_w, ln_b, total;
-};
 
 struct mz_engine {
   mz_config cfg;
@@ -250,122 +245,9 @@ static int dmalloc(mz_engine *e, T **p, size_t n) {
   return 0;
 }
 
-// ---------------------------------------------------------------- weight layout
+// ---------------------------------------------------------------- weight layout (mz_pack.inc)
 
-static FlatLayout flat_layout(int O, int A, int Sv, int Sr) {
-  FlatLayout L;
-  size_t off = 0;
-  auto take = [&](size_t n) { size_t o = off; off += n; return o; };
-  const int K = MZ_H + A;
-  L.rep_w1 = take((size_t)MZ_F * O); L.rep_b1 = take(MZ_F); L.rep_w2 = take((size_t)MZ_H * MZ_F); L.rep_b2 = take(MZ_H);
-  L.val_w1 = take((size_t)MZ_F * MZ_H); L.val_b1 = take(MZ_F); L.val_w2 = take((size_t)Sv * MZ_F); L.val_b2 = take(Sv);
-  L.pol_w1 = take((size_t)MZ_F * MZ_H); L.pol_b1 = take(MZ_F); L.pol_w2 = take((size_t)A * MZ_F); L.pol_b2 = take(A);
-  L.rew_w1 = take((size_t)MZ_F * K); L.rew_b1 = take(MZ_F); L.rew_w2 = take((size_t)Sr * MZ_F); L.rew_b2 = take(Sr);
-  L.tr_w1 = take((size_t)MZ_F * K); L.tr_b1 = take(MZ_F); L.tr_w2 = take((size_t)MZ_H * MZ_F); L.tr_b2 = take(MZ_H);
-  L.ln_w = take(MZ_H); L.ln_b = take(MZ_H);
-  L.total = off;
-  return L;
-}
-
-// fc1 pack: weights [4 waves][NT/4][ks][64][4], bias [4][NT][64][4]; NT = 8*NH tiles per wave, tile t of
-// wave w = head t/8, features 128w + 16(t%8) + 0..15.
-static void fill_fc1(std::vector<int32_t> &idx, size_t wpos, size_t bpos, int NH, const size_t *woff,
-                     const size_t *boff, int K, int ks) {
-  const int NT = 8 * NH, TG = NT / 4;
-  for (int w = 0; w < 4; ++w)
-    for (int tg = 0; tg < TG; ++tg)
-      for (int s = 0; s < ks; ++s)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int i = 0; i < 4; ++i) {
-            const int t = 4 * tg + i, head = t / 8, tt = t % 8;
-            const int nf = 128 * w + 16 * tt + (lane & 15), k = 4 * s + (lane >> 4);
-            idx[wpos + ((((size_t)(w * TG + tg) * ks + s) * 64 + lane) * 4 + i)] =
-                k < K ? (int32_t)(woff[head] + (size_t)nf * K + k) : -1;
-          }
-  for (int w = 0; w < 4; ++w)
-    for (int t = 0; t < NT; ++t)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int r = 0; r < 4; ++r) {
-          const int head = t / 8, tt = t % 8;
-          const int nf = 128 * w + 16 * tt + 4 * (lane >> 4) + r;
-          idx[bpos + (((size_t)(w * NT + t) * 64 + lane) * 4 + r)] = (int32_t)(boff[head] + nf);
-        }
-}
-
-// fc1 pack for the fused kernel: as fill_fc1 (two heads), but input column K carries the bias
-static void fill_fc1_biascol(std::vector<int32_t> &idx, size_t wpos, const size_t *woff, const size_t *boff, int K,
-                             int ks) {
-  for (int w = 0; w < 4; ++w)
-    for (int tg = 0; tg < 4; ++tg)
-      for (int s = 0; s < ks; ++s)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int i = 0; i < 4; ++i) {
-            const int t = 4 * tg + i, head = t / 8, tt = t % 8;
-            const int nf = 128 * w + 16 * tt + (lane & 15), k = 4 * s + (lane >> 4);
-            int32_t v = -1;
-            if (k < K) v = (int32_t)(woff[head] + (size_t)nf * K + k);
-            else if (k == K) v = (int32_t)(boff[head] + nf);
-            idx[wpos + ((((size_t)(w * 4 + tg) * ks + s) * 64 + lane) * 4 + i)] = v;
-          }
-}
-
-// dynamics fc1 pack for the fused kernel: as fill_fc1_biascol, but without a bias column -- the input's one-hot part holds
-// exactly one 1, so the bias rides in the one-hot columns: their packed weight is W[n][50 + a] + b[n] (idx2 = the
-// bias element to add, k_pack_weights).  K = 50 + A columns instead of 51 + A: one k-step of four fewer for
-// A = 6, 10, 14, ... (Pong-ram: 14 steps instead of 15).
-// Kuse < K (the rows with an action table, mz_fused_atab): only the first Kuse = 50 columns are packed, the one-hot
-// columns + bias go into the table (fill_action_table).
-static void fill_fc1_foldbias(std::vector<int32_t> &idx, std::vector<int32_t> &idx2, size_t wpos, const size_t *woff,
-                              const size_t *boff, int K, int ks, int Kuse) {
-  for (int w = 0; w < 4; ++w)
-    for (int tg = 0; tg < 4; ++tg)
-      for (int s = 0; s < ks; ++s)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int i = 0; i < 4; ++i) {
-            const int t = 4 * tg + i, head = t / 8, tt = t % 8;
-            const int nf = 128 * w + 16 * tt + (lane & 15), k = 4 * s + (lane >> 4);
-            const size_t o = wpos + ((((size_t)(w * 4 + tg) * ks + s) * 64 + lane) * 4 + i);
-            idx[o] = k < Kuse ? (int32_t)(woff[head] + (size_t)nf * K + k) : -1;
-            idx2[o] = (k >= MZ_H && k < Kuse) ? (int32_t)(boff[head] + nf) : -1;
-          }
-}
-
-// the action table of one wave (mz_fused.hip.h): T[a][tile 0..15][g 0..3][r 0..3] = W[nf][50 + a] + b[nf] -- what lane row g
-// holds of accumulator tile `tile` (head tile / 8, feature nf = 128 w + 16 (tile % 8) + 4 g + r) once the one-hot columns
-// and the bias are in.  Scale class 1: it is part of the fc1 layer.  Actions >= A stay zero.
-static void fill_action_table(std::vector<int32_t> &idx, std::vector<int32_t> &idx2, size_t pos, int w, const size_t *woff,
-                              const size_t *boff, int K, int A) {
-  for (int a = 0; a < A && a < MZ_ATAB_AMAX; ++a)
-    for (int t = 0; t < 16; ++t)
-      for (int g = 0; g < 4; ++g)
-        for (int r = 0; r < 4; ++r) {
-          const int head = t / 8, nf = 128 * w + 16 * (t % 8) + 4 * g + r;
-          const size_t o = pos + (size_t)a * 256 + t * 16 + g * 4 + r;
-          idx[o] = (int32_t)(woff[head] + (size_t)nf * K + MZ_H + a) | (1 << 29);
-          idx2[o] = (int32_t)(boff[head] + nf);
-        }
-}
-
-// fc2 pack: [JT][4 waves][8 tiles][64][4]: A operand row j = 16jt + (lane&15), k = 128w + 16t + 4(lane>>4) + r
-static void fill_fc2(std::vector<int32_t> &idx, size_t wpos, int JT, size_t woff, int J) {
-  for (int jt = 0; jt < JT; ++jt)
-    for (int w = 0; w < 4; ++w)
-      for (int t = 0; t < 8; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int r = 0; r < 4; ++r) {
-            const int j = 16 * jt + (lane & 15), nf = 128 * w + 16 * t + 4 * (lane >> 4) + r;
-            idx[wpos + ((((size_t)(jt * 4 + w) * 8 + t) * 64 + lane) * 4 + r)] =
-                j < J ? (int32_t)(woff + (size_t)j * MZ_F + nf) : -1;
-          }
-}
-
-static void fill_vec(std::vector<int32_t> &idx, size_t pos, int padded, size_t off, int n) {
-  for (int i = 0; i < padded; ++i) idx[pos + i] = i < n ? (int32_t)(off + i) : -1;
-}
-
-// ---- split-f16 weight stream (mz_fused_h2.hip.h): per wave [NGROUPS][8 pieces][64 lanes][8 halfs]; a group = the A
-// operands of four 16 x 32 blocks ("units"): pieces 0..3 their high parts, 4..7 their low parts.  Lane l of a piece holds
-// row l & 15, k = 8 (l >> 4) + j of the block.
+// the split-f16 weight stream (mz_fused_h2.hip.h) from its gather table: bit 30 of an index asks for the low part
 __global__ void k_pack_weights_h2(const float *flat, const int32_t *idx, _Float16 *packed, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -458,252 +340,67 @@ __global__ void k_relu_scale(const unsigned *mx, float *scale, int force) {
   scale[3] = ok ? 1.f : 0.f;
 }
 
-static int build_packing_h2(mz_engine *e, const FlatLayout &L, int Sv, int Sr) {
-  using SC = H2Sched;
-  const int A = e->A;
-  const size_t per_wave = (size_t)SC::NGROUPS * 8 * 512;
-  e->n_packed_h2 = 4 * per_wave;
-  std::vector<int32_t> idx(e->n_packed_h2, -1);
-  for (int w = 0; w < 4; ++w) {
-    size_t group = 0;
-    // unit: source index of (row 0..15, k 0..31) of one block, or -1
-    auto emit = [&](const std::function<int32_t(int, int)> (&unit)[4]) {
-      for (int part = 0; part < 2; ++part)
-        for (int u = 0; u < 4; ++u) {
-          const size_t base = (size_t)w * per_wave + (group * 8 + (size_t)part * 4 + u) * 512;
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int32_t sidx = unit[u](lane & 15, 8 * (lane >> 4) + j);
-              idx[base + (size_t)lane * 8 + j] = sidx < 0 ? -1 : (sidx | (part ? 0x40000000 : 0));
-            }
-        }
-      ++group;
-    };
-    // fc1 block: tile tt of this wave (head tt / 8, feature 128 w + 16 (tt % 8) + row), K chunk c; column K1 = bias
-    auto fc1_unit = [&](int tt, int c, const size_t *woff, const size_t *boff, int K1) {
-      return [=](int row, int kl) -> int32_t {
-        const int head = tt / 8, nf = 128 * w + 16 * (tt % 8) + row, k = 32 * c + kl;
-        if (k < K1) return (int32_t)(woff[head] + (size_t)nf * K1 + k);
-        if (k == K1) return (int32_t)(boff[head] + nf);
-        return -1;
-      };
-    };
-    // fc2 block: output rows 16 ot + row (< J) of the layer at woff, K pair p of this wave's eight tiles of the head:
-    // k = 8 g + j  <->  feature 128 w + 16 (2 p + (j >= 4)) + 4 g + (j & 3)   (the D fragments of tiles 2p, 2p+1)
-    auto fc2_unit = [&](size_t woff, int ot, int J, int p) {
-      return [=](int row, int kl) -> int32_t {
-        const int r = 16 * ot + row, g = kl / 8, j = kl % 8;
-        if (r >= J) return -1;
-        const int feat = 128 * w + 16 * (2 * p + (j >= 4 ? 1 : 0)) + 4 * g + (j & 3);
-        return (int32_t)(woff + (size_t)r * MZ_F + feat);
-      };
-    };
-    const size_t d1w[2] = {L.rew_w1, L.tr_w1}, d1b[2] = {L.rew_b1, L.tr_b1};
-    const size_t p1w[2] = {L.val_w1, L.pol_w1}, p1b[2] = {L.val_b1, L.pol_b1};
-    for (int tg = 0; tg < 4; ++tg)
-      for (int c = 0; c < 2; ++c) {
-        const std::function<int32_t(int, int)> u[4] = {fc1_unit(4 * tg, c, d1w, d1b, MZ_H + A), fc1_unit(4 * tg + 1, c, d1w, d1b, MZ_H + A),
-                                                         fc1_unit(4 * tg + 2, c, d1w, d1b, MZ_H + A), fc1_unit(4 * tg + 3, c, d1w, d1b, MZ_H + A)};
-        emit(u);
-      }
-    for (int half = 0; half < 2; ++half) {
-      for (int sub = 0; sub < 2; ++sub) {
-        const int p = 2 * half + sub;
-        const std::function<int32_t(int, int)> u[4] = {fc2_unit(L.rew_w2, 0, Sr, p), fc2_unit(L.rew_w2, 1, Sr, p),
-                                                         fc2_unit(L.tr_w2, 0, MZ_H, p), fc2_unit(L.tr_w2, 1, MZ_H, p)};
-        emit(u);
-      }
-      const std::function<int32_t(int, int)> u[4] = {fc2_unit(L.tr_w2, 2, MZ_H, 2 * half), fc2_unit(L.tr_w2, 3, MZ_H, 2 * half),
-                                                       fc2_unit(L.tr_w2, 2, MZ_H, 2 * half + 1), fc2_unit(L.tr_w2, 3, MZ_H, 2 * half + 1)};
-      emit(u);
-    }
-    for (int tg = 0; tg < 4; ++tg)
-      for (int c = 0; c < 2; ++c) {
-        const std::function<int32_t(int, int)> u[4] = {fc1_unit(4 * tg, c, p1w, p1b, MZ_H), fc1_unit(4 * tg + 1, c, p1w, p1b, MZ_H),
-                                                         fc1_unit(4 * tg + 2, c, p1w, p1b, MZ_H), fc1_unit(4 * tg + 3, c, p1w, p1b, MZ_H)};
-        emit(u);
-      }
-    for (int k = 0; k < 2; ++k) {
-      const std::function<int32_t(int, int)> u[4] = {fc2_unit(L.val_w2, 0, Sv, 2 * k), fc2_unit(L.val_w2, 1, Sv, 2 * k),
-                                                       fc2_unit(L.val_w2, 0, Sv, 2 * k + 1), fc2_unit(L.val_w2, 1, Sv, 2 * k + 1)};
-      emit(u);
-    }
-    {
-      const std::function<int32_t(int, int)> u[4] = {fc2_unit(L.pol_w2, 0, A, 0), fc2_unit(L.pol_w2, 0, A, 1),
-                                                       fc2_unit(L.pol_w2, 0, A, 2), fc2_unit(L.pol_w2, 0, A, 3)};
-      emit(u);
-    }
-    if ((int)group != SC::REAL) return fail("internal: split-f16 stream has %zu groups, expected %d", group, SC::REAL);
-  }
-  if (dmalloc(e, &e->pack_idx_h2, e->n_packed_h2)) return -1;
-  if (dmalloc(e, &e->packed_h2, e->n_packed_h2)) return -1;
-  HIPCHECK(hipMemcpy(e->pack_idx_h2, idx.data(), e->n_packed_h2 * sizeof(int32_t), hipMemcpyHostToDevice));
-  return 0;
+// the shape an engine's tables are built for
+static PackShape pack_shape(const mz_config &cfg, const SearchShape &row, bool split_f16) {
+  const int Sv = cfg.no_support ? 1 : cfg.value_support_max - cfg.value_support_min + 1;   // networks.py:135-136
+  const int Sr = cfg.no_support ? 1 : cfg.reward_support_max - cfg.reward_support_min + 1;
+  return PackShape{cfg.obs_dim, cfg.action_space, Sv, Sr, row.ks1, row.jtp, row.g, split_f16};
 }
 
 static int build_packing(mz_engine *e) {
-  const int O = e->O, A = e->A;
-  const int Sv = e->cfg.no_support ? 1 : e->cfg.value_support_max - e->cfg.value_support_min + 1;   // networks.py:135-136
-  const int Sr = e->cfg.no_support ? 1 : e->cfg.reward_support_max - e->cfg.reward_support_min + 1;
-  const FlatLayout L = flat_layout(O, A, Sv, Sr);
-  e->layout = L;
-  e->n_flat = L.total;
-  const int ks0 = (O + 3) / 4, ks1 = (MZ_H + A + 3) / 4, ks3 = (MZ_H + 3) / 4;
-  const int jtp = e->jtp;
-  size_t pos = 0;
-  auto seg = [&](size_t n) { size_t p = pos; pos += (n + 3) & ~(size_t)3; return p; };
-  const size_t p_w0o = seg(4 * 4 * 8 * 256), p_b0o = seg(64);
-  const size_t p_w1 = seg((size_t)4 * 4 * ks1 * 256), p_b1 = seg(4 * 16 * 256), p_w2 = seg(6 * 4 * 8 * 256), p_b2 = seg(96);
-  const size_t p_w3 = seg((size_t)4 * 4 * ks3 * 256), p_b3 = seg(4 * 16 * 256);
-  const size_t p_w4 = seg((size_t)(2 + jtp) * 4 * 8 * 256), p_b4 = seg(32 + 16 * jtp);
-  const size_t p_lnw = seg(64), p_lnb = seg(64);
-  // fused kernel: fc1 weights with the bias inside the packed matrix -- prediction: one more input column (constant-1
-  // input); dynamics: added to the one-hot columns (fill_fc1_foldbias); the k-step count is that of the kernel
-  // instantiation chosen for this action count (zero-padded above 50+A)
-  // (rows with an action table: K = 50, 13 k-steps; the one-hot columns + bias are the table behind each wave's stream)
-  const bool atab = mz_fused_atab(e->shape->ks1, e->shape->jtp, e->shape->g);
-  const int ks1f = atab ? (MZ_H + 3) / 4 : e->shape->ks1, ks3f = (MZ_H + 1 + 3) / 4;
-  const size_t p_w1f = seg((size_t)4 * 4 * ks1f * 256), p_w3f = seg((size_t)4 * 4 * ks3f * 256);
-  const int nj2 = 2 + jtp;
-  const int real_steps = ks1f + 12 + ks3f + 2 * nj2;
-  const int rs = mz_fused_rs(e->shape->ks1, jtp);
-  const int nsteps = rs + (real_steps - rs + MZ_NB - 1) / MZ_NB * MZ_NB;   // FusedSched::NSTEPS
-  const size_t wstride = (size_t)nsteps * 4 * 256 + (atab ? MZ_ATAB_WAVE_FLOATS : 0);      // floats per wave
-  const size_t p_ws = seg(4 * wstride);
-  // A operands of the small MFMA (mz_fused.hip.h): rows 48..51 of the next hidden state; the policy head when A <= 4
-  const size_t p_h4 = seg((size_t)4 * 8 * 256), p_p4 = seg((size_t)4 * 8 * 256);
-  const bool p4 = A <= 4;
-  // root kernel stream: [nst0 first-stage steps][8 representation-out][13 prediction fc1][2*nj2 prediction out]
-  const int nst0 = mz_root_nst0(O), nroot = nst0 + 8 + ks3f + 2 * nj2;
-  const size_t p_is = seg((size_t)4 * nroot * 4 * 256);
-  e->n_packed = pos;
-  std::vector<int32_t> idx(pos, -1);
-  std::vector<int32_t> idx2(pos, -1);      // second source element, added to the first (the folded bias of fill_fc1_foldbias)
-  {
-    fill_fc2(idx, p_w0o, 4, L.rep_w2, MZ_H);
-    fill_vec(idx, p_b0o, 64, L.rep_b2, MZ_H);
-  }
-  {
-    size_t wo[2] = {L.rew_w1, L.tr_w1}, bo[2] = {L.rew_b1, L.tr_b1};
-    fill_fc1(idx, p_w1, p_b1, 2, wo, bo, MZ_H + A, ks1);
-    fill_fc2(idx, p_w2, 2, L.rew_w2, Sr);
-    fill_fc2(idx, p_w2 + (size_t)2 * 4 * 8 * 256, 4, L.tr_w2, MZ_H);
-    fill_vec(idx, p_b2, 32, L.rew_b2, Sr);
-    fill_vec(idx, p_b2 + 32, 64, L.tr_b2, MZ_H);
-  }
-  {
-    size_t wo[2] = {L.val_w1, L.pol_w1}, bo[2] = {L.val_b1, L.pol_b1};
-    fill_fc1(idx, p_w3, p_b3, 2, wo, bo, MZ_H, ks3);
-    fill_fc2(idx, p_w4, 2, L.val_w2, Sv);
-    fill_fc2(idx, p_w4 + (size_t)2 * 4 * 8 * 256, jtp, L.pol_w2, A);
-    fill_vec(idx, p_b4, 32, L.val_b2, Sv);
-    fill_vec(idx, p_b4 + 32, 16 * jtp, L.pol_b2, A);
-  }
-  fill_vec(idx, p_lnw, 64, L.ln_w, MZ_H);
-  fill_vec(idx, p_lnb, 64, L.ln_b, MZ_H);
-  {
-    size_t wo[2] = {L.rew_w1, L.tr_w1}, bo[2] = {L.rew_b1, L.tr_b1};
-    fill_fc1_foldbias(idx, idx2, p_w1f, wo, bo, MZ_H + A, ks1f, atab ? MZ_H : MZ_H + A);
-    size_t wo3[2] = {L.val_w1, L.pol_w1}, bo3[2] = {L.val_b1, L.pol_b1};
-    fill_fc1_biascol(idx, p_w3f, wo3, bo3, MZ_H, ks3f);
-  }
-  // small-MFMA pieces, [wave][t][lane][r]: lane l carries output row l & 3 for the features 128w + 16t + 4(l >> 4) + r
-  for (int w = 0; w < 4; ++w)
-    for (int t = 0; t < 8; ++t)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int r = 0; r < 4; ++r) {
-          const int row = lane & 3, nf = 128 * w + 16 * t + 4 * (lane >> 4) + r;
-          const size_t o = ((size_t)(w * 8 + t) * 64 + lane) * 4 + r;
-          idx[p_h4 + o] = 48 + row < MZ_H ? (int32_t)(L.tr_w2 + (size_t)(48 + row) * MZ_F + nf) : -1;
-          idx[p_p4 + o] = row < A ? (int32_t)(L.pol_w2 + (size_t)row * MZ_F + nf) : -1;
-        }
-  // the fused kernel's weight stream: per wave [nsteps][4 pieces][64 lanes][4], consumption order
-  for (int w = 0; w < 4; ++w) {
-    size_t piece = 0;
-    // cls: the scale class of the piece (bits 29-30 of its gather indices, k_pack_weights): 1 = an fc1 layer of the
-    // search (times 2^-k), 2 = a layer that consumes its activations (times 2^k) -- k_relu_scale, mz_fused.hip.h
-    auto put = [&](size_t src, int cls) {
-      const size_t d0 = p_ws + (size_t)w * wstride + piece * 256;
-      for (int i = 0; i < 256; ++i) {
-        idx[d0 + i] = idx[src + i] < 0 ? -1 : (idx[src + i] | (cls << 29));
-        idx2[d0 + i] = idx2[src + i];
-      }
-      ++piece;
-    };
-    for (int st = 0; st < ks1f; ++st)
-      for (int tg = 0; tg < 4; ++tg) put(p_w1f + ((size_t)(w * 4 + tg) * ks1f + st) * 256, 1);
-    for (int t = 0; t < 8; ++t)
-      for (int jt = 0; jt < 6; ++jt) put(jt == 5 ? p_h4 + (size_t)(w * 8 + t) * 256 : p_w2 + ((size_t)(jt * 4 + w) * 8 + t) * 256, 2);
-    for (int st = 0; st < ks3f; ++st)
-      for (int tg = 0; tg < 4; ++tg) put(p_w3f + ((size_t)(w * 4 + tg) * ks3f + st) * 256, 1);
-    for (int t = 0; t < 8; ++t)
-      for (int jt = 0; jt < nj2; ++jt)
-        put(p4 && jt == 2 ? p_p4 + (size_t)(w * 8 + t) * 256 : p_w4 + ((size_t)(jt * 4 + w) * 8 + t) * 256, 2);
-    if ((int)piece != real_steps * 4) return fail("internal: weight stream has %zu pieces, expected %d", piece, real_steps * 4);
-    // the remaining (nsteps - real_steps) * 4 pieces are padding (index -1 -> 0.0), loaded but never used
-    if (atab) {
-      size_t wo[2] = {L.rew_w1, L.tr_w1}, bo[2] = {L.rew_b1, L.tr_b1};
-      fill_action_table(idx, idx2, p_ws + (size_t)w * wstride + (size_t)nsteps * 4 * 256, w, wo, bo, MZ_H + A, A);
-    }
-  }
-
-  // the root kernel's stream (mz_root.hip.h).  First stage, wave w, step st, piece p: k-step 2*st + (p>>1),
-  // tiles 4*(p&1)..+3 of the wave's 8 (features 128w + 16*tile + (lane&15)), k = 4*kstep + (lane>>4); column O
-  // carries the bias.
-  for (int w = 0; w < 4; ++w) {
-    const size_t base = p_is + (size_t)w * nroot * 4 * 256;
-    for (int st = 0; st < nst0; ++st)
-      for (int p = 0; p < 4; ++p)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int i = 0; i < 4; ++i) {
-            const int tile = 4 * (p & 1) + i, nf = 128 * w + 16 * tile + (lane & 15);
-            const int k = 4 * (2 * st + (p >> 1)) + (lane >> 4);
-            int32_t v = -1;
-            if (k < O) v = (int32_t)(L.rep_w1 + (size_t)nf * O + k);
-            else if (k == O) v = (int32_t)(L.rep_b1 + nf);
-            idx[base + ((size_t)(st * 4 + p) * 64 + lane) * 4 + i] = v;
-          }
-    size_t piece = (size_t)nst0 * 4;
-    // (the root's prediction stage shares the search's scaled layers: its v_max ReLU is scale-blind; the representation
-    // layers take raw observations, for which no bound exists: unscaled)
-    auto put = [&](size_t src, int cls) {
-      int32_t *dst = &idx[base + piece * 256];
-      for (int i = 0; i < 256; ++i) dst[i] = idx[src + i] < 0 ? -1 : (idx[src + i] | (cls << 29));
-      ++piece;
-    };
-    for (int t = 0; t < 8; ++t)
-      for (int jt = 0; jt < 4; ++jt) put(p_w0o + ((size_t)(jt * 4 + w) * 8 + t) * 256, 0);
-    for (int st = 0; st < ks3f; ++st)
-      for (int tg = 0; tg < 4; ++tg) put(p_w3f + ((size_t)(w * 4 + tg) * ks3f + st) * 256, 1);
-    for (int t = 0; t < 8; ++t)
-      for (int jt = 0; jt < nj2; ++jt) put(p_w4 + ((size_t)(jt * 4 + w) * 8 + t) * 256, 2);
-    if ((int)piece != nroot * 4) return fail("internal: root stream has %zu pieces, expected %d", piece, nroot * 4);
-  }
-
-  if (L.total >= ((size_t)1 << 29)) return fail("internal: %zu weights do not fit the gather index", L.total);
-  if (dmalloc(e, &e->pack_idx, pos)) return -1;
-  if (dmalloc(e, &e->pack_idx2, pos)) return -1;
-  if (dmalloc(e, &e->packed, pos)) return -1;
+  const PackShape sh = pack_shape(e->cfg, *e->shape, e->split_f16);
+  PackPlan p;
+  std::string err;
+  if (pack_plan(sh, p, err)) return fail("%s", err.c_str());
+  e->layout = p.L;
+  e->n_flat = p.L.total;
+  e->n_packed = p.n_packed;
+  e->n_packed_h2 = p.n_packed_h2;
+  if (dmalloc(e, &e->pack_idx, p.n_packed)) return -1;
+  if (dmalloc(e, &e->pack_idx2, p.n_packed)) return -1;
+  if (dmalloc(e, &e->packed, p.n_packed)) return -1;
   if (dmalloc(e, &e->relu_scale_dev, (size_t)4)) return -1;
   if (dmalloc(e, &e->relu_bound_dev, (size_t)2)) return -1;
-  if (dmalloc(e, &e->flat_dev, L.total)) return -1;
-  HIPCHECK(hipMemcpy(e->pack_idx, idx.data(), pos * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIPCHECK(hipMemcpy(e->pack_idx2, idx2.data(), pos * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (dmalloc(e, &e->flat_dev, p.L.total)) return -1;
+  HIPCHECK(hipMemcpy(e->pack_idx, p.idx.data(), p.n_packed * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(e->pack_idx2, p.idx2.data(), p.n_packed * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (e->split_f16) {
+    if (dmalloc(e, &e->pack_idx_h2, p.n_packed_h2)) return -1;
+    if (dmalloc(e, &e->packed_h2, p.n_packed_h2)) return -1;
+    HIPCHECK(hipMemcpy(e->pack_idx_h2, p.idx_h2.data(), p.n_packed_h2 * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
   NetView &n = e->nv;
   const float *P = e->packed;
-  n.w0o = (const f32x4 *)(P + p_w0o); n.b0o = P + p_b0o;
-  n.w1 = (const f32x4 *)(P + p_w1); n.b1 = (const f32x4 *)(P + p_b1); n.w2 = (const f32x4 *)(P + p_w2); n.b2 = P + p_b2;
-  n.w3 = (const f32x4 *)(P + p_w3); n.b3 = (const f32x4 *)(P + p_b3); n.w4 = (const f32x4 *)(P + p_w4); n.b4 = P + p_b4;
-  n.lnw = P + p_lnw; n.lnb = P + p_lnb;
-  e->wstream = (const f32x4 *)(P + p_ws);
-  e->istream = (const f32x4 *)(P + p_is);
-  e->nst0 = nst0;
-  n.ks0 = ks0; n.ks1 = ks1; n.ks3 = ks3; n.O = O; n.A = A; n.jtp = jtp;
-  n.Sr = Sr; n.Sv = Sv;
+  n.w0o = (const f32x4 *)(P + p.w0o); n.b0o = P + p.b0o;
+  n.w1 = (const f32x4 *)(P + p.w1); n.b1 = (const f32x4 *)(P + p.b1); n.w2 = (const f32x4 *)(P + p.w2); n.b2 = P + p.b2;
+  n.w3 = (const f32x4 *)(P + p.w3); n.b3 = (const f32x4 *)(P + p.b3); n.w4 = (const f32x4 *)(P + p.w4); n.b4 = P + p.b4;
+  n.lnw = P + p.lnw; n.lnb = P + p.lnb;
+  e->wstream = (const f32x4 *)(P + p.ws);
+  e->istream = (const f32x4 *)(P + p.is);
+  e->nst0 = p.nst0;
+  n.ks0 = p.ks0; n.ks1 = p.ks1; n.ks3 = p.ks3; n.O = sh.O; n.A = sh.A; n.jtp = sh.jtp;
+  n.Sr = sh.Sr; n.Sv = sh.Sv;
   n.rmin = e->cfg.no_support ? 0 : e->cfg.reward_support_min;   // (0: mz_support_to_scalar_q adds the raw output to it)
   n.vmin = e->cfg.no_support ? 0 : e->cfg.value_support_min;
   n.no_transform = e->cfg.no_support ? 2 : (e->cfg.no_target_transform ? 1 : 0);
-  if (e->split_f16 && build_packing_h2(e, L, Sv, Sr)) return -1;
+  return 0;
+}
+
+// What every weight set enqueues on s, from the flat weights at src [dev]: the power of two the search kernel's stream is scaled by (its
+// ReLU is a [0, 1] clamp, mz_fused.hip.h) from a bound of this weight set's activations, then the packed vector and, for a split-f16
+// engine, its stream.  force: k_relu_scale's (< 0 the device decides, 0 / 1 the caller has)
+static int enqueue_pack(mz_engine *e, const float *src, int force, hipStream_t s) {
+  const int threads = 256;
+  const unsigned blocks = (unsigned)((e->n_packed + threads - 1) / threads);
+  HIPCHECK(hipMemsetAsync(e->relu_bound_dev, 0, 2 * sizeof(unsigned), s));
+  hipLaunchKernelGGL(k_relu_bound, dim3(64), dim3(256), 0, s, src, e->layout, e->A, e->nv.Sr, e->nv.Sv, e->relu_bound_dev);
+  hipLaunchKernelGGL(k_relu_scale, dim3(1), dim3(1), 0, s, (const unsigned *)e->relu_bound_dev, e->relu_scale_dev, force);
+  hipLaunchKernelGGL(k_pack_weights, dim3(blocks), dim3(threads), 0, s, src, e->pack_idx, (const int32_t *)e->pack_idx2,
+                     e->packed, e->n_packed, (const float *)e->relu_scale_dev);
+  if (e->split_f16)
+    hipLaunchKernelGGL(k_pack_weights_h2, dim3((unsigned)((e->n_packed_h2 + threads - 1) / threads)), dim3(threads), 0, s, src,
+                       e->pack_idx_h2, (_Float16 *)e->packed_h2, e->n_packed_h2);
+  HIPCHECK(hipGetLastError());
   return 0;
 }
 
@@ -1110,8 +807,6 @@ int mz_set_weights(mz_engine *e, const float *flat, size_t n, int on_device, voi
     HIPCHECK(hipMemcpyAsync(e->flat_dev, flat, n * sizeof(float), hipMemcpyHostToDevice, s));
     src = e->flat_dev;
   }
-  const int threads = 256;
-  const unsigned blocks = (unsigned)((e->n_packed + threads - 1) / threads);
   if (e->split_f16) {
     // the high part of a split weight is its float16 rounding: beyond the float16 range it would be inf and poison every
     // search silently.  Checked here, loudly (one small reduction + a 4-byte read back; split_f16 is opt-in).
@@ -1127,19 +822,10 @@ int mz_set_weights(mz_engine *e, const float *flat, size_t n, int on_device, voi
       return fail("mz_set_weights: split_f16 needs every weight finite and |w| <= 65504 (the float16 range of the high part); "
                   "max |w| = %g.  Use the exact-float32 kernel (split_f16 = 0) for these weights", (double)mx);
   }
-  // the power of two the search kernel's stream is scaled by (its ReLU is a [0, 1] clamp, mz_fused.hip.h), from a bound of
-  // this weight set's activations; a 16-byte read back tells the host whether one exists -- if not, the engine runs
-  // the stand-alone kernels until the next weight set
-  HIPCHECK(hipMemsetAsync(e->relu_bound_dev, 0, 2 * sizeof(unsigned), s));
-  hipLaunchKernelGGL(k_relu_bound, dim3(64), dim3(256), 0, s, src, e->layout, e->A, e->nv.Sr, e->nv.Sv, e->relu_bound_dev);
-  hipLaunchKernelGGL(k_relu_scale, dim3(1), dim3(1), 0, s, (const unsigned *)e->relu_bound_dev, e->relu_scale_dev, -1);
-  hipLaunchKernelGGL(k_pack_weights, dim3(blocks), dim3(threads), 0, s, src, e->pack_idx, (const int32_t *)e->pack_idx2,
-                     e->packed, e->n_packed, (const float *)e->relu_scale_dev);
+  // the device decides whether a scale exists; a 16-byte read back tells the host -- if not, the engine runs the stand-alone kernels
+  // until the next weight set
+  if (enqueue_pack(e, src, -1, s)) return -1;
   HIPCHECK(hipMemcpyAsync(e->relu_scale_host, e->relu_scale_dev, 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (e->split_f16)
-    hipLaunchKernelGGL(k_pack_weights_h2, dim3((unsigned)((e->n_packed_h2 + threads - 1) / threads)), dim3(threads), 0, s, src,
-                       e->pack_idx_h2, (_Float16 *)e->packed_h2, e->n_packed_h2);
-  HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(s));     // (also: a host buffer may be freed by the caller)
   const bool scaled = e->relu_scale_host[3] != 0.f;
   if (scaled != e->stream_scaled) drop_graphs(e, true);      // captured graphs hold the launches of the other kernel set
@@ -1214,14 +900,7 @@ int mz_set_weights_async(mz_engine *e, const float *flat, size_t n, int on_devic
     HIPCHECK(hipEventRecord(e->wstage_ev[w], s));
     src = e->flat_dev;
   }
-  const int threads = 256;
-  const unsigned blocks = (unsigned)((e->n_packed + threads - 1) / threads);
-  HIPCHECK(hipMemsetAsync(e->relu_bound_dev, 0, 2 * sizeof(unsigned), s));
-  hipLaunchKernelGGL(k_relu_bound, dim3(64), dim3(256), 0, s, src, e->layout, e->A, e->nv.Sr, e->nv.Sv, e->relu_bound_dev);
-  hipLaunchKernelGGL(k_relu_scale, dim3(1), dim3(1), 0, s, (const unsigned *)e->relu_bound_dev, e->relu_scale_dev, scale_ok ? 1 : 0);
-  hipLaunchKernelGGL(k_pack_weights, dim3(blocks), dim3(threads), 0, s, src, e->pack_idx, (const int32_t *)e->pack_idx2,
-                     e->packed, e->n_packed, (const float *)e->relu_scale_dev);
-  HIPCHECK(hipGetLastError());
+  if (enqueue_pack(e, src, scale_ok ? 1 : 0, s)) return -1;
   const bool scaled = scale_ok != 0;
   if (scaled != e->stream_scaled) {      // (rare: captured graphs hold the launches of the other kernel set)
     HIPCHECK(hipStreamSynchronize(s));
@@ -1243,6 +922,36 @@ int mz_weight_scale(mz_engine *e, float *out, void *stream) {
     e->scale_host_valid = true;
   }
   memcpy(out, e->relu_scale_host, sizeof(e->relu_scale_host));
+  return 0;
+}
+
+// ---- test hooks of the packing (include/mz_engine_debug.h)
+int mz_pack_host(int obs_dim, int action_space, int value_bins, int reward_bins, int split_f16, long long *out, int which, int32_t *table,
+                 size_t cap) {
+  if (!out || obs_dim < 1 || action_space < 1 || value_bins < 1 || reward_bins < 1 || which < 0 || which > 2 ||
+      (split_f16 && action_space > MZ_H2_MAXA))
+    return fail("mz_pack_host: bad argument");
+  const SearchShape *row = shape_for(g_fused_shapes, action_space);
+  if (!row) return fail("mz_pack_host: bad argument");
+  PackPlan p;
+  std::string err;
+  if (pack_plan(PackShape{obs_dim, action_space, value_bins, reward_bins, row->ks1, row->jtp, row->g, split_f16 != 0}, p, err))
+    return fail("%s", err.c_str());
+  pack_plan_record(p, out);
+  if (!table) return 0;
+  const std::vector<int32_t> &t = which == 0 ? p.idx : (which == 1 ? p.idx2 : p.idx_h2);
+  if (cap < t.size()) return fail("mz_pack_host: table %d has %zu entries, room for %zu", which, t.size(), cap);
+  memcpy(table, t.data(), t.size() * sizeof(int32_t));
+  return 0;
+}
+
+int mz_pack_indices(mz_engine *e, int which, int32_t *out, size_t cap) {
+  if (!e || !out || which < 0 || which > 2) return fail("mz_pack_indices: bad argument");
+  MZ_ENTER(e);
+  const int32_t *t = which == 0 ? e->pack_idx : (which == 1 ? e->pack_idx2 : e->pack_idx_h2);
+  const size_t n = which == 2 ? e->n_packed_h2 : e->n_packed;
+  if (cap < n) return fail("mz_pack_indices: table %d has %zu entries, room for %zu", which, n, cap);
+  if (n) HIPCHECK(hipMemcpy(out, t, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

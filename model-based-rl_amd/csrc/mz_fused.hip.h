@@ -39,58 +39,23 @@ __device__ __forceinline__ void mz_static_for(F &&f) {
   mz_static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-#ifndef MZ_NB
-#define MZ_NB 4      // register ring depth in steps (prefetch distance NB-1 steps = ~1600 cycles; A/B on one box:
-#endif               // 4 buffers + 13 resident steps 406 us, 5 + 12: 410, 3 + 14: 407)
 // s_waitcnt vmcnt(N), nothing else waited for (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8)
 #define MZ_VMCNT(N) (((N) & 15) | (((N) >> 4) << 14) | 0x0F70)
-// steps of the stream held in registers (AGPRs) across all simulations: less L2 traffic and no load issue in those
-// steps (a streamed step runs at ~37 cycles/MFMA, a resident one at 32).  As many as the register file takes
-// without scratch: the wide-action instantiations (two tree passes, two policy tiles) have fewer to spare.
-#ifndef MZ_RS_MAIN
-#define MZ_RS_MAIN 13
-#endif
-__host__ __device__ constexpr int mz_fused_rs(int ks1, int jtp) { return jtp > 1 ? 9 : (ks1 > 16 ? 11 : (ks1 > 14 ? 12 : MZ_RS_MAIN)); }
 #define MZ_XE 36     // row stride of the x-tile extensions (k >= 50): dynamics [one-hot(action) | 0 ...], prediction [1 | 0 ...]
 
-// Action table (the rows of mz_kernels.inc for which mz_fused_atab holds: the A <= 4 row).  For one tree the one-hot
-// columns of the dynamics fc1 contribute nothing but W[n][50 + a] + b[n], a vector chosen by the tree's action: no
-// multiplication is needed for it.  The host packs that vector for every action as the accumulator tiles themselves
-// (T[a][tile 0..15][lane row g][r], per wave: what lane (g, .) of tile t holds), each lane reads its column's vector
-// straight into acc[0..15] before the first k-step, and that step accumulates instead of starting from zero.  The
-// dynamics fc1 is then K = 50: 13 k-steps instead of 14, all of them resident.  The term is the first addend of the
-// sum instead of the last: the same products in another float32 order.
-// -DMZ_ACTION_COLUMNS (development switch, A/B builds): the earlier form, K = 50 + A columns.
-__host__ __device__ constexpr bool mz_fused_atab(int ks1, int jtp, int g) {
-#ifdef MZ_ACTION_COLUMNS
-  return false;
-#else
-  return ks1 == 14 && jtp == 1 && g == 4;
-#endif
-}
-#define MZ_ATAB_AMAX 4                         // actions the packed table has room for (the row's largest action count)
-#define MZ_ATAB_WAVE_FLOATS (MZ_ATAB_AMAX * 256)   // one wave's slice behind its weight stream: [a][16 tiles][4 g][4 r]
-// LDS copy (trees in the pool or whole trees in LDS): [a][wave][256 floats], the action stride padded by 64 bytes so that
-// the four actions x four lane rows of one read cover 256 distinct bytes (lanes with the same action and lane row read
-// the same address: a broadcast).  Beside compact trees (lt = 2) the table stays in global memory.
-#define MZ_ATAB_LDS_STRIDE (4096 + 64)
-__host__ __device__ constexpr size_t mz_fused_atab_lds(bool atab, int A, int lt) {
-  return atab && lt != 2 ? (size_t)A * MZ_ATAB_LDS_STRIDE : 0;
-}
+// (MZ_NB, MZ_RS_MAIN, mz_fused_rs, the action table mz_fused_atab / MZ_ATAB_* and the step counts below: mz_stream_sizes.h)
 
 // per-simulation schedule (in steps of 16 MFMAs per wave)
 template <int KS1, int JTP, bool ATAB = false>
 struct FusedSched {
-  // dynamics fc1: K = 50 + A (the bias rides in the one-hot columns), 4 per step; with the action table K = 50 (KS1
-  // stays the row's label)
-  static constexpr int FC1 = ATAB ? (MZ_H + 3) / 4 : KS1;
-  static constexpr int FC2 = 12;                // reward (2 tiles) + next hidden (4 tiles): 48 pieces
-  static constexpr int P1 = (MZ_H + 1 + 3) / 4; // prediction fc1: K = 51 -> 13 steps
-  static constexpr int P2 = 2 * (2 + JTP);      // value (2 tiles) + policy (JTP tiles)
-  static constexpr int REAL = FC1 + FC2 + P1 + P2;
-  static constexpr int RS = mz_fused_rs(KS1, JTP);            // the first RS steps stay resident in registers for the whole launch
-  static constexpr int NRING = (REAL - RS + MZ_NB - 1) / MZ_NB * MZ_NB;   // streamed steps, padded to the ring depth
-  static constexpr int NSTEPS = RS + NRING;     // schedule length incl. padding steps (prefetch only)
+  static constexpr int FC1 = mz_fused_fc1(KS1, ATAB);              // dynamics fc1
+  static constexpr int FC2 = MZ_FUSED_FC2;                         // reward + next hidden
+  static constexpr int P1 = mz_pred_fc1();                         // prediction fc1
+  static constexpr int P2 = mz_pred_fc2(JTP);                      // value + policy
+  static constexpr int REAL = mz_fused_real(KS1, JTP, ATAB);
+  static constexpr int RS = mz_fused_rs(KS1, JTP);                 // the first RS steps stay resident in registers for the whole launch
+  static constexpr int NRING = mz_fused_nring(KS1, JTP, ATAB);     // streamed steps, padded to the ring depth
+  static constexpr int NSTEPS = mz_fused_nsteps(KS1, JTP, ATAB);   // schedule length incl. padding steps (prefetch only)
 };
 
 // MFMA from inline asm with the accumulator tied in place ("+a").  Left to itself hipcc, in this kernel,

@@ -26,28 +26,8 @@
 #pragma once
 #include "mz_fused.hip.h"
 
-#ifndef MZ_H2_NBG
-#define MZ_H2_NBG 3       // ring depth (groups)
-#endif
-#ifndef MZ_H2_RSG
-#define MZ_H2_RSG 4       // resident groups
-#endif
-// (A/B on one box, us per launch of the headline workload: RSG / NBG = 4 / 3: 269, 1 / 4: 283, 5 / 2: 276 -- both the
-// bytes streamed and the prefetch distance matter.  Resident groups in arch VGPRs (5 / 4 with one of them there) were
-// tried: under the register pressure that creates the compiler moves operands around with VALU copies right in front of
-// the asm MFMAs, whose wait states it cannot know -- wrong results on a full grid; dropped.)
+// (MZ_H2_NBG, MZ_H2_RSG, MZ_H2_MAXA and H2Sched, the groups per stage: mz_stream_sizes.h)
 #define MZ_H2_XS 72       // row stride of the f16 x tiles (halfs): 144 B, rows 36 banks apart
-#define MZ_H2_MAXA 13
-
-struct H2Sched {
-  static constexpr int D1 = 8, D2 = 6, P1 = 8, P2 = 3;                      // groups per stage
-  static constexpr int E_D1 = D1, E_D2 = E_D1 + D2, E_P1 = E_D2 + P1, E_P2 = E_P1 + P2;
-  static constexpr int REAL = E_P2;                                          // 25 groups = 200 KiB per wave and simulation
-  static constexpr int RSG = MZ_H2_RSG, NBG = MZ_H2_NBG;
-  static constexpr int NRING = (REAL - RSG + NBG - 1) / NBG * NBG;
-  static constexpr int NGROUPS = RSG + NRING;
-};
-static_assert(H2Sched::NRING == H2Sched::REAL - H2Sched::RSG, "no padding groups: (REAL - RSG) must be a multiple of NBG");
 
 typedef _Float16 mz_h16;
 typedef mz_h16 mz_h16x2 __attribute__((ext_vector_type(2)));

@@ -24,13 +24,11 @@
 
 template <int JTP>
 struct RootSched {
-  static constexpr int R2 = 8;                   // representation out: 4 tiles x this wave's 8 hidden tiles
-  static constexpr int P1 = (MZ_H + 1 + 3) / 4;  // prediction fc1: K = 51 -> 13 steps
-  static constexpr int P2 = 2 * (2 + JTP);       // value (2 tiles) + policy (JTP tiles)
-  static constexpr int NS = R2 + P1 + P2;
+  static constexpr int R2 = MZ_ROOT_R2;          // representation out
+  static constexpr int P1 = mz_pred_fc1();       // prediction fc1
+  static constexpr int P2 = mz_pred_fc2(JTP);    // value + policy
+  static constexpr int NS = mz_root_ns(JTP);     // (the counts, and mz_root_nst0 of the run-time first stage: mz_stream_sizes.h)
 };
-// steps of the run-time first stage: two k-steps of K0 = obs_dim + 1 (bias column) per step
-__host__ __device__ inline int mz_root_nst0(int O) { return ((O + 1 + 3) / 4 + 1) / 2; }
 
 #define MZ_ROOT_LDS_FLOATS (16 * MZ_ROOT_XS + 16 * MZ_HS + 4 * 6 * 256 + 96 * 16 + 16 + 16 * 32 + 64 + 64 + 64 + 64 + 16 * MZ_XE)
 
