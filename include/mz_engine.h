@@ -470,6 +470,20 @@ int mz_gz_expand_backup_select(mz_engine *e, const float *value, const float *re
 int mz_gz_search(mz_engine *e, int num_simulations, void *stream);
 int mz_gz_pick(mz_engine *e, int32_t *action, float *pred_reward, double *improved_policy, double *v_mix, void *stream);
 
+/* Self-play with the Gumbel search (DESIGN s7i; csrc/mz_gumbel_selfplay.hip.h).  While on, a move of mz_selfplay_steps /
+ * mz_selfplay_steps_into on a device game (mz_selfplay_set_env 1, 2, 3) is: observe, initial inference, the root WITHOUT
+ * exploration noise, mz_gz_root with G drawn on the device -- keyed (seed, env_id_offset + b, the environment's move counter,
+ * action): the counter that keys the Dirichlet draw of a PUCT move, so a record does not depend on its batch --, all
+ * num_simulations of mz_gz_search, and one end-of-move launch.  The record keeps its layout: the child_visits slots hold
+ * (float)pi'(a) of the root (exactly 0 on illegal actions), action is the pick of mz_gz_pick, root_value the root's mean value
+ * (value_kind 0) or its v_mix (value_kind 1), error = root_value - the initial inference's value.  The visit-softmax
+ * temperature plays no part; exploration comes from mz_set_gumbel's gumbel_scale (1 for training).
+ * The moves run in the launch-per-step form, up to 16 per hipGraph: mz_selfplay_moves_per_launch returns 0 while on.
+ * Needs mz_set_gumbel on this engine and a game environment; refused with host-given draws (mz_selfplay_set_draws), with an
+ * mz_sim_io mode, and while moves wait in the device ring.  While on, mz_set_gumbel(e, 0, ..), mz_selfplay_set_draws,
+ * mz_selfplay_set_env, mz_sim_io modes and mz_selfplay_steps_timed are refused.  on 0: the loop runs again as it did before. */
+int mz_selfplay_set_gumbel(mz_engine *e, int on, int value_kind);
+
 /* MuZero Reanalyse: stored positions of the replay searched again under the engine's CURRENT weights.  rows_host [host, pinned]
  * is [n_rows][rec_floats] record rows as mzr_reanalyse_pick (include/mz_replay.h) wrote them, rec_floats = obs_dim + action_space
  * + MZ_REC_EXTRA; fresh_host [host, pinned] receives [n_rows][action_space + 2] floats per row: child_visits as float32 (the

@@ -150,6 +150,18 @@ def build_parser():
          'root_value rewritten in place (reanalyse.py); 0: off')
   a('--reanalyse_every', type=int, default=None,
     help='learner steps between Reanalyse passes (default: --weight_sync_frequency); a pass follows the first weight pull past each multiple')
+  a('--selfplay_gumbel', action='store_true',
+    help='TicTacToe / ConnectFour / CartPole-v0 / -v1 on the device: the self-play moves are searched with the Gumbel MuZero '
+         'search at --num_simulations (8 or 16 are its range), the records carry the improved policy pi\' as the policy target and '
+         'the Gumbel pick as the action; the visit-softmax temperature plays no part (selfplay_gumbel.py; evaluation keeps its '
+         'own --gumbel flags)')
+  a('--selfplay_gumbel_considered', type=int, default=16, help='--selfplay_gumbel: the actions sequential halving starts from (at least 2)')
+  a('--selfplay_gumbel_c_visit', type=float, default=50.0, help='--selfplay_gumbel: sigma = (c_visit + max visits) * c_scale * normalised Q')
+  a('--selfplay_gumbel_c_scale', type=float, default=1.0, help='--selfplay_gumbel: see --selfplay_gumbel_c_visit')
+  a('--selfplay_gumbel_scale', type=float, default=1.0,
+    help='--selfplay_gumbel: the scale of the Gumbel noise at the root, the exploration of this mode; 1 is the training setting of the paper')
+  a('--selfplay_gumbel_value', type=str, default='mean', choices=['mean', 'vmix'],
+    help='--selfplay_gumbel: what a record stores as the root value, the n-step targets\' bootstrap: the root\'s mean value, or its v_mix')
   a('--symmetry', action='store_true',
     help='TicTacToe / ConnectFour: train every sample of a batch on one of the equivalent images of its position (8 rotations and '
          'mirrors / the left-right mirror), drawn per (seed, update, sample); observation, unrolled actions and policy targets move '

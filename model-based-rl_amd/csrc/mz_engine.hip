@@ -44,6 +44,7 @@
 #include "mz_symmetry.hip.h"
 #include "mz_truemodel.hip.h"
 #include "mz_gumbel.hip.h"
+#include "mz_gumbel_selfplay.hip.h"
 // the search kernels are compiled in their own translation units, one per shape (mz_inst.hip); here they are declared,
 // tabled and launched -- all three from the lists of mz_kernels.inc
 #include "mz_kernels.inc"
@@ -172,6 +173,8 @@ struct mz_engine {
   TmState tm = {};                  // the true-rules search (mz_set_true_model, mz_tm_*; mz_truemodel.hip.h), allocated when set
   GzState gz = {};                  // the Gumbel search (mz_set_gumbel, mz_gz_*; mz_gumbel.hip.h), allocated when set
   bool root_noise = false;          // the last mz_root_prepare mixed exploration noise into the root's priors
+  bool sp_gumbel = false;           // the self-play loop's moves are searched with the Gumbel search (mz_selfplay_set_gumbel; DESIGN s7i)
+  int sp_gumbel_value = 0;          // ... and their records' root_value: 0 the root's mean value, 1 its v_mix
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -511,8 +514,9 @@ static SearchPlan search_plan(const mz_engine *e) {
   // environment on the exact-f32 game kernel (host-given uniforms / draws work there too), or the device CartPole
   // environment on the single-player game kernel, or the device Connect Four environment on its two game kernels (whole
   // trees, compact placement); a game environment without such an instantiation for its shape and
-  // placement, or with split_f16, plays in the launch-per-step form (launch_move_game)
-  p.persist = e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
+  // placement, or with split_f16, plays in the launch-per-step form (launch_move_game), and so does every move searched with
+  // the Gumbel search (mz_selfplay_set_gumbel)
+  p.persist = !e->sp_gumbel && e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
               (p.game ? !e->split_f16 && !!e->cfg.two_players == (p.game != 2) &&
                             find_kernel(1, *p.shape, p.lt, false, p.sp, true, true) != nullptr
                       : p.sp && !e->sp.env_kind);

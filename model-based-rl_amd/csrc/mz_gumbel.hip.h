@@ -238,12 +238,15 @@ __device__ __forceinline__ void mz_gz_select(const TreeView &t, const GzState &g
 // ------------------------------------------------------------------ kernels
 // k_gz_root (after k_tree_root without noise): v^ of slot 0 = the initial inference's root value; G = the caller's
 // (given), or -log(-log u) with u from the counter RNG keyed (env, move, action) -- a game's draws do not depend on its
-// batch --, or 0 with gumbel_scale 0 (nothing is drawn); then the first descent, by the root rule.
+// batch --, or 0 with gumbel_scale 0 (nothing is drawn); then the first descent, by the root rule.  The move is move_val, or
+// -- the self-play loop, whose captured graphs must draw afresh at every replay -- what move_ptr points to (as k_dirichlet).
 template <int G>
-__global__ void k_gz_root(TreeView t, GzState gz, const double *given, uint64_t seed, uint64_t move, int env_offset) {
+__global__ void k_gz_root(TreeView t, GzState gz, const double *given, uint64_t seed, uint64_t move_val,
+                          const unsigned long long *move_ptr, int env_offset) {
   const int gt = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = gt / G, lane = gt % G;
   if (b >= t.B) return;
+  const uint64_t move = move_ptr ? (uint64_t)*move_ptr : move_val;
   if (lane < t.A) {
     double g = 0.0;
     if (gz.par.gumbel_scale != 0.0) {
@@ -294,6 +297,29 @@ __global__ void k_gz_step(TreeView t, GzState gz, const float *value, const floa
   }
 }
 
+// The end of the move at the root of tree b, by the G lanes of one group (lane = action): the action by the root rule among the
+// most visited (-1: no legal action), this lane's pi'(a) (0 beyond A and on illegal actions), v_mix, and this lane's child's
+// reward.  Shared by k_gz_pick and the self-play loop's end-of-move kernels (mz_gumbel_selfplay.hip.h).
+template <int G>
+__device__ __forceinline__ int mz_gz_root_pick(const TreeView &t, const GzState &gz, int b, int lane, double *pi, double *vmix,
+                                               float *child_reward) {
+  const int A = t.A;
+  const size_t o = mz_slab(t, b);
+  const uint32_t legal = t.legal[b];
+  const bool has = lane < A && ((legal >> lane) & 1u);
+  const double gl = lane < A ? gz.par.gumbel_scale * gz.G[(size_t)b * A + lane] + (double)t.root_logits[(size_t)b * A + lane] : 0.0;
+  double cP = 0.0, cW = 0.0;
+  int cN = 0;
+  float cR = 0.f;
+  if (has) {
+    const MzNode c = mz_node_load(t, o + 1 + lane);
+    cP = c.P; cW = c.W; cN = c.N; cR = c.R;
+  }
+  *child_reward = cR;
+  return mz_gz_node(GzLanes<G>{lane}, A, gz.par, t.two_players, t.discount, t.mn[b], t.mx[b],
+                    (double)gz.vhat[(size_t)b * (size_t)(t.sims + 1)], &has, &cP, &cW, &cN, &cR, true, &gl, -1, pi, vmix);
+}
+
 // The end of the move, one 64-lane workgroup per tree (its 64 / G groups compute the same): the action by the root rule
 // among the most visited, its child's reward, pi' and v_mix of the root -- and what k_eval_walk writes for one action per
 // move: actions, pred_rewards, n_actions = 1 (0: a root without a legal action) and path_lengths (mz_walk_path_lengths).
@@ -308,19 +334,9 @@ __global__ __launch_bounds__(64) void k_gz_pick(TreeView t, GzState gz, int nexp
   const int A = t.A;
   const size_t o = mz_slab(t, b);
   if (path_lengths) mz_walk_path_lengths(t, o, b, wl, nexp, par, path_lengths);
-  const uint32_t legal = t.legal[b];
-  const bool has = lane < A && ((legal >> lane) & 1u);
-  const double gl = lane < A ? gz.par.gumbel_scale * gz.G[(size_t)b * A + lane] + (double)t.root_logits[(size_t)b * A + lane] : 0.0;
-  double cP = 0.0, cW = 0.0, pi, vmix;
-  int cN = 0;
-  float cR = 0.f;
-  if (has) {
-    const MzNode c = mz_node_load(t, o + 1 + lane);
-    cP = c.P; cW = c.W; cN = c.N; cR = c.R;
-  }
-  const int best = mz_gz_node(GzLanes<G>{lane}, A, gz.par, t.two_players, t.discount, t.mn[b], t.mx[b],
-                              (double)gz.vhat[(size_t)b * (size_t)(t.sims + 1)], &has, &cP, &cW, &cN, &cR, true, &gl, -1, &pi,
-                              &vmix);
+  double pi, vmix;
+  float cR;
+  const int best = mz_gz_root_pick<G>(t, gz, b, lane, &pi, &vmix, &cR);
   const float r = __shfl(cR, best < 0 ? 0 : best, G);
   if (wl < A && improved_policy) improved_policy[(size_t)b * A + wl] = pi;
   if (wl == 0) {

@@ -77,7 +77,9 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
 // observe, initial inference on that observation, Dirichlet draw over the legal actions (or the host's draw), root
 // expansion + first descent, the two-player search kernel, end of move with the real env.step -- all on the stream, no
 // host round trip; up to 16 moves per hipGraph like every other configuration.
+static int launch_move_gumbel(mz_engine *e, hipStream_t s);      // (mz_gumbel_abi.inc: the move of mz_selfplay_set_gumbel)
 static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
+  if (e->sp_gumbel) return launch_move_gumbel(e, s);
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
   const bool cart = sp.env_kind == 2, c4 = sp.env_kind == 3;
@@ -200,6 +202,7 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
   if (!e) return fail("mz_selfplay_set_env: null engine");
   MZ_ENTER(e);
   if (kind < 0 || kind > 3) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole, 3 Connect Four)", kind);
+  if (e->sp_gumbel) return fail("mz_selfplay_set_env: the self-play moves are searched with the Gumbel search, set for the current game (mz_selfplay_set_gumbel 0 first)");
   if (kind != 0 && game_shape(e, "mz_selfplay_set_env", kind)) return -1;
   if (kind == 3 && e->sp.obs_u8 == 2)
     return fail("mz_selfplay_set_env: packed byte observations are for the synthetic -ram- environments");
@@ -232,6 +235,7 @@ int mz_selfplay_set_draws(mz_engine *e, const double *noise, const double *unifo
   if (!e) return fail("mz_selfplay_set_draws: null engine");
   MZ_ENTER(e);
   if (e->sp.env_kind != 1) return fail("mz_selfplay_set_draws: only for the TicTacToe environment (mz_selfplay_set_env)");
+  if (e->sp_gumbel) return fail("mz_selfplay_set_draws: the self-play moves are searched with the Gumbel search, which draws its own noise on the device (mz_selfplay_set_gumbel 0 first)");
   hipStream_t s = (hipStream_t)stream;
   if (noise) HIPCHECK(hipMemcpyAsync(e->tv.noise, noise, (size_t)e->B * e->A * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (uniform) HIPCHECK(hipMemcpyAsync(e->draw_uniform, uniform, (size_t)e->B * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -272,6 +276,7 @@ int mz_sim_io(mz_engine *e, int mode, float *buf, int keep_moves) {
   MZ_ENTER(e);
   if (mode < 0 || mode > 2) return fail("mz_sim_io: mode %d (0 off, 1 log, 2 inject)", mode);
   if (mode && (!buf || keep_moves < 1)) return fail("mz_sim_io: a buffer of keep_moves >= 1 moves is required");
+  if (mode && e->sp_gumbel) return fail("mz_sim_io: the self-play moves are searched with the Gumbel search, which the fused kernels do not run (mz_selfplay_set_gumbel 0 first)");
   HIPCHECK(hipDeviceSynchronize());
   e->tv.sim_io = mode ? buf : nullptr;
   e->tv.sim_io_keep = mode == 2 ? -keep_moves : (mode == 1 ? keep_moves : 0);
@@ -424,7 +429,9 @@ int mz_selfplay_steps_timed(mz_engine *e, int k, float *ms_out, void *stream) {
   if (!e || !ms_out) return fail("mz_selfplay_steps_timed: null argument");
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
-  const int brc = produce_begin(e, "mz_selfplay_steps_timed", fused_usable(e) ? nullptr : "fused kernel not in use", k, INT_MAX, true, s);
+  const char *own = e->sp_gumbel ? "the moves are searched with the Gumbel search, which has no single search dispatch to clock" :
+                    fused_usable(e) ? nullptr : "fused kernel not in use";
+  const int brc = produce_begin(e, "mz_selfplay_steps_timed", own, k, INT_MAX, true, s);
   if (brc > 0) return fail("mz_selfplay_steps_timed: %d moves do not fit the undrained ring", k);
   if (brc) return -1;
   // eager launches, back to back, no synchronisation in between, events around every search dispatch; where the loop runs as

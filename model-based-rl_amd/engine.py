@@ -863,6 +863,18 @@ class Engine(object):
     noise = self._dev(noise, torch.float64); uniform = self._dev(uniform, torch.float64)
     _abi.check(self.lib.mz_selfplay_set_draws(self._h, _ptr(noise), _ptr(uniform), self.stream), 'mz_selfplay_set_draws')
 
+  SELFPLAY_GUMBEL_VALUES = {'mean': 0, 'vmix': 1}
+
+  def selfplay_set_gumbel(self, on=True, value='mean'):
+    """mz_selfplay_set_gumbel (DESIGN s7i): while on, the self-play moves of a device game are searched with the Gumbel search
+    (set_gumbel first, with gumbel_scale 1 for training) and their records carry pi' of the root in the policy slots, the
+    Gumbel pick as the action and, as root_value, the root's mean value ('mean') or its v_mix ('vmix').  After
+    selfplay_set_env, with the ring drained."""
+    if value not in self.SELFPLAY_GUMBEL_VALUES:
+      raise ValueError("selfplay_set_gumbel: value is 'mean' or 'vmix', got %r" % (value,))
+    _abi.check(self.lib.mz_selfplay_set_gumbel(self._h, int(bool(on)), self.SELFPLAY_GUMBEL_VALUES[value]), 'mz_selfplay_set_gumbel')
+    self.selfplay_gumbel = bool(on)
+
   def selfplay_export_trees(self, keep=True):
     _abi.check(self.lib.mz_selfplay_export_trees(self._h, int(bool(keep))), 'mz_selfplay_export_trees')
 

@@ -17,6 +17,7 @@ from . import rayshim as ray
 from .actors import Actor
 from .config import build_parser, Config, env_shapes
 from .envs import KIND_OF_ENV
+from .selfplay_gumbel import refuse_selfplay_gumbel
 from .learners import Learner
 from .networks import FCNetwork
 from .replay_buffer import PrioritizedReplay
@@ -327,6 +328,7 @@ def main(argv=None):
   refuse_reanalyse(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))      # (before any rank or device exists)
   from .symmetry import refuse_symmetry
   refuse_symmetry(cfg)                                                        # (--symmetry: likewise)
+  refuse_selfplay_gumbel(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))   # (--selfplay_gumbel: likewise)
   if spawn:                         # `train --ranks N` without a launcher: pre-flight here (one sentence instead of N tracebacks), then the ranks
     _preflight_ranks(ranks, cfg)
     raise SystemExit(_spawn_ranks(ranks, argv))

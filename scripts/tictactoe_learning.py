@@ -7,6 +7,10 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
   python scripts/tictactoe_learning.py [--training_steps 3000] [--num_envs 1024] [--no_support [--scalar_loss Huber]]
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
                                        [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]] [--true_model] [--gumbel]
+                                       [--selfplay_gumbel [--num_simulations 8] [--selfplay_gumbel_value vmix] ...]
+--selfplay_gumbel adds train's flag (self-play searched with the Gumbel search, the learner trained on pi'; selfplay_gumbel.py) with
+its --selfplay_gumbel_* parameters, and --num_simulations sets the simulations of the TRAINING run's self-play; the evaluation
+blocks below stay as they are -- PUCT at 30 simulations unless --gumbel is given.
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --symmetry adds train's flag (every sample trained on one of the equivalent images of its position, symmetry.py) to the training run.
@@ -82,7 +86,7 @@ def play_vs_random_device(config, weights, agent_side, games=512, seed=0, opp_pl
   return int((ret > 0).sum()), int((ret == 0).sum()), int((ret < 0).sum())
 
 
-def main():
+def build_parser():
   ap = argparse.ArgumentParser()
   ap.add_argument('--environment', default='TicTacToe', choices=['TicTacToe', 'ConnectFour'])
   ap.add_argument('--training_steps', type=int, default=3000)
@@ -108,6 +112,43 @@ def main():
   ap.add_argument('--gumbel', action='store_true',
                   help='also play (and with --grade, grade) the 512 games per side with the Gumbel search (evaluate --gumbel, default '
                        'parameters) at the same number of simulations: next to the plain games, what the search rule changes')
+  ap.add_argument('--num_simulations', type=int, default=None,
+                  help='simulations per move of the training run\'s self-play (default: the recipe\'s 30); the evaluation blocks keep 30')
+  ap.add_argument('--selfplay_gumbel', action='store_true',
+                  help='train --selfplay_gumbel: self-play with the Gumbel search, pi\' as the policy target (use with --num_simulations 8 or 16)')
+  ap.add_argument('--selfplay_gumbel_considered', type=int, default=None, help='train --selfplay_gumbel_considered')
+  ap.add_argument('--selfplay_gumbel_c_visit', type=float, default=None, help='train --selfplay_gumbel_c_visit')
+  ap.add_argument('--selfplay_gumbel_c_scale', type=float, default=None, help='train --selfplay_gumbel_c_scale')
+  ap.add_argument('--selfplay_gumbel_scale', type=float, default=None, help='train --selfplay_gumbel_scale')
+  ap.add_argument('--selfplay_gumbel_value', default=None, choices=['mean', 'vmix'], help='train --selfplay_gumbel_value')
+  return ap
+
+
+def recipe(a):
+  """(base, extra) of the parsed arguments: base is the recipe the evaluation blocks build their configs from, base + extra the
+  training run's flags (a flag given again in extra overrides base's)"""
+  base = ['--environment', a.environment, '--two_players', '--architecture', 'FCNetwork', '--td_steps', '10', '--discount', '1',
+          '--known_bounds', '-1', '1', '--num_simulations', '30', '--seed', '0', '--num_envs', str(a.num_envs)]
+  if a.no_support:
+    base += ['--no_support', '--scalar_loss', a.scalar_loss]
+  extra = ['--reanalyse_rows', str(a.reanalyse_rows)] if a.reanalyse_rows else []
+  if a.reanalyse_rows and a.reanalyse_every:
+    extra += ['--reanalyse_every', str(a.reanalyse_every)]
+  if a.symmetry:
+    extra += ['--symmetry']
+  if a.num_simulations is not None:
+    extra += ['--num_simulations', str(a.num_simulations)]
+  if a.selfplay_gumbel:
+    extra += ['--selfplay_gumbel']
+    for k in ('considered', 'c_visit', 'c_scale', 'scale', 'value'):
+      v = getattr(a, 'selfplay_gumbel_' + k)
+      if v is not None:
+        extra += ['--selfplay_gumbel_' + k, str(v)]
+  return base, extra
+
+
+def main():
+  ap = build_parser()
   a = ap.parse_args()
   if a.grade_table and not a.grade:
     ap.error('--grade_table: it chooses the search that --grade solves with and grades nothing without --grade.')
@@ -119,15 +160,9 @@ def main():
   from model_based_rl_amd.config import make_config
   from model_based_rl_amd.networks import get_network
   from model_based_rl_amd.engine import flatten_weights
-  base = ['--environment', a.environment, '--two_players', '--architecture', 'FCNetwork', '--td_steps', '10', '--discount', '1',
-          '--known_bounds', '-1', '1', '--num_simulations', '30', '--seed', '0', '--num_envs', str(a.num_envs)]
-  if a.no_support:
-    base += ['--no_support', '--scalar_loss', a.scalar_loss]
-  extra = ['--reanalyse_rows', str(a.reanalyse_rows)] if a.reanalyse_rows else []
-  if a.reanalyse_rows and a.reanalyse_every:
-    extra += ['--reanalyse_every', str(a.reanalyse_every)]
-  if a.symmetry:
-    extra += ['--symmetry']
+  if not a.selfplay_gumbel and any(getattr(a, 'selfplay_gumbel_' + k) is not None for k in ('considered', 'c_visit', 'c_scale', 'scale', 'value')):
+    ap.error('--selfplay_gumbel_*: parameters of --selfplay_gumbel, which is not given.')
+  base, extra = recipe(a)
   torch.manual_seed(0)
   untrained_sd = get_network(make_config(base), torch.device('cpu')).state_dict()
   if a.environment == 'TicTacToe':
