@@ -501,6 +501,20 @@ int mz_selfplay_set_gumbel(mz_engine *e, int on, int value_kind);
 int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
                  int num_simulations, void *stream);
 
+/* Reanalyse with the Gumbel search (DESIGN s7j), for a replay whose records come from mz_selfplay_set_gumbel: mz_reanalyse's
+ * buffers, layouts, pinned-memory requirement, kinds and chunks, but each chunk is searched as a self-play move of that mode is
+ * -- observe, mz_initial_inference, the root WITHOUT noise (and without the first PUCT descent), the Gumbel root, the
+ * mz_gz_search loop for num_simulations -- and fresh_host receives per row the root's improved policy pi' as float32 (exactly 0
+ * at illegal actions) where mz_reanalyse puts the visit shares, then a float64 in two float slots: the root's mean value
+ * (value_kind 0) or its v_mix (value_kind 1), the rule of mz_selfplay_set_gumbel's records.  mz_set_gumbel's parameters are
+ * the search's; with gumbel_scale 0 nothing is drawn and the pass is deterministic.  Otherwise the Gumbel draws of a row are
+ * keyed (engine seed, the row's index within the pass, draw_key, action): the row, not the tree that searched it, so a pass does
+ * not depend on num_envs, and a caller that passes another draw_key per pass gets other draws.  One synchronisation at the end;
+ * afterwards the engine's stepwise state is what mz_gz_search leaves after num_simulations on the last chunk.
+ * Refused: everything mz_reanalyse refuses; no Gumbel search set (mz_set_gumbel); value_kind other than 0 or 1. */
+int mz_reanalyse_gumbel(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
+                        int num_simulations, int value_kind, uint64_t draw_key, void *stream);
+
 /* Raw tree dump (Node objects of mcts.py:28-45 in SoA form) to [host] arrays, synchronous.
  * Each per-node array is [B][NN]; minmax [B][2]; legal_mask [B] (bit a = root child a exists);
  * noise [B][A] (the Dirichlet draw last mixed in).  Any pointer may be NULL. */

@@ -477,7 +477,10 @@ class Actor(Logger):
       if self.reanalyser is None:
         self.reanalyser = Reanalyser(cfg, self.replay_buffer, device=self.device)
       self.reanalyser.set_weights(weights)
-      out = self.reanalyser.run(rows)
+      if getattr(cfg, 'reanalyse_gumbel', False):      # the pull's training step keys the pass's Gumbel draws: passes differ, a resumed run repeats its own
+        out = self.reanalyser.run(rows, draw_key=self.training_step)
+      else:
+        out = self.reanalyser.run(rows)
     self.last_reanalyse = out
     if out['busy']:      # another actor's pass holds the shared replay's one ticket: this pull's pass is left out
       self.reanalyse_skipped += 1

@@ -150,6 +150,13 @@ def build_parser():
          'root_value rewritten in place (reanalyse.py); 0: off')
   a('--reanalyse_every', type=int, default=None,
     help='learner steps between Reanalyse passes (default: --weight_sync_frequency); a pass follows the first weight pull past each multiple')
+  a('--reanalyse_gumbel', action='store_true',
+    help='--reanalyse_rows with --selfplay_gumbel: the passes search with the Gumbel MuZero search (--selfplay_gumbel_considered / '
+         '_c_visit / _c_scale) and write the root\'s improved policy pi\' and the value --selfplay_gumbel_value names, what the '
+         'self-play records of that mode hold (reanalyse.py)')
+  a('--reanalyse_gumbel_scale', type=float, default=0.0,
+    help='--reanalyse_gumbel: the scale of the Gumbel noise at a reanalysed root; 0 (the default) draws none: a reanalysed root '
+         'needs a policy target, not exploration')
   a('--selfplay_gumbel', action='store_true',
     help='TicTacToe / ConnectFour / CartPole-v0 / -v1 on the device: the self-play moves are searched with the Gumbel MuZero '
          'search at --num_simulations (8 or 16 are its range), the records carry the improved policy pi\' as the policy target and '

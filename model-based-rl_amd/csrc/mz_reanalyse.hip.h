@@ -10,9 +10,16 @@
 //                        mz_root_visit_share / mz_root_mean_value, mz_tree.hip.h), not restated
 //
 // Between the two run mz_initial_inference, mz_root_prepare (no noise) and mz_search, unchanged.
+//
+// Reanalyse with the Gumbel search (mz_reanalyse_gumbel; DESIGN s7j) keeps k_reanalyse_observe, searches as a self-play move of
+// mz_selfplay_set_gumbel does (the root without noise, k_gz_root, the mz_gz_search loop; mz_gumbel.hip.h) and stores with
+//
+//   k_reanalyse_store_gumbel  the root's improved policy pi' as float32 where k_reanalyse_store puts the visit shares, then the
+//                             root's mean value or its v_mix as the float64; k_gz_pick's mapping and mz_gz_root_pick, not restated
 #pragma once
 #include "mz_common.h"
 #include "mz_tree.hip.h"
+#include "mz_gumbel.hip.h"
 
 // Separate from SelfplayState / EvalState / MatchState: self-play, evaluation and matches on the same engine are untouched.
 struct ReanalyseState {
@@ -72,4 +79,25 @@ static __global__ void k_reanalyse_store(TreeView t, float *fresh, int n) {
     const unsigned long long bits = (unsigned long long)__double_as_longlong(mz_root_mean_value(t, o));
     ((uint32_t *)fresh)[i] = j == A ? (uint32_t)bits : (uint32_t)(bits >> 32);
   }
+}
+
+// fresh: the chunk's first row, [n][A + 2]; nothing is stored for b >= n.  k_gz_pick's mapping: one 64-lane workgroup per row
+// (its 64 / G groups compute the same), lane = action.  Lanes wl < A store (float)pi'(a) -- exactly 0 on an illegal action --,
+// lane 0 the two halves of the float64 value: the root's mean value (value_kind 0) or its v_mix (1), k_gz_move_record's rule.
+// No LDS; plain vector stores.
+template <int G>
+__global__ __launch_bounds__(64) void k_reanalyse_store_gumbel(TreeView t, GzState gz, float *fresh, int n, int value_kind) {
+  const int b = blockIdx.x, wl = threadIdx.x, lane = wl % G;
+  if (b >= t.B || b >= n) return;
+  const int A = t.A;
+  double pi, vmix;
+  float cR;
+  (void)mz_gz_root_pick<G>(t, gz, b, lane, &pi, &vmix, &cR);
+  float *row = fresh + (size_t)b * (A + 2);
+  if (wl < A) row[wl] = (float)pi;
+  if (wl != 0) return;
+  const double rv = value_kind ? vmix : mz_root_mean_value(t, mz_slab(t, b));
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(rv);
+  ((uint32_t *)row)[A] = (uint32_t)bits;
+  ((uint32_t *)row)[A + 1] = (uint32_t)(bits >> 32);
 }

@@ -54,3 +54,84 @@ int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats,
   HIPCHECK(hipStreamSynchronize(s));
   return 0;
 }
+
+// Reanalyse with the Gumbel search (DESIGN s7j): mz_reanalyse's buffers, kinds and chunks, searched as a self-play move of
+// mz_selfplay_set_gumbel is (launch_move_gumbel, mz_gumbel_abi.inc) and stored as pi' and the root's mean value (value_kind 0)
+// or its v_mix (1).  A row's Gumbel draws are keyed (engine seed, the row's index in the pass, draw_key, action): k_gz_root takes
+// the chunk's first row as its environment offset, so a pass does not depend on the engine's B.  The host side of the step
+// protocol starts over at every chunk and ends where mz_gz_search leaves it.
+int mz_reanalyse_gumbel(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
+                        int num_simulations, int value_kind, uint64_t draw_key, void *stream) {
+  if (!e) return fail("mz_reanalyse_gumbel: null engine");
+  MZ_ENTER(e);
+  if (!e->weights_set) return fail("mz_reanalyse_gumbel: weights not set (call mz_set_weights)");
+  if (!e->gz.on) return fail("mz_reanalyse_gumbel: no Gumbel search is set on this engine (call mz_set_gumbel first)");
+  if (value_kind != 0 && value_kind != 1)
+    return fail("mz_reanalyse_gumbel: value_kind %d (0 the root's mean value, 1 its v_mix)", value_kind);
+  if (rec_floats != e->O + e->A + MZ_REC_EXTRA)
+    return fail("mz_reanalyse_gumbel: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, e->O + e->A + MZ_REC_EXTRA);
+  if (kind < 0 || kind > 3)
+    return fail("mz_reanalyse_gumbel: kind must be 0 (synthetic), 1 (TicTacToe), 2 (CartPole) or 3 (Connect Four), got %d", kind);
+  if (kind != 0 && game_shape(e, "mz_reanalyse_gumbel", kind)) return -1;
+  if (n_rows < 0) return fail("mz_reanalyse_gumbel: n_rows must be >= 0, got %d", n_rows);
+  if (num_simulations < 1 || num_simulations > e->sims)
+    return fail("mz_reanalyse_gumbel: num_simulations must be in 1 .. %d (the engine's pool), got %d", e->sims, num_simulations);
+  if (n_rows == 0) return 0;
+  if (!rows_host || !fresh_host) return fail("mz_reanalyse_gumbel: null buffer");
+  const float *rows_dev = nullptr;
+  float *fresh_dev = nullptr;
+  if (hipHostGetDevicePointer((void **)&rows_dev, (void *)rows_host, 0) != hipSuccess || !rows_dev ||
+      hipHostGetDevicePointer((void **)&fresh_dev, (void *)fresh_host, 0) != hipSuccess || !fresh_dev) {
+    (void)hipGetLastError();
+    return fail("mz_reanalyse_gumbel: rows and fresh must be page-locked (pinned) host memory");
+  }
+  ReanalyseState &rs = e->ra;
+  const int B = e->B, O = e->O, A = e->A;
+  if (!rs.to_play) {      // (as mz_reanalyse: allocated on the first call of either)
+    rs = ReanalyseState{};
+    if (dmalloc(e, &rs.obs, (size_t)e->Bp * O) || dmalloc(e, &rs.legal, (size_t)B * A) || dmalloc(e, &rs.to_play, (size_t)B)) {
+      rs = ReanalyseState{};
+      return -1;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 block(128), grid_obs(((size_t)B * O + 127) / 128);
+  // one chunk; a launch that fails leaves rc set, and what it had enqueued is waited for below
+  auto chunk = [&](int at, int n) -> int {
+    hipLaunchKernelGGL(k_reanalyse_observe, grid_obs, block, 0, s, rs, rows_dev + (size_t)at * rec_floats, n, rec_floats, kind, B, O, A);
+    if (hipGetLastError() != hipSuccess) return fail("mz_reanalyse_gumbel: k_reanalyse_observe did not launch");
+    if (mz_initial_inference(e, rs.obs, s)) return -1;
+    TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)rs.to_play, (const uint8_t *)rs.legal, (const double *)nullptr,
+                e->cfg.root_exploration_fraction, 0);
+    TREE_LAUNCH(k_gz_root, s, e->tv, e->gz, (const double *)nullptr, (uint64_t)e->cfg.seed, draw_key,
+                (const unsigned long long *)nullptr, at);
+    HIPCHECK(hipGetLastError());
+    e->sims_done = 0;
+    e->root_ready = true;
+    e->root_noise = false;
+    e->tm.root_set = false;
+    e->gz.root_set = true;
+    e->selection_valid = true;
+    if (gz_simulations(e, "mz_reanalyse_gumbel", num_simulations, s)) return -1;
+#define RA_STORE(G_)                                                                                                     \
+  hipLaunchKernelGGL(k_reanalyse_store_gumbel<G_>, dim3(B), dim3(64), 0, s, e->tv, e->gz, fresh_dev + (size_t)at * (A + 2), n, \
+                     value_kind)
+    switch (e->G) {
+      case 4: RA_STORE(4); break;
+      case 8: RA_STORE(8); break;
+      case 16: RA_STORE(16); break;
+      default: RA_STORE(32); break;
+    }
+#undef RA_STORE
+    if (hipGetLastError() != hipSuccess) return fail("mz_reanalyse_gumbel: k_reanalyse_store_gumbel did not launch");
+    return 0;
+  };
+  int rc = 0;
+  for (int at = 0; at < n_rows && !rc; at += B) rc = chunk(at, n_rows - at < B ? n_rows - at : B);
+  if (rc) {      // what was enqueued still reads / writes the caller's buffers: let it end before they are handed back
+    (void)hipStreamSynchronize(s);
+    return -1;
+  }
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}

@@ -784,17 +784,34 @@ class Engine(object):
     first n_rows rows are searched again under the current weights in chunks of B, without exploration noise, and fresh
     receives child_visits (float32) and root_value (float64 in two slots) per row -- what PrioritizedReplay.reanalyse_write
     takes.  kind: an ENVS / EVAL_ENVS name or 0..3.  Returns when the last chunk has been stored."""
+    kind, n_rows, sims = self._reanalyse_args('reanalyse', rows, fresh, n_rows, kind, num_simulations)
+    _abi.check(self.lib.mz_reanalyse(self._h, kind, _ptr(rows), int(rows.shape[1]), n_rows, _ptr(fresh), sims, self.stream),
+               'mz_reanalyse')
+
+  def _reanalyse_args(self, fn, rows, fresh, n_rows, kind, num_simulations):
+    """the tensor checks of reanalyse / reanalyse_gumbel -> (kind, n_rows, num_simulations) as ints"""
     if isinstance(kind, str):
       kind = self.ENVS[kind] if kind in self.ENVS else self.EVAL_ENVS[kind]
     n_rows = int(n_rows)
     for t, name, width in ((rows, 'rows', None), (fresh, 'fresh', self.A + 2)):
       if not (torch.is_tensor(t) and t.dtype == torch.float32 and not t.is_cuda and t.is_pinned() and t.is_contiguous() and t.dim() == 2):
-        raise ValueError('reanalyse: %s must be a contiguous pinned float32 host tensor [rows, floats]' % name)
+        raise ValueError('%s: %s must be a contiguous pinned float32 host tensor [rows, floats]' % (fn, name))
       if t.shape[0] < n_rows or (width is not None and t.shape[1] != width):
-        raise ValueError('reanalyse: %s has shape %s for %d rows of %s floats' % (name, tuple(t.shape), n_rows, width or 'rec_floats'))
-    sims = self.sims if num_simulations is None else int(num_simulations)
-    _abi.check(self.lib.mz_reanalyse(self._h, int(kind), _ptr(rows), int(rows.shape[1]), n_rows, _ptr(fresh), sims, self.stream),
-               'mz_reanalyse')
+        raise ValueError('%s: %s has shape %s for %d rows of %s floats' % (fn, name, tuple(t.shape), n_rows, width or 'rec_floats'))
+    return int(kind), n_rows, self.sims if num_simulations is None else int(num_simulations)
+
+  def reanalyse_gumbel(self, rows, fresh, n_rows, kind, num_simulations=None, value='mean', draw_key=0):
+    """mz_reanalyse_gumbel (DESIGN s7j; set_gumbel first): reanalyse's buffers and chunks, searched with the Gumbel search; fresh
+    receives the root's improved policy pi' (float32, exactly 0 at illegal actions) and, as the float64, the root's mean value
+    ('mean') or its v_mix ('vmix') -- what a record of selfplay_set_gumbel holds.  draw_key: with a gumbel_scale above 0 a row's
+    draws are keyed (engine seed, row index in the pass, draw_key, action), so a pass does not depend on B; at scale 0 nothing
+    is drawn."""
+    if value not in self.SELFPLAY_GUMBEL_VALUES:
+      raise ValueError("reanalyse_gumbel: value is 'mean' or 'vmix', got %r" % (value,))
+    kind, n_rows, sims = self._reanalyse_args('reanalyse_gumbel', rows, fresh, n_rows, kind, num_simulations)
+    _abi.check(self.lib.mz_reanalyse_gumbel(self._h, kind, _ptr(rows), int(rows.shape[1]), n_rows, _ptr(fresh), sims,
+                                            self.SELFPLAY_GUMBEL_VALUES[value], int(draw_key) & 0xFFFFFFFFFFFFFFFF, self.stream),
+               'mz_reanalyse_gumbel')
 
   def export_tree(self, hidden=False):
     B, NN, A = self.B, self.NN, self.A

@@ -6,6 +6,8 @@ statistics back in place.  The replay builds its n-step targets at sampling time
   replay.reanalyse_pick   whole history slices out, all their rows (include/mz_replay.h)        -> pinned rows
   Engine.reanalyse        per chunk of B rows: observe, initial inference, root without noise,
                           search, store (csrc/mz_reanalyse.hip.h; no host work between chunks)    -> pinned fresh
+                          (--reanalyse_gumbel: Engine.reanalyse_gumbel, the Gumbel search, pi' and
+                          the value kind of --selfplay_gumbel's records; DESIGN s7j)
   replay.reanalyse_write  child_visits and root_value of exactly those rows                       <- pinned fresh
 
 Not part of this: exploration noise at the reanalysed root; refreshing the stored error or the priorities (the learner's own
@@ -20,12 +22,28 @@ import torch
 from .actors import _call
 from .engine import Engine, REC_EXTRA
 from .envs import KIND_OF_ENV
+from .selfplay_gumbel import selfplay_gumbel_params
 
 KINDS = KIND_OF_ENV      # (envs.DEVICE_GAMES; anything else: 0, all actions legal)
 
 
 def env_kind(config):
   return KINDS.get(str(getattr(config, 'environment', '')), 0)
+
+
+def refuse_reanalyse_gumbel(config):
+  """what --reanalyse_gumbel is not built for, one sentence each, before any device is touched (--reanalyse_rows' own refusals
+  apply beside these: refuse_reanalyse)"""
+  if not getattr(config, 'reanalyse_gumbel', False):
+    return
+  no = lambda why: SystemExit('--reanalyse_gumbel: ' + why)
+  if int(getattr(config, 'reanalyse_rows', 0) or 0) <= 0:
+    raise no('it chooses the search of the Reanalyse passes and does nothing without --reanalyse_rows above 0.')
+  if not getattr(config, 'selfplay_gumbel', False):
+    raise no('without --selfplay_gumbel it would mix the visit shares of PUCT self-play and pi\' policy targets in one replay.')
+  scale = float(getattr(config, 'reanalyse_gumbel_scale', 0.0))
+  if not scale >= 0:
+    raise no('--reanalyse_gumbel_scale must not be negative, got %g.' % scale)
 
 
 def refuse_reanalyse(config, ranks=0):
@@ -50,7 +68,8 @@ def refuse_reanalyse(config, ranks=0):
 
 class Reanalyser(object):
   """Reanalyser(config, replay, device=None, batch=None): an Engine of its own (B = batch or min(num_envs, 4096), the actor's
-  search settings) and two pinned buffers; set_weights(flat or state_dict), then run(max_rows) per pass."""
+  search settings) and two pinned buffers; set_weights(flat or state_dict), then run(max_rows) per pass.  With
+  config.reanalyse_gumbel the engine searches with the Gumbel search and run(max_rows, draw_key) writes pi' (DESIGN s7j)."""
 
   def __init__(self, config, replay, device=None, batch=None, max_rows=None):
     self.config, self.replay = config, replay
@@ -59,6 +78,12 @@ class Reanalyser(object):
     self.kind = env_kind(config)
     self.engine = Engine.from_config(config, self.B, device=device)
     self.device = self.engine.device
+    # --reanalyse_gumbel (DESIGN s7j): the search and the value kind of the --selfplay_gumbel run that filled the replay -- one
+    # replay holds one kind of policy target and one kind of value --, with a noise scale of its own
+    self.gumbel = bool(getattr(config, 'reanalyse_gumbel', False))
+    self.gumbel_value = getattr(config, 'selfplay_gumbel_value', 'mean') if self.gumbel else None
+    if self.gumbel:
+      self.engine.set_gumbel(True, *selfplay_gumbel_params(config)[:3], float(getattr(config, 'reanalyse_gumbel_scale', 0.0) or 0.0))
     self.rows = self.fresh = None
     self.max_rows = 0
     self._size(int(max_rows or getattr(config, 'reanalyse_rows', 0) or 0))
@@ -72,8 +97,8 @@ class Reanalyser(object):
   def set_weights(self, weights):
     self.engine.set_weights(weights)
 
-  def run(self, max_rows=None):
-    """one pass: pick -> Engine.reanalyse -> write.  -> dict(rows, slices, skipped_slices, seconds, mean_abs_value_change,
+  def run(self, max_rows=None, draw_key=0):
+    """one pass: pick -> Engine.reanalyse (Engine.reanalyse_gumbel under --reanalyse_gumbel, draw_key in the key of its draws) -> write.  -> dict(rows, slices, skipped_slices, seconds, mean_abs_value_change,
     mean_policy_l1, busy): rows written, and the means over them of |new - old root_value| and of the L1 distance between the old
     and the new child_visits.  busy: another pass over the same replay holds its one ticket (several actors share a replay and
     pull weights at the same steps): this pass is skipped, nothing is searched or written"""
@@ -86,7 +111,10 @@ class Reanalyser(object):
     if pick['ticket']:
       n = int(pick['n_rows'])
       try:
-        self.engine.reanalyse(self.rows, self.fresh, n, self.kind)
+        if self.gumbel:
+          self.engine.reanalyse_gumbel(self.rows, self.fresh, n, self.kind, value=self.gumbel_value, draw_key=draw_key)
+        else:
+          self.engine.reanalyse(self.rows, self.fresh, n, self.kind)
       except BaseException:
         _call(self.replay, 'reanalyse_release', pick['ticket'])
         raise

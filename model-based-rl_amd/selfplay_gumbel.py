@@ -30,8 +30,8 @@ def refuse_selfplay_gumbel(config, ranks=0):
     raise no('--split_f16 is a fused search kernel, which this search does not run.')
   if int(ranks or 0) > 1:
     raise no('multi-rank runs (--ranks above 1) are not built for it.')
-  if int(getattr(config, 'reanalyse_rows', 0) or 0) > 0:
-    raise no('--reanalyse_rows would mix visit-share and pi\' policy targets in one replay; Reanalyse does not write pi\'.')
+  if int(getattr(config, 'reanalyse_rows', 0) or 0) > 0 and not getattr(config, 'reanalyse_gumbel', False):
+    raise no('--reanalyse_rows would mix visit-share and pi\' policy targets in one replay; Reanalyse does not write pi\' unless --reanalyse_gumbel is given.')
   m, c_visit, c_scale, scale = selfplay_gumbel_params(config)
   if m < 2:
     raise no('--selfplay_gumbel_considered must be at least 2, got %d.' % m)

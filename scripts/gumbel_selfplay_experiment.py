@@ -1,5 +1,6 @@
-"""The experiment --selfplay_gumbel was built for (DESIGN s7i): scripts/tictactoe_learning.py, seed 0, three ways -- PUCT self-play
-at 30 simulations as today, Gumbel self-play at 8 with the mean root value, Gumbel self-play at 8 with v_mix -- and the three final
+"""The experiment --selfplay_gumbel was built for (DESIGN s7i): scripts/tictactoe_learning.py, seed 0, four ways -- PUCT self-play
+at 30 simulations as today, Gumbel self-play at 8 with the mean root value, Gumbel self-play at 8 with v_mix, and the mean-value run
+with Gumbel Reanalyse (--reanalyse_rows 4096 --reanalyse_gumbel, DESIGN s7j) -- and the final
 checkpoints compared: the mutual matches (256 seeds, both seats, two random opening plies) evaluated with PUCT at 30 and with the
 Gumbel search at 8, and from each run's own report the --grade optimal-move rates, the scores against the 1024-playout search and
 the wall-clock.  Writes ONE JSON line (default profiles/gumbel_selfplay_tictactoe_learning.json).  An observation, not a claim.
@@ -20,7 +21,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 RUNS = {'puct30': [], 'gumbel8_mean': ['--selfplay_gumbel', '--num_simulations', '8'],
-        'gumbel8_vmix': ['--selfplay_gumbel', '--num_simulations', '8', '--selfplay_gumbel_value', 'vmix']}
+        'gumbel8_vmix': ['--selfplay_gumbel', '--num_simulations', '8', '--selfplay_gumbel_value', 'vmix'],
+        # (DESIGN s7j: the gumbel8_mean run with its stored targets refreshed by Gumbel Reanalyse passes of 4096 rows)
+        'gumbel8_mean_reanalyse': ['--selfplay_gumbel', '--num_simulations', '8', '--reanalyse_rows', '4096', '--reanalyse_gumbel']}
 RUN_SECONDS = 420
 
 

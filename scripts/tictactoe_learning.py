@@ -8,6 +8,9 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
                                        [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]] [--true_model] [--gumbel]
                                        [--selfplay_gumbel [--num_simulations 8] [--selfplay_gumbel_value vmix] ...]
+                                       [--reanalyse_rows N [--reanalyse_every K] [--reanalyse_gumbel [--reanalyse_gumbel_scale S]]]
+--reanalyse_rows / --reanalyse_every / --reanalyse_gumbel / --reanalyse_gumbel_scale are train's flags, passed on to the training run
+(--reanalyse_gumbel: Reanalyse with the Gumbel search for a --selfplay_gumbel run, reanalyse.py).
 --selfplay_gumbel adds train's flag (self-play searched with the Gumbel search, the learner trained on pi'; selfplay_gumbel.py) with
 its --selfplay_gumbel_* parameters, and --num_simulations sets the simulations of the TRAINING run's self-play; the evaluation
 blocks below stay as they are -- PUCT at 30 simulations unless --gumbel is given.
@@ -96,6 +99,9 @@ def build_parser():
   ap.add_argument('--scalar_loss', default='MSE', choices=['MSE', 'Huber'])
   ap.add_argument('--reanalyse_rows', type=int, default=0, help='train --reanalyse_rows (0: off)')
   ap.add_argument('--reanalyse_every', type=int, default=None, help='train --reanalyse_every')
+  ap.add_argument('--reanalyse_gumbel', action='store_true',
+                  help='train --reanalyse_gumbel: with --selfplay_gumbel and --reanalyse_rows, the passes search with the Gumbel search and write pi\'')
+  ap.add_argument('--reanalyse_gumbel_scale', type=float, default=None, help='train --reanalyse_gumbel_scale')
   ap.add_argument('--keep_checkpoint', default=None, help='copy the run\'s last checkpoint to this file')
   ap.add_argument('--match_against', default=None, help='a checkpoint kept by another run: the last checkpoint also plays it, from both seats')
   ap.add_argument('--opp_playouts', type=int, default=0,
@@ -134,6 +140,10 @@ def recipe(a):
   extra = ['--reanalyse_rows', str(a.reanalyse_rows)] if a.reanalyse_rows else []
   if a.reanalyse_rows and a.reanalyse_every:
     extra += ['--reanalyse_every', str(a.reanalyse_every)]
+  if a.reanalyse_gumbel:      # (given without --reanalyse_rows or --selfplay_gumbel: train's preflight says so)
+    extra += ['--reanalyse_gumbel']
+    if a.reanalyse_gumbel_scale is not None:
+      extra += ['--reanalyse_gumbel_scale', str(a.reanalyse_gumbel_scale)]
   if a.symmetry:
     extra += ['--symmetry']
   if a.num_simulations is not None:
