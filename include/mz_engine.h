@@ -433,6 +433,11 @@ int mz_tm_expand_backup(mz_engine *e, const float *value, const float *logits, v
 int mz_tm_expand_backup_select(mz_engine *e, const float *value, const float *logits, float *obs_out, uint8_t *finished_out,
                                void *stream);
 int mz_tm_search(mz_engine *e, int num_simulations, void *stream);
+/* mz_tm_search in ONE launch (DESIGN s7k; k_tm_search, csrc/mz_truemodel.hip.h): every workgroup alternates the leaf inference of
+ * its 16 rows with the tree step of its 16 trees, num_simulations times.  The same preconditions, the same refusals in its own
+ * name, the same effect on the step protocol (a pending descent is launched first if there is none; a descent is pending
+ * afterwards unless the pool is used up) and bit-identical trees, slots, leaf observations and leaf flags. */
+int mz_tm_search_fused(mz_engine *e, int num_simulations, void *stream);
 
 /* The Gumbel MuZero search (DESIGN s7h; csrc/mz_gumbel.hip.h; Danihelka et al., ICLR 2022) beside mz_search, on the same
  * node pool, weights, expansion and backup: at the root, simulation s goes to the legal action with the largest
@@ -483,6 +488,19 @@ int mz_gz_pick(mz_engine *e, int32_t *action, float *pred_reward, double *improv
  * mz_sim_io mode, and while moves wait in the device ring.  While on, mz_set_gumbel(e, 0, ..), mz_selfplay_set_draws,
  * mz_selfplay_set_env, mz_sim_io modes and mz_selfplay_steps_timed are refused.  on 0: the loop runs again as it did before. */
 int mz_selfplay_set_gumbel(mz_engine *e, int on, int value_kind);
+
+/* Self-play on the true rules (DESIGN s7k).  While on, a move of mz_selfplay_steps / mz_selfplay_steps_into on a device board
+ * game (mz_selfplay_set_env 1 or 3) is a PUCT move -- observe, initial inference, the Dirichlet draw keyed by the environment's
+ * move counter, the root with that noise, the PUCT move's end with its temperature, sampling uniform, error and reset on done --
+ * whose search is the true-rules search: the root's position is taken from the environment on the device, then num_simulations
+ * of mz_tm_search_fused (fused != 0: one launch) or of mz_tm_search (fused 0: two launches per simulation); both give the same
+ * records.  The record keeps its layout; only what a node below the root is differs.
+ * The moves run in the launch-per-step form, up to 16 per hipGraph: mz_selfplay_moves_per_launch returns 0 while on.
+ * Needs mz_set_true_model with the environment's kind; refused in the Gumbel self-play mode, with host-given draws
+ * (mz_selfplay_set_draws), with an mz_sim_io mode, and while moves wait in the device ring.  While on, mz_set_true_model to
+ * another kind, mz_selfplay_set_draws, mz_selfplay_set_env, mz_selfplay_set_gumbel, mz_sim_io modes and mz_selfplay_steps_timed
+ * are refused.  Switching synchronises and drops the captured graphs; on 0: the loop runs again as it did before. */
+int mz_selfplay_set_true_model(mz_engine *e, int on, int fused);
 
 /* MuZero Reanalyse: stored positions of the replay searched again under the engine's CURRENT weights.  rows_host [host, pinned]
  * is [n_rows][rec_floats] record rows as mzr_reanalyse_pick (include/mz_replay.h) wrote them, rec_floats = obs_dim + action_space

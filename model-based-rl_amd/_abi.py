@@ -174,6 +174,7 @@ SIGNATURES = {
     'mz_tm_expand_backup': (_I, [_VP, _VP, _VP, _VP]),
     'mz_tm_expand_backup_select': (_I, [_VP] * 6),
     'mz_tm_search': (_I, [_VP, _I, _VP]),
+    'mz_tm_search_fused': (_I, [_VP, _I, _VP]),
     'mz_tm_export': (_I, [_VP] * 7),
     'mz_tm_search_host': (_I, [C.POINTER(MzConfig), _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP] + [_VP] * 15),
     'mz_set_gumbel': (_I, [_VP, _I, _I, C.c_double, C.c_double, C.c_double]),
@@ -206,6 +207,7 @@ SIGNATURES = {
     'mz_selfplay_set_env': (_I, [_VP, _I]),
     'mz_selfplay_set_draws': (_I, [_VP, _VP, _VP, _VP]),
     'mz_selfplay_set_gumbel': (_I, [_VP, _I, _I]),
+    'mz_selfplay_set_true_model': (_I, [_VP, _I, _I]),
     'mz_selfplay_export_trees': (_I, [_VP, _I]),
     'mz_selfplay_noise_log': (_I, [_VP, _I]),
     'mz_selfplay_read_noise': (_I, [_VP, _U64, _VP]),

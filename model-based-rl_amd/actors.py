@@ -412,6 +412,9 @@ class Actor(Logger):
       if getattr(cfg, 'selfplay_gumbel', False):      # the moves are searched with the Gumbel search, the records carry pi' (DESIGN s7i)
         eng.set_gumbel(True, *selfplay_gumbel_params(cfg))
         eng.selfplay_set_gumbel(True, getattr(cfg, 'selfplay_gumbel_value', 'mean'))
+      if getattr(cfg, 'selfplay_true_model', False):      # PUCT moves searched on the game's true rules (DESIGN s7k)
+        eng.set_true_model(KIND_OF_ENV[cfg.environment])
+        eng.selfplay_set_true_model(True, fused=not getattr(cfg, 'selfplay_true_model_loop', False))
       # (CartPole: the episode length is the environment's time limit, whatever --episode_length says)
       eng.selfplay_reset(CARTPOLE_TIME_LIMITS.get(cfg.environment, cfg.episode_length), temperature, stagger=True)
       self._selfplay_temperature = temperature

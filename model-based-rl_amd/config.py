@@ -169,6 +169,13 @@ def build_parser():
     help='--selfplay_gumbel: the scale of the Gumbel noise at the root, the exploration of this mode; 1 is the training setting of the paper')
   a('--selfplay_gumbel_value', type=str, default='mean', choices=['mean', 'vmix'],
     help='--selfplay_gumbel: what a record stores as the root value, the n-step targets\' bootstrap: the root\'s mean value, or its v_mix')
+  a('--selfplay_true_model', action='store_true',
+    help='TicTacToe / ConnectFour on the device: the self-play moves are PUCT moves searched on the TRUE rules below the root '
+         '(real positions, legal moves only, the game\'s end), AlphaZero\'s search feeding MuZero\'s learner; records, learner and '
+         'checkpoint are unchanged (selfplay_true_model.py; evaluation keeps its own --true_model flag)')
+  a('--selfplay_true_model_loop', action='store_true',
+    help='--selfplay_true_model: two launches per simulation (mz_tm_search) instead of one launch per move (mz_tm_search_fused); '
+         'the records are the same')
   a('--symmetry', action='store_true',
     help='TicTacToe / ConnectFour: train every sample of a batch on one of the equivalent images of its position (8 rotations and '
          'mirrors / the left-right mirror), drawn per (seed, update, sample); observation, unrolled actions and policy targets move '

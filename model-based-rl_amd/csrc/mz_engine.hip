@@ -175,6 +175,8 @@ struct mz_engine {
   bool root_noise = false;          // the last mz_root_prepare mixed exploration noise into the root's priors
   bool sp_gumbel = false;           // the self-play loop's moves are searched with the Gumbel search (mz_selfplay_set_gumbel; DESIGN s7i)
   int sp_gumbel_value = 0;          // ... and their records' root_value: 0 the root's mean value, 1 its v_mix
+  bool sp_tm = false;               // the self-play loop's moves are searched on the true rules (mz_selfplay_set_true_model; DESIGN s7k)
+  bool sp_tm_fused = false;         // ... all simulations of a move in one launch of k_tm_search (else the two-launch loop)
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -515,8 +517,8 @@ static SearchPlan search_plan(const mz_engine *e) {
   // environment on the single-player game kernel, or the device Connect Four environment on its two game kernels (whole
   // trees, compact placement); a game environment without such an instantiation for its shape and
   // placement, or with split_f16, plays in the launch-per-step form (launch_move_game), and so does every move searched with
-  // the Gumbel search (mz_selfplay_set_gumbel)
-  p.persist = !e->sp_gumbel && e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
+  // the Gumbel search (mz_selfplay_set_gumbel) or on the true rules (mz_selfplay_set_true_model)
+  p.persist = !e->sp_gumbel && !e->sp_tm && e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
               (p.game ? !e->split_f16 && !!e->cfg.two_players == (p.game != 2) &&
                             find_kernel(1, *p.shape, p.lt, false, p.sp, true, true) != nullptr
                       : p.sp && !e->sp.env_kind);

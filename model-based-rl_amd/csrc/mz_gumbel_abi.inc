@@ -192,6 +192,7 @@ int mz_selfplay_set_gumbel(mz_engine *e, int on, int value_kind) {
   if (!e) return fail("mz_selfplay_set_gumbel: null engine");
   MZ_ENTER(e);
   if (on) {
+    if (e->sp_tm) return fail("mz_selfplay_set_gumbel: the self-play moves are searched on the true rules (mz_selfplay_set_true_model 0 first)");
     if (value_kind != 0 && value_kind != 1) return fail("mz_selfplay_set_gumbel: value_kind %d (0 the root's mean value, 1 its v_mix)", value_kind);
     if (!e->gz.on) return fail("mz_selfplay_set_gumbel: no Gumbel search is set on this engine (call mz_set_gumbel first)");
     if (!e->sp.env_kind) return fail("mz_selfplay_set_gumbel: the Gumbel self-play runs on the device games; set one first (mz_selfplay_set_env 1, 2 or 3)");

@@ -31,6 +31,8 @@ struct RootSched {
 };
 
 #define MZ_ROOT_LDS_FLOATS (16 * MZ_ROOT_XS + 16 * MZ_HS + 4 * 6 * 256 + 96 * 16 + 16 + 16 * 32 + 64 + 64 + 64 + 64 + 16 * MZ_XE)
+// where the body leaves its rows' outputs: value [16] at MZ_ROOT_LDS_VAL, logits [16][32] behind it (k_tm_search reads them)
+#define MZ_ROOT_LDS_VAL (16 * MZ_ROOT_XS + 16 * MZ_HS + 4 * 6 * 256 + 96 * 16)
 
 // The whole root of one move for the 16 rows of this workgroup (256 threads), on MZ_ROOT_LDS_FLOATS floats of LDS the
 // caller provides: the body of k_root, and the head of every move of the persistent self-play kernel (mz_fused.hip.h,
@@ -61,7 +63,7 @@ __device__ __forceinline__ void mz_root_body(const NetView &n, const TreeView &t
   float *xR = xO + 16 * XS;               // [16][MZ_HS] hidden tile
   float *red = xR + 16 * MZ_HS;           // split-K partials
   float *fin = red + 4 * 6 * 256;         // combined outputs [96][16]
-  float *s_val = fin + 96 * 16;
+  float *s_val = smem + MZ_ROOT_LDS_VAL;
   float *s_lg = s_val + 16;               // [16][32]
   float *s_b0o = s_lg + 16 * 32;
   float *s_b4 = s_b0o + 64;

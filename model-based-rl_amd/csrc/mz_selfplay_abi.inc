@@ -78,8 +78,10 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
 // expansion + first descent, the two-player search kernel, end of move with the real env.step -- all on the stream, no
 // host round trip; up to 16 moves per hipGraph like every other configuration.
 static int launch_move_gumbel(mz_engine *e, hipStream_t s);      // (mz_gumbel_abi.inc: the move of mz_selfplay_set_gumbel)
+static int launch_move_true_model(mz_engine *e, hipStream_t s);      // (mz_truemodel_abi.inc: the move of mz_selfplay_set_true_model)
 static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
   if (e->sp_gumbel) return launch_move_gumbel(e, s);
+  if (e->sp_tm) return launch_move_true_model(e, s);
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
   const bool cart = sp.env_kind == 2, c4 = sp.env_kind == 3;
@@ -203,6 +205,7 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
   MZ_ENTER(e);
   if (kind < 0 || kind > 3) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole, 3 Connect Four)", kind);
   if (e->sp_gumbel) return fail("mz_selfplay_set_env: the self-play moves are searched with the Gumbel search, set for the current game (mz_selfplay_set_gumbel 0 first)");
+  if (e->sp_tm) return fail("mz_selfplay_set_env: the self-play moves are searched on the true rules of the current game (mz_selfplay_set_true_model 0 first)");
   if (kind != 0 && game_shape(e, "mz_selfplay_set_env", kind)) return -1;
   if (kind == 3 && e->sp.obs_u8 == 2)
     return fail("mz_selfplay_set_env: packed byte observations are for the synthetic -ram- environments");
@@ -236,6 +239,7 @@ int mz_selfplay_set_draws(mz_engine *e, const double *noise, const double *unifo
   MZ_ENTER(e);
   if (e->sp.env_kind != 1) return fail("mz_selfplay_set_draws: only for the TicTacToe environment (mz_selfplay_set_env)");
   if (e->sp_gumbel) return fail("mz_selfplay_set_draws: the self-play moves are searched with the Gumbel search, which draws its own noise on the device (mz_selfplay_set_gumbel 0 first)");
+  if (e->sp_tm) return fail("mz_selfplay_set_draws: the self-play moves are searched on the true rules, a mode that draws its noise on the device (mz_selfplay_set_true_model 0 first)");
   hipStream_t s = (hipStream_t)stream;
   if (noise) HIPCHECK(hipMemcpyAsync(e->tv.noise, noise, (size_t)e->B * e->A * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (uniform) HIPCHECK(hipMemcpyAsync(e->draw_uniform, uniform, (size_t)e->B * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -277,6 +281,7 @@ int mz_sim_io(mz_engine *e, int mode, float *buf, int keep_moves) {
   if (mode < 0 || mode > 2) return fail("mz_sim_io: mode %d (0 off, 1 log, 2 inject)", mode);
   if (mode && (!buf || keep_moves < 1)) return fail("mz_sim_io: a buffer of keep_moves >= 1 moves is required");
   if (mode && e->sp_gumbel) return fail("mz_sim_io: the self-play moves are searched with the Gumbel search, which the fused kernels do not run (mz_selfplay_set_gumbel 0 first)");
+  if (mode && e->sp_tm) return fail("mz_sim_io: the self-play moves are searched on the true rules, which the fused kernels do not run (mz_selfplay_set_true_model 0 first)");
   HIPCHECK(hipDeviceSynchronize());
   e->tv.sim_io = mode ? buf : nullptr;
   e->tv.sim_io_keep = mode == 2 ? -keep_moves : (mode == 1 ? keep_moves : 0);
@@ -430,6 +435,7 @@ int mz_selfplay_steps_timed(mz_engine *e, int k, float *ms_out, void *stream) {
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
   const char *own = e->sp_gumbel ? "the moves are searched with the Gumbel search, which has no single search dispatch to clock" :
+                    e->sp_tm ? "the moves are searched on the true rules, a search without a clocked dispatch (mz_selfplay_set_true_model 0 first)" :
                     fused_usable(e) ? nullptr : "fused kernel not in use";
   const int brc = produce_begin(e, "mz_selfplay_steps_timed", own, k, INT_MAX, true, s);
   if (brc > 0) return fail("mz_selfplay_steps_timed: %d moves do not fit the undrained ring", k);

@@ -1,5 +1,5 @@
-// mz_truemodel.hip.h -- the true-rules search of evaluation games and matches (DESIGN s7g; gfx950; included by mz_engine.hip,
-// -ffp-contract=off).  The MCTS of mz_tree.hip.h -- the same PUCT, MinMaxStats, tie rules and backup, in the same node pool --
+// mz_truemodel.hip.h -- the true-rules search of evaluation games and matches (DESIGN s7g) and of self-play (s7k: k_tm_search, all
+// simulations in one launch, and k_tm_root_selfplay, at the end of this file); gfx950; included by mz_engine.hip, -ffp-contract=off.  The MCTS of mz_tree.hip.h -- the same PUCT, MinMaxStats, tie rules and backup, in the same node pool --
 // in which a node below the root is a REAL position of TicTacToe or Connect Four: reached by mz_game_step from its parent's
 // position, evaluated by the engine's representation + prediction on mz_game_observe of it, expanded over its legal actions
 // only and closed where the game ends, with the true reward.  No hidden state is kept below the root; the side state of an
@@ -14,6 +14,7 @@
 #include "mz_games.h"
 #include "mz_tree.hip.h"
 #include "mz_tree_host.h"      // (the host twin's trees, mz_truemodel_host.inc)
+#include "mz_root.hip.h"       // (k_tm_search runs the leaf inference, mz_root_body, itself)
 
 // side state of one expansion slot, and (pend) of the leaf the last descent selected
 struct alignas(16) MzTmSlot {
@@ -51,7 +52,8 @@ __device__ __forceinline__ void mz_tm_slot_store(MzTmSlot *dst, const MzTmSlotBi
 
 // The leaf q = step(parent position, action) as a slot record: the rules are mz_games.h's.  Returns through u (the
 // parent's record on entry); obs[O] = mz_game_observe(q) in the mover's view, zeros when q is finished.
-__host__ __device__ inline void mz_tm_leaf(int kind, MzTmSlot &u, int action, int O, int A, float *obs) {
+// legal: room for the A legal bytes mz_game_observe also writes (MZ_GAME_MAX_ACTIONS of them; not read here)
+__host__ __device__ inline void mz_tm_leaf(int kind, MzTmSlot &u, int action, int O, int A, float *obs, uint8_t *legal) {
   const int mp = (int)u.mover, st = u.step;
   bool won = false;
   const bool done = mz_game_step(kind, u.bd, mp, action, st, &won);
@@ -62,7 +64,6 @@ __host__ __device__ inline void mz_tm_leaf(int kind, MzTmSlot &u, int action, in
   u.mask = mask;
   u.fin = (uint8_t)(mask == 0u ? 1 : 0);      // (a live position always has a legal action: a full board is done)
   u.revisit = 0;
-  uint8_t legal[MZ_GAME_MAX_ACTIONS];
   mz_game_observe(kind, u.bd, -mp, nullptr, mask != 0u, O, A, obs, legal);
 }
 
@@ -80,16 +81,21 @@ struct MzTmChildren {
 
 // The descent (mz_tree_descend by PUCT, mz_tree.hip.h) over those children.  It ends at a node that is not expanded, or at a
 // finished one: that is a revisit, nothing will be expanded.  Lane 0 then leaves the leaf's record in tm.pend[b] and its
-// observation in tm.obs[b].
-template <int G>
-__device__ __forceinline__ void mz_tm_select(const TreeView &t, const TmState &tm, int O, int b, int lane) {
+// observation in tm.obs[b].  WS (k_tm_search: LDS): lane 0 forms the record, which it indexes by cell at run time, in
+// *ws and leaves mz_tm_leaf's legal bytes in legal_ws; else in private memory, 80 bytes of scratch in the stand-alone kernels.
+template <int G, bool WS = false>
+__device__ __forceinline__ void mz_tm_select(const TreeView &t, const TmState &tm, int O, int b, int lane,
+                                             MzTmSlotBits *ws = nullptr, uint8_t *legal_ws = nullptr) {
   const size_t o = mz_slab(t, b);
   const MzTmSlot *slots = tm.slots + (size_t)b * (size_t)(t.sims + 1);
   MzPuctRule<G, MzTmChildren> rule = {t, o, lane, t.mn[b], t.mx[b], {slots}, 0};
   const MzDescent d = mz_tree_descend<G>(t, b, lane, rule);
   if (lane == 0) {
     float *obs = tm.obs + (size_t)b * O;
-    MzTmSlotBits u;
+    MzTmSlotBits own;
+    uint8_t own_legal[MZ_GAME_MAX_ACTIONS];
+    MzTmSlotBits &u = WS ? *ws : own;
+    uint8_t *legal = WS ? legal_ws : own_legal;
     if (d.stopped) {
       u.q[0] = u.q[1] = u.q[2] = u.q[3] = mz_i32x4{0, 0, 0, 0};
       u.s.reward = t.R[o + d.node];      // stored at its first visit
@@ -99,7 +105,7 @@ __device__ __forceinline__ void mz_tm_select(const TreeView &t, const TmState &t
       for (int k = 0; k < O; ++k) obs[k] = 0.f;
     } else {
       mz_tm_slot_load(u, slots + d.slot);
-      mz_tm_leaf(tm.kind, u.s, d.act, O, t.A, obs);
+      mz_tm_leaf(tm.kind, u.s, d.act, O, t.A, obs, legal);
     }
     mz_tm_slot_store(tm.pend + b, u);
     tm.leaf_fin[b] = u.s.fin;
@@ -116,7 +122,10 @@ __device__ __forceinline__ void mz_tm_expand_backup(const TreeView &t, const TmS
   mz_tm_slot_load(u, tm.pend + b);      // (one address for the group's lanes)
   const bool grow = u.s.revisit == 0;
   const int e = mz_tree_expand_backup<G>(t, b, lane, u.s.fin != 0 ? 0.f : value, u.s.reward, logits, MzExpandMask{u.s.mask, grow});
-  if (grow && lane < 4) ((mz_i32x4 *)(tm.slots + (size_t)b * (size_t)(t.sims + 1) + e))[lane] = u.q[lane];
+  if (grow && lane < 4) {      // (the word picked by compares: indexing u.q by the lane would put the record into private memory)
+    const mz_i32x4 q = lane == 0 ? u.q[0] : (lane == 1 ? u.q[1] : (lane == 2 ? u.q[2] : u.q[3]));
+    ((mz_i32x4 *)(tm.slots + (size_t)b * (size_t)(t.sims + 1) + e))[lane] = q;
+  }
 }
 
 // ------------------------------------------------------------------ kernels
@@ -159,5 +168,68 @@ __global__ void k_tm_step(TreeView t, TmState tm, int O, const float *value, con
   if (do_select) {
     __threadfence_block();          // lane 0's node and slot updates -> visible to the group's other lanes
     mz_tm_select<G>(t, tm, O, b, lane);
+  }
+}
+
+// mz_tm_root for a self-play move (mz_selfplay_set_true_model; DESIGN s7k): the root's position is the environment's own --
+// sp.board at the game's own stride (TicTacToe [B][9], Connect Four [B][42]), sp.turn and sp.t -- on the stream, no host copy
+template <int G>
+__global__ void k_tm_root_selfplay(TreeView t, TmState tm, int O, SelfplayState sp) {
+  const int gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = gt / G, lane = gt % G;
+  if (b >= t.B) return;
+  if (lane == 0) {
+    MzTmSlotBits u;
+    u.q[0] = u.q[1] = u.q[2] = u.q[3] = mz_i32x4{0, 0, 0, 0};
+    const int cells = mz_game_info(tm.kind).cells;
+    for (int k = 0; k < cells; ++k) u.s.bd[k] = sp.board[(size_t)b * cells + k];
+    u.s.mask = t.legal[b];
+    u.s.step = sp.t[b];
+    u.s.mover = sp.turn[b];
+    mz_tm_slot_store(tm.slots + (size_t)b * (size_t)(t.sims + 1), u);
+  }
+  __threadfence_block();
+  mz_tm_select<G>(t, tm, O, b, lane);
+}
+
+// All the simulations of a true-rules search in ONE launch (mz_tm_search_fused; DESIGN s7k).  A true-rules simulation keeps no
+// hidden state, and a tree's next leaf depends on that tree alone: the workgroup that runs the leaf inference of its 16 rows
+// (mz_root_body, k_root's body, on tm.obs) also runs the tree step of those 16 trees, and goes round nsims times.  No grid-wide
+// dependency arises.  Grid Bp / MZ_ROWS, 256 threads; tree m of the workgroup has the 16-lane slot [16 m, 16 m + 16) -- the
+// threads that combined row m's value and logits --, of which the first G lanes work (lane = action; G-aligned, as the shuffles
+// of mz_group_argmax need).  sel_last: the descent behind the call's last simulation is made (the pool is not used up).
+// Every thread reaches every barrier: rows past B and the idle lanes are predicated, not returned.  The leaf's value and logits
+// are read from the body's LDS copies; tm.obs, written by lane 0 of a tree and read by the next inference's loader threads,
+// passes through global memory behind the barrier (the waves of a workgroup share the CU's L1; __syncthreads waits for the
+// outstanding stores).  Bound by the latency chain of 2 nsims dependent phases per workgroup.
+template <int JTP, int G>
+__global__ __launch_bounds__(256, 1) void k_tm_search(NetView n, TreeView t, TmState tm, const f32x4 *istream, int nst0,
+                                                       int nsims, int sel_last) {
+  static_assert(G <= 16, "one 16-lane slot per tree");
+  __shared__ __attribute__((aligned(16))) float smem[MZ_ROOT_LDS_FLOATS];
+  const float *s_val = smem + MZ_ROOT_LDS_VAL, *s_lg = s_val + 16;      // (mz_root_body's)
+  const int tid = (int)threadIdx.x, mt = tid >> 4, tl = tid & 15;
+  const int b = blockIdx.x * MZ_ROWS + mt;
+  const bool work = b < t.B && tl < G;
+  // lane 0's position record and legal bytes: in the observation tile, which is dead between the body's first stage and the next
+  // body's (both lie behind a barrier)
+  MzTmSlotBits *ws = (MzTmSlotBits *)smem + mt;
+  uint8_t *legal_ws = (uint8_t *)(smem + 16 * (sizeof(MzTmSlotBits) / sizeof(float))) + mt * MZ_GAME_MAX_ACTIONS;
+  static_assert(16 * sizeof(MzTmSlotBits) + 16 * MZ_GAME_MAX_ACTIONS <= 16 * MZ_ROOT_XS * sizeof(float), "inside the observation tile");
+  TreeView leaf_tv = t;      // the leaf inference's outputs land in the true-model state (as mz_tm_search's)
+  leaf_tv.root_value = tm.value;
+  leaf_tv.root_logits = tm.logits;
+  const SelfplayState no_sp = {};
+  for (int s = 0; s < nsims; ++s) {
+    mz_root_body<JTP, 4, false, 0>(n, leaf_tv, tm.obs, istream, nst0, no_sp, 0ull, 0.0, 0.0, smem, tid, nullptr, MzNoStamp(), nullptr);
+    __syncthreads();
+    if (work) {
+      mz_tm_expand_backup<G>(t, tm, b, tl, s_val[mt], s_lg + mt * 32);
+      if (s + 1 < nsims || sel_last) {
+        __threadfence_block();          // lane 0's node and slot updates -> visible to the group's other lanes
+        mz_tm_select<G, true>(t, tm, n.O, b, tl, ws, legal_ws);
+      }
+    }
+    __syncthreads();
   }
 }

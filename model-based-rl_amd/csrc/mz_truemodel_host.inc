@@ -59,7 +59,8 @@ int mz_tm_search_host(const mz_config *cfg, int kind, int n, const int8_t *board
         for (int k = 0; k < O; ++k) obs[(size_t)b * O + k] = 0.f;
       } else {
         u = sl[d.slot];
-        mz_tm_leaf(kind, u, d.act, O, A, obs.data() + (size_t)b * O);
+        uint8_t legal[MZ_GAME_MAX_ACTIONS];
+        mz_tm_leaf(kind, u, d.act, O, A, obs.data() + (size_t)b * O, legal);
       }
     }
     eval(ctx, obs.data(), n, value.data(), logits.data());

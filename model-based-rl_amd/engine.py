@@ -520,6 +520,11 @@ class Engine(object):
     n = self.sims if num_simulations is None else int(num_simulations)
     _abi.check(self.lib.mz_tm_search(self._h, n, self.stream), 'mz_tm_search')
 
+  def tm_search_fused(self, num_simulations=None):
+    """mz_tm_search_fused (DESIGN s7k): tm_search's simulations in one launch, bit-identical trees"""
+    n = self.sims if num_simulations is None else int(num_simulations)
+    _abi.check(self.lib.mz_tm_search_fused(self._h, n, self.stream), 'mz_tm_search_fused')
+
   def tm_export(self):
     """mz_tm_export -> dict of numpy arrays per expansion slot: boards [B, sims + 1, 42], mover, step, mask, finished
     [B, sims + 1], and nexp [B]; EX [B, NN]: the nodes that exist (export_tree's EX counts every child of an expanded node)"""
@@ -891,6 +896,13 @@ class Engine(object):
       raise ValueError("selfplay_set_gumbel: value is 'mean' or 'vmix', got %r" % (value,))
     _abi.check(self.lib.mz_selfplay_set_gumbel(self._h, int(bool(on)), self.SELFPLAY_GUMBEL_VALUES[value]), 'mz_selfplay_set_gumbel')
     self.selfplay_gumbel = bool(on)
+
+  def selfplay_set_true_model(self, on=True, fused=True):
+    """mz_selfplay_set_true_model (DESIGN s7k): while on, the self-play moves of a device board game are PUCT moves searched on
+    the true rules (set_true_model with the game's kind first); fused: a move's simulations in one launch (tm_search_fused),
+    else tm_search's two launches per simulation, with the same records.  After selfplay_set_env, with the ring drained."""
+    _abi.check(self.lib.mz_selfplay_set_true_model(self._h, int(bool(on)), int(bool(fused))), 'mz_selfplay_set_true_model')
+    self.selfplay_true_model = bool(on)
 
   def selfplay_export_trees(self, keep=True):
     _abi.check(self.lib.mz_selfplay_export_trees(self._h, int(bool(keep))), 'mz_selfplay_export_trees')

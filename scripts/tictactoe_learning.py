@@ -8,12 +8,15 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
                                        [--environment ConnectFour] [--out profiles/r03_tictactoe_learning.json]
                                        [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]] [--true_model] [--gumbel]
                                        [--selfplay_gumbel [--num_simulations 8] [--selfplay_gumbel_value vmix] ...]
+                                       [--selfplay_true_model [--selfplay_true_model_loop]]
                                        [--reanalyse_rows N [--reanalyse_every K] [--reanalyse_gumbel [--reanalyse_gumbel_scale S]]]
 --reanalyse_rows / --reanalyse_every / --reanalyse_gumbel / --reanalyse_gumbel_scale are train's flags, passed on to the training run
 (--reanalyse_gumbel: Reanalyse with the Gumbel search for a --selfplay_gumbel run, reanalyse.py).
 --selfplay_gumbel adds train's flag (self-play searched with the Gumbel search, the learner trained on pi'; selfplay_gumbel.py) with
 its --selfplay_gumbel_* parameters, and --num_simulations sets the simulations of the TRAINING run's self-play; the evaluation
 blocks below stay as they are -- PUCT at 30 simulations unless --gumbel is given.
+--selfplay_true_model adds train's flag (self-play searched on the game's true rules below the root, selfplay_true_model.py;
+--selfplay_true_model_loop: its two-launch form) to the training run; the evaluation blocks stay as they are.
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).
 --symmetry adds train's flag (every sample trained on one of the equivalent images of its position, symmetry.py) to the training run.
@@ -127,6 +130,9 @@ def build_parser():
   ap.add_argument('--selfplay_gumbel_c_scale', type=float, default=None, help='train --selfplay_gumbel_c_scale')
   ap.add_argument('--selfplay_gumbel_scale', type=float, default=None, help='train --selfplay_gumbel_scale')
   ap.add_argument('--selfplay_gumbel_value', default=None, choices=['mean', 'vmix'], help='train --selfplay_gumbel_value')
+  ap.add_argument('--selfplay_true_model', action='store_true',
+                  help='train --selfplay_true_model: self-play searched on the true rules below the root; the evaluation blocks are unchanged')
+  ap.add_argument('--selfplay_true_model_loop', action='store_true', help='train --selfplay_true_model_loop')
   return ap
 
 
@@ -154,6 +160,8 @@ def recipe(a):
       v = getattr(a, 'selfplay_gumbel_' + k)
       if v is not None:
         extra += ['--selfplay_gumbel_' + k, str(v)]
+  if a.selfplay_true_model:
+    extra += ['--selfplay_true_model'] + (['--selfplay_true_model_loop'] if a.selfplay_true_model_loop else [])
   return base, extra
 
 
@@ -172,6 +180,8 @@ def main():
   from model_based_rl_amd.engine import flatten_weights
   if not a.selfplay_gumbel and any(getattr(a, 'selfplay_gumbel_' + k) is not None for k in ('considered', 'c_visit', 'c_scale', 'scale', 'value')):
     ap.error('--selfplay_gumbel_*: parameters of --selfplay_gumbel, which is not given.')
+  if a.selfplay_true_model_loop and not a.selfplay_true_model:
+    ap.error('--selfplay_true_model_loop: an option of --selfplay_true_model, which is not given.')
   base, extra = recipe(a)
   torch.manual_seed(0)
   untrained_sd = get_network(make_config(base), torch.device('cpu')).state_dict()
