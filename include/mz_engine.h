@@ -475,6 +475,11 @@ int mz_gz_expand_backup_select(mz_engine *e, const float *value, const float *re
 int mz_gz_search(mz_engine *e, int num_simulations, void *stream);
 int mz_gz_pick(mz_engine *e, int32_t *action, float *pred_reward, double *improved_policy, double *v_mix, void *stream);
 
+/* The self-play loop searches its moves in ONE mode (DESIGN s7l): PUCT on the learned model (the default), or one of the two
+ * below.  Switching one on while the other is on is refused; switching one off while the other is on succeeds and leaves the
+ * other on.  While a mode is on, the entry points named below refuse with one sentence that names the mode and the call that
+ * switches it off. */
+
 /* Self-play with the Gumbel search (DESIGN s7i; csrc/mz_gumbel_selfplay.hip.h).  While on, a move of mz_selfplay_steps /
  * mz_selfplay_steps_into on a device game (mz_selfplay_set_env 1, 2, 3) is: observe, initial inference, the root WITHOUT
  * exploration noise, mz_gz_root with G drawn on the device -- keyed (seed, env_id_offset + b, the environment's move counter,

@@ -11,8 +11,8 @@ import subprocess
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _SO = os.environ.get('MZ_HIP_LIB') or os.path.join(_CSRC, 'libmz_hip.so')      # (MZ_HIP_LIB: A/B runs of two builds on one box)
 _SOURCES = ['mz_engine.hip', 'mz_comm.inc', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_fcl_plan.inc', 'mz_fcl_sizes.h', 'mz_pack.inc', 'mz_stream_sizes.h', 'mz_inst.hip', 'mz_kernels.inc', 'mz_common.h', 'mz_games.h', 'mz_net.hip.h', 'mz_tree.hip.h', 'mz_tree_host.h', 'mz_rng.h', 'mz_eval.hip.h',
-            'mz_selfplay.hip.h', 'mz_selfplay_abi.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_playout.hip.h', 'mz_playout_abi.inc', 'mz_solve.hip.h', 'mz_solve_abi.inc', 'mz_unroll.hip.h', 'mz_unroll_abi.inc', 'mz_truemodel.hip.h', 'mz_truemodel_abi.inc', 'mz_truemodel_host.inc', 'mz_gumbel.hip.h', 'mz_gumbel_selfplay.hip.h', 'mz_gumbel_abi.inc', 'mz_gumbel_host.inc', 'mz_fused.hip.h', 'mz_root.hip.h', 'mz_fused_h2.hip.h', 'mz_symmetry.hip.h']
-_ENGINE_ONLY = ('mz_engine.hip', 'mz_tree_host.h', 'mz_comm.inc', 'mz_eval.hip.h', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_fcl_plan.inc', 'mz_fcl_sizes.h', 'mz_pack.inc', 'mz_selfplay_abi.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_playout.hip.h', 'mz_playout_abi.inc', 'mz_solve.hip.h', 'mz_solve_abi.inc', 'mz_unroll.hip.h', 'mz_unroll_abi.inc', 'mz_truemodel.hip.h', 'mz_truemodel_abi.inc', 'mz_truemodel_host.inc', 'mz_gumbel.hip.h', 'mz_gumbel_selfplay.hip.h', 'mz_gumbel_abi.inc', 'mz_gumbel_host.inc', 'mz_symmetry.hip.h')      # included by mz_engine.hip alone
+            'mz_selfplay.hip.h', 'mz_selfplay_abi.inc', 'mz_selfplay_mode.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_playout.hip.h', 'mz_playout_abi.inc', 'mz_solve.hip.h', 'mz_solve_abi.inc', 'mz_unroll.hip.h', 'mz_unroll_abi.inc', 'mz_truemodel.hip.h', 'mz_truemodel_abi.inc', 'mz_truemodel_host.inc', 'mz_gumbel.hip.h', 'mz_gumbel_selfplay.hip.h', 'mz_gumbel_abi.inc', 'mz_gumbel_host.inc', 'mz_fused.hip.h', 'mz_root.hip.h', 'mz_fused_h2.hip.h', 'mz_symmetry.hip.h']
+_ENGINE_ONLY = ('mz_engine.hip', 'mz_tree_host.h', 'mz_comm.inc', 'mz_eval.hip.h', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_fcl_plan.inc', 'mz_fcl_sizes.h', 'mz_pack.inc', 'mz_selfplay_abi.inc', 'mz_selfplay_mode.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_playout.hip.h', 'mz_playout_abi.inc', 'mz_solve.hip.h', 'mz_solve_abi.inc', 'mz_unroll.hip.h', 'mz_unroll_abi.inc', 'mz_truemodel.hip.h', 'mz_truemodel_abi.inc', 'mz_truemodel_host.inc', 'mz_gumbel.hip.h', 'mz_gumbel_selfplay.hip.h', 'mz_gumbel_abi.inc', 'mz_gumbel_host.inc', 'mz_symmetry.hip.h')      # included by mz_engine.hip alone
 _lib = None
 
 HIPCC_FLAGS = ['-O3', '--offload-arch=gfx950', '-ffp-contract=off', '-std=c++17', '-fPIC', '-Wno-unused-value',

@@ -23,7 +23,7 @@ import os
 from .engine import Engine, flatten_weights, records_view
 from .config import CARTPOLE_TIME_LIMITS
 from .envs import get_environment, KIND_OF_ENV
-from .selfplay_gumbel import selfplay_gumbel_params
+from . import selfplay_search
 from .logger import Logger
 from .networks import get_network
 
@@ -409,12 +409,7 @@ class Actor(Logger):
                              packed=ram and bool(getattr(cfg, 'obs_u8', False)))      # (bytes in the records: a replay with obs_u8)
       if cfg.environment in KIND_OF_ENV:      # (refuses the wrong number of players, and --norm_obs where the game is not built for it: the engine's sentence surfaces)
         eng.selfplay_set_env(KIND_OF_ENV[cfg.environment])
-      if getattr(cfg, 'selfplay_gumbel', False):      # the moves are searched with the Gumbel search, the records carry pi' (DESIGN s7i)
-        eng.set_gumbel(True, *selfplay_gumbel_params(cfg))
-        eng.selfplay_set_gumbel(True, getattr(cfg, 'selfplay_gumbel_value', 'mean'))
-      if getattr(cfg, 'selfplay_true_model', False):      # PUCT moves searched on the game's true rules (DESIGN s7k)
-        eng.set_true_model(KIND_OF_ENV[cfg.environment])
-        eng.selfplay_set_true_model(True, fused=not getattr(cfg, 'selfplay_true_model_loop', False))
+      selfplay_search.configure(eng, cfg)      # --selfplay_gumbel / --selfplay_true_model: how the moves are searched (DESIGN s7l)
       # (CartPole: the episode length is the environment's time limit, whatever --episode_length says)
       eng.selfplay_reset(CARTPOLE_TIME_LIMITS.get(cfg.environment, cfg.episode_length), temperature, stagger=True)
       self._selfplay_temperature = temperature

@@ -160,7 +160,7 @@ def build_parser():
   a('--selfplay_gumbel', action='store_true',
     help='TicTacToe / ConnectFour / CartPole-v0 / -v1 on the device: the self-play moves are searched with the Gumbel MuZero '
          'search at --num_simulations (8 or 16 are its range), the records carry the improved policy pi\' as the policy target and '
-         'the Gumbel pick as the action; the visit-softmax temperature plays no part (selfplay_gumbel.py; evaluation keeps its '
+         'the Gumbel pick as the action; the visit-softmax temperature plays no part (selfplay_search.py; evaluation keeps its '
          'own --gumbel flags)')
   a('--selfplay_gumbel_considered', type=int, default=16, help='--selfplay_gumbel: the actions sequential halving starts from (at least 2)')
   a('--selfplay_gumbel_c_visit', type=float, default=50.0, help='--selfplay_gumbel: sigma = (c_visit + max visits) * c_scale * normalised Q')
@@ -172,7 +172,7 @@ def build_parser():
   a('--selfplay_true_model', action='store_true',
     help='TicTacToe / ConnectFour on the device: the self-play moves are PUCT moves searched on the TRUE rules below the root '
          '(real positions, legal moves only, the game\'s end), AlphaZero\'s search feeding MuZero\'s learner; records, learner and '
-         'checkpoint are unchanged (selfplay_true_model.py; evaluation keeps its own --true_model flag)')
+         'checkpoint are unchanged (selfplay_search.py; evaluation keeps its own --true_model flag)')
   a('--selfplay_true_model_loop', action='store_true',
     help='--selfplay_true_model: two launches per simulation (mz_tm_search) instead of one launch per move (mz_tm_search_fused); '
          'the records are the same')

@@ -27,6 +27,7 @@
 #include "mz_tree.hip.h"
 #include "mz_selfplay.hip.h"
 #include "mz_selfplay_ring.inc"   // MZ_GRAPH_MOVES, RecordRing
+#include "mz_selfplay_mode.inc"   // MzSpMode, mz_sp_refusal, mz_sp_switch_ok
 #include "mz_fused.hip.h"
 #include "mz_root.hip.h"
 #include "mz_fused_h2.hip.h"
@@ -173,10 +174,9 @@ struct mz_engine {
   TmState tm = {};                  // the true-rules search (mz_set_true_model, mz_tm_*; mz_truemodel.hip.h), allocated when set
   GzState gz = {};                  // the Gumbel search (mz_set_gumbel, mz_gz_*; mz_gumbel.hip.h), allocated when set
   bool root_noise = false;          // the last mz_root_prepare mixed exploration noise into the root's priors
-  bool sp_gumbel = false;           // the self-play loop's moves are searched with the Gumbel search (mz_selfplay_set_gumbel; DESIGN s7i)
-  int sp_gumbel_value = 0;          // ... and their records' root_value: 0 the root's mean value, 1 its v_mix
-  bool sp_tm = false;               // the self-play loop's moves are searched on the true rules (mz_selfplay_set_true_model; DESIGN s7k)
-  bool sp_tm_fused = false;         // ... all simulations of a move in one launch of k_tm_search (else the two-launch loop)
+  MzSpMode sp_mode = MZ_SP_PUCT;    // how the self-play loop's moves are searched (mz_selfplay_mode.inc; DESIGN s7l)
+  int sp_gumbel_value = 0;          // MZ_SP_GUMBEL: the records' root_value, 0 the root's mean value, 1 its v_mix
+  bool sp_tm_fused = false;         // MZ_SP_TRUE_RULES: all simulations of a move in one launch of k_tm_search (else the two-launch loop)
 };
 
 // Every ABI entry runs on the engine's own device, whatever the calling thread's current device is (an engine may be
@@ -518,7 +518,7 @@ static SearchPlan search_plan(const mz_engine *e) {
   // trees, compact placement); a game environment without such an instantiation for its shape and
   // placement, or with split_f16, plays in the launch-per-step form (launch_move_game), and so does every move searched with
   // the Gumbel search (mz_selfplay_set_gumbel) or on the true rules (mz_selfplay_set_true_model)
-  p.persist = !e->sp_gumbel && !e->sp_tm && e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
+  p.persist = e->sp_mode == MZ_SP_PUCT && e->use_persist && fused_usable(e) && p.lt != 0 && lds_fits(p.lds_static, p.dyn_head) &&
               (p.game ? !e->split_f16 && !!e->cfg.two_players == (p.game != 2) &&
                             find_kernel(1, *p.shape, p.lt, false, p.sp, true, true) != nullptr
                       : p.sp && !e->sp.env_kind);
@@ -619,6 +619,15 @@ static int step_advance(mz_engine *e, const char *fn, bool ready, const char *se
   e->sims_done += 1;
   e->selection_valid = more;
   return 0;
+}
+// a new root: the protocol starts over, no simulation done and the root's first descent pending.  noise: exploration noise is in the
+// root's priors; variant: the search whose own root kernel the caller launched as well (a self-play move; MZ_SP_PUCT: none yet)
+static void step_restart(mz_engine *e, bool noise, MzSpMode variant = MZ_SP_PUCT) {
+  e->sims_done = 0;
+  e->selection_valid = e->root_ready = true;
+  e->root_noise = noise;
+  e->gz.root_set = variant == MZ_SP_GUMBEL;
+  e->tm.root_set = variant == MZ_SP_TRUE_RULES;
 }
 
 // what the last descent left, for the caller; any may be null (one launch: four D2D blits cost 4 x 4 us per simulation)
@@ -1034,12 +1043,7 @@ int mz_root_prepare(mz_engine *e, const int8_t *to_play, const uint8_t *legal, c
   }
   TREE_LAUNCH(k_tree_root, s, e->tv, to_play, legal, nz, e->cfg.root_exploration_fraction, 1);
   HIPCHECK(hipGetLastError());
-  e->sims_done = 0;
-  e->selection_valid = true;
-  e->root_ready = true;
-  e->tm.root_set = false;
-  e->gz.root_set = false;
-  e->root_noise = nz != nullptr;
+  step_restart(e, nz != nullptr);
   return 0;
 }
 
@@ -1393,12 +1397,18 @@ int mz_export_tree(mz_engine *e, int32_t *N, double *W, double *P, float *R, int
   return 0;
 }
 
-#include "mz_selfplay_abi.inc"
+// whether engine e can play the game `kind` (mz_game_shape_ok); if not, the failure is fn's: "<fn>: <Name> needs ..."
+static int game_shape(const mz_engine *e, const char *fn, int kind) {
+  char why[96];
+  return mz_game_shape_ok(kind, e->O, e->A, e->cfg.two_players != 0, why, sizeof why) ? 0 : fail("%s: %s", fn, why);
+}
+
 #include "mz_playout_abi.inc"
 #include "mz_solve_abi.inc"
 #include "mz_unroll_abi.inc"
 #include "mz_truemodel_abi.inc"
 #include "mz_gumbel_abi.inc"
+#include "mz_selfplay_abi.inc"      // (after the two searches a game move chooses between: launch_move_game)
 #include "mz_eval_abi.inc"
 #include "mz_match_abi.inc"
 #include "mz_reanalyse_abi.inc"

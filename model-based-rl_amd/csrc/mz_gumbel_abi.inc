@@ -7,7 +7,7 @@ int mz_set_gumbel(mz_engine *e, int on, int max_considered, double c_visit, doub
   if (!e) return fail("mz_set_gumbel: null engine");
   MZ_ENTER(e);
   GzState &gz = e->gz;
-  if (!on && e->sp_gumbel) return fail("mz_set_gumbel: the self-play loop searches with the Gumbel search on this engine (mz_selfplay_set_gumbel 0 first)");
+  if (!on && e->sp_mode == MZ_SP_GUMBEL) return fail("mz_set_gumbel: the self-play loop searches with the Gumbel search on this engine (mz_selfplay_set_gumbel 0 first)");
   if (!on) { gz.on = 0; gz.root_set = false; return 0; }
   if (e->tm.kind) return fail("mz_set_gumbel: the true-rules search is set on this engine; an engine takes one of the two (mz_set_true_model 0 first)");
   if (max_considered < 2) return fail("mz_set_gumbel: max_considered must be >= 2, got %d", max_considered);
@@ -25,7 +25,7 @@ int mz_set_gumbel(mz_engine *e, int on, int max_considered, double c_visit, doub
     gz.seq = seq;
   }
   gz.par = GzPar{max_considered, c_visit, c_scale, gumbel_scale};
-  if (e->sp_gumbel) drop_graphs(e, false);      // (captured self-play moves hold the parameters by value)
+  if (e->sp_mode == MZ_SP_GUMBEL) drop_graphs(e, false);      // (captured self-play moves hold the parameters by value)
   gz.on = 1;
   gz.root_set = false;
   return 0;
@@ -58,7 +58,7 @@ static int gz_step(mz_engine *e, const char *fn, const float *value, const float
                       [&](bool m) { GZ_LAUNCH(k_gz_step, s, value, reward, logits, hidden, m ? 1 : 0, e->sims_done + 1); });
 }
 
-// n simulations behind a pending descent (mz_gz_search, and a self-play move of mz_selfplay_set_gumbel): the recurrent
+// n simulations behind a pending descent (mz_gz_search, and a self-play move of mz_selfplay_set_gumbel: launch_move_game): the recurrent
 // inference on the rows the descent left (parent hidden state, action), then the tree step with the next descent
 static int gz_simulations(mz_engine *e, const char *fn, int n, hipStream_t s) {
   const GzState &gz = e->gz;
@@ -143,68 +143,6 @@ int mz_gz_export(mz_engine *e, double *gumbel, float *vhat) {
   HIPCHECK(hipDeviceSynchronize());
   if (gumbel) HIPCHECK(hipMemcpy(gumbel, e->gz.G, (size_t)e->B * e->A * sizeof(double), hipMemcpyDeviceToHost));
   if (vhat) HIPCHECK(hipMemcpy(vhat, e->gz.vhat, (size_t)e->B * (e->sims + 1) * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
-}
-// ---- self-play with this search (DESIGN s7i; the end-of-move kernels: mz_gumbel_selfplay.hip.h)
-// One self-play move of a device game, on the stream, no host round trip: observe, initial inference, the root WITHOUT
-// exploration noise (no first PUCT descent either: k_gz_root makes the move's first descent), the Gumbel root with the move
-// read from the environments' counter -- what keys the Dirichlet draw of a PUCT move, so a record does not depend on its batch
-// and a captured graph draws afresh at every replay --, all the simulations, and the end of the move in one launch.  The host
-// side of the step protocol starts over at every move, so that k moves may follow one another inside one chunk or one capture;
-// the kernels' arguments are the same at every move.
-static int launch_move_gumbel(mz_engine *e, hipStream_t s) {
-  SelfplayState &sp = e->sp;
-  const int B = e->B, A = e->A;
-  hipLaunchKernelGGL(k_game_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, e->O, A);
-  if (launch_root(e, sp.obs, false, s)) return -1;
-  TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, (const double *)nullptr,
-              e->cfg.root_exploration_fraction, 0);
-  GZ_LAUNCH(k_gz_root, s, (const double *)nullptr, (uint64_t)e->cfg.seed, (uint64_t)0, (const unsigned long long *)sp.movecnt,
-            sp.env_offset);
-  HIPCHECK(hipGetLastError());
-  e->sims_done = 0;
-  e->root_ready = true;
-  e->root_noise = false;
-  e->tm.root_set = false;
-  e->gz.root_set = true;
-  e->selection_valid = true;
-  if (gz_simulations(e, "mz_selfplay_steps", e->sims, s)) return -1;
-#define GZ_MOVE(G_, KIND_)                                                                                                \
-  hipLaunchKernelGGL((k_gz_move_record<G_, KIND_>), dim3(B), dim3(64), 0, s, e->tv, e->gz, sp, e->sp_gumbel_value, \
-                     (uint64_t)e->cfg.seed)
-#define GZ_MOVE_G(KIND_)                    \
-  switch (e->G) {                           \
-    case 4: GZ_MOVE(4, KIND_); break;       \
-    case 8: GZ_MOVE(8, KIND_); break;       \
-    case 16: GZ_MOVE(16, KIND_); break;     \
-    default: GZ_MOVE(32, KIND_); break;     \
-  }
-  if (sp.env_kind == 2) { GZ_MOVE_G(2) }
-  else if (sp.env_kind == 3) { GZ_MOVE_G(3) }
-  else { GZ_MOVE_G(1) }
-#undef GZ_MOVE_G
-#undef GZ_MOVE
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-int mz_selfplay_set_gumbel(mz_engine *e, int on, int value_kind) {
-  if (!e) return fail("mz_selfplay_set_gumbel: null engine");
-  MZ_ENTER(e);
-  if (on) {
-    if (e->sp_tm) return fail("mz_selfplay_set_gumbel: the self-play moves are searched on the true rules (mz_selfplay_set_true_model 0 first)");
-    if (value_kind != 0 && value_kind != 1) return fail("mz_selfplay_set_gumbel: value_kind %d (0 the root's mean value, 1 its v_mix)", value_kind);
-    if (!e->gz.on) return fail("mz_selfplay_set_gumbel: no Gumbel search is set on this engine (call mz_set_gumbel first)");
-    if (!e->sp.env_kind) return fail("mz_selfplay_set_gumbel: the Gumbel self-play runs on the device games; set one first (mz_selfplay_set_env 1, 2 or 3)");
-    if (e->draws_set) return fail("mz_selfplay_set_gumbel: host-given draws are set (mz_selfplay_set_draws); the Gumbel search draws its own noise on the device");
-    if (e->tv.sim_io) return fail("mz_selfplay_set_gumbel: mz_sim_io instruments the fused search kernels, which this mode does not run (mz_sim_io 0 first)");
-  }
-  if (e->ring.undrained()) return fail("mz_selfplay_set_gumbel: %llu moves wait in the device ring; drain them first", e->ring.undrained());
-  HIPCHECK(hipDeviceSynchronize());      // (moves in flight were launched under the other plan)
-  e->sp_gumbel = on != 0;
-  e->sp_gumbel_value = on ? value_kind : 0;
-  e->gz.root_set = false;
-  drop_graphs(e, false);
   return 0;
 }
 #undef GZ_LAUNCH

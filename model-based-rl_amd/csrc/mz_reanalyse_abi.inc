@@ -106,12 +106,7 @@ int mz_reanalyse_gumbel(mz_engine *e, int kind, const float *rows_host, int rec_
     TREE_LAUNCH(k_gz_root, s, e->tv, e->gz, (const double *)nullptr, (uint64_t)e->cfg.seed, draw_key,
                 (const unsigned long long *)nullptr, at);
     HIPCHECK(hipGetLastError());
-    e->sims_done = 0;
-    e->root_ready = true;
-    e->root_noise = false;
-    e->tm.root_set = false;
-    e->gz.root_set = true;
-    e->selection_valid = true;
+    step_restart(e, false, MZ_SP_GUMBEL);
     if (gz_simulations(e, "mz_reanalyse_gumbel", num_simulations, s)) return -1;
 #define RA_STORE(G_)                                                                                                     \
   hipLaunchKernelGGL(k_reanalyse_store_gumbel<G_>, dim3(B), dim3(64), 0, s, e->tv, e->gz, fresh_dev + (size_t)at * (A + 2), n, \

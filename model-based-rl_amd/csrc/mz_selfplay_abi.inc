@@ -2,10 +2,10 @@
 // mz_engine.hip).  Replaces the per-move body of Actor.play_game (reference actors.py:131-173) for B
 // synthetic environments; the history hand-off to the replay buffer (actors.py:160-169) is the drain.
 
-// whether engine e can play the game `kind` (mz_game_shape_ok); if not, the failure is fn's: "<fn>: <Name> needs ..."
-static int game_shape(const mz_engine *e, const char *fn, int kind) {
-  char why[96];
-  return mz_game_shape_ok(kind, e->O, e->A, e->cfg.two_players != 0, why, sizeof why) ? 0 : fail("%s: %s", fn, why);
+// while the moves are not searched with PUCT on the learned model (mz_selfplay_mode.inc), fn refuses: the one sentence of the mode
+static int refuse_searched(const mz_engine *e, const char *fn, const char *why) {
+  char buf[256];
+  return e->sp_mode == MZ_SP_PUCT ? 0 : fail("%s", mz_sp_refusal(buf, sizeof buf, fn, e->sp_mode, why));
 }
 
 static int selfplay_alloc(mz_engine *e) {
@@ -73,30 +73,53 @@ int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int sta
   return 0;
 }
 
-// One move of a game environment (mz_selfplay_set_env): every step of actors.py:131-158 is its own launch here --
-// observe, initial inference on that observation, Dirichlet draw over the legal actions (or the host's draw), root
-// expansion + first descent, the two-player search kernel, end of move with the real env.step -- all on the stream, no
-// host round trip; up to 16 moves per hipGraph like every other configuration.
-static int launch_move_gumbel(mz_engine *e, hipStream_t s);      // (mz_gumbel_abi.inc: the move of mz_selfplay_set_gumbel)
-static int launch_move_true_model(mz_engine *e, hipStream_t s);      // (mz_truemodel_abi.inc: the move of mz_selfplay_set_true_model)
+// One move of a game environment (mz_selfplay_set_env), the only statement of it (DESIGN s7l): every step of actors.py:131-158 is its own
+// launch here -- observe, initial inference on that observation, the root with its noise, the search of the loop's mode, end of move with the
+// real env.step --, on the stream, no host round trip, the same arguments at every move; up to 16 moves per hipGraph like every other configuration.
 static int launch_move_game(mz_engine *e, const SearchOpts &o, hipStream_t s) {
-  if (e->sp_gumbel) return launch_move_gumbel(e, s);
-  if (e->sp_tm) return launch_move_true_model(e, s);
   SelfplayState &sp = e->sp;
   const int B = e->B, A = e->A;
-  const bool cart = sp.env_kind == 2, c4 = sp.env_kind == 3;
-  hipLaunchKernelGGL(k_game_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, e->O, A);
+  const MzSpMode mode = e->sp_mode;
+  const dim3 per_env((B + 127) / 128), threads(128);
+  hipLaunchKernelGGL(k_game_observe, per_env, threads, 0, s, sp, B, e->O, A);
   if (launch_root(e, sp.obs, false, s)) return -1;
-  if (!e->draws_noise)
-    hipLaunchKernelGGL(k_dirichlet, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, (const uint8_t *)sp.legal,
-                       e->cfg.root_dirichlet_alpha, e->cfg.seed, 0ull, (const unsigned long long *)sp.movecnt, sp.env_offset);
+  // the root's noise: the Dirichlet draw over the legal actions, keyed by the environments' move counter -- a record does not depend on its batch, a
+  // captured graph draws afresh at every replay --, or the host's draw (PUCT only); none, and no first PUCT descent, at the Gumbel root: k_gz_root's
+  const bool noise = mode != MZ_SP_GUMBEL;
+  if (noise && !e->draws_noise)
+    hipLaunchKernelGGL(k_dirichlet, per_env, threads, 0, s, e->tv, (const uint8_t *)sp.legal, e->cfg.root_dirichlet_alpha, e->cfg.seed, 0ull,
+                       (const unsigned long long *)sp.movecnt, sp.env_offset);
   // (a timed run clocks the search kernel's dispatch, not the root's)
-  TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, (const double *)e->tv.noise,
-              e->cfg.root_exploration_fraction, 1);
-  if (launch_search(e, o, true, s)) return -1;
-  if (cart) hipLaunchKernelGGL(k_cartpole_step_record, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
-  else if (c4) hipLaunchKernelGGL(k_board_step_record<3>, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
-  else hipLaunchKernelGGL(k_board_step_record<1>, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
+  TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, noise ? (const double *)e->tv.noise : nullptr,
+              e->cfg.root_exploration_fraction, noise ? 1 : 0);
+  // the mode's own root and its simulations; the step protocol's host side starts over at every move: k moves follow one another in a chunk or a capture
+  if (mode != MZ_SP_PUCT) step_restart(e, noise, mode);
+  if (mode == MZ_SP_GUMBEL) {      // G drawn under the move read from the environments' counter, what keys a PUCT move's Dirichlet draw
+    TREE_LAUNCH(k_gz_root, s, e->tv, e->gz, (const double *)nullptr, (uint64_t)e->cfg.seed, (uint64_t)0, (const unsigned long long *)sp.movecnt,
+                sp.env_offset);
+    if (gz_simulations(e, "mz_selfplay_steps", e->sims, s)) return -1;
+  } else if (mode == MZ_SP_TRUE_RULES) {      // the root's position from the environment itself; one launch of k_tm_search, or the two-launch loop
+    TREE_LAUNCH(k_tm_root_selfplay, s, e->tv, e->tm, e->O, sp);
+    if (e->sp_tm_fused ? tm_simulations_fused(e, "mz_selfplay_steps", e->sims, s) : tm_simulations(e, "mz_selfplay_steps", e->sims, s)) return -1;
+  } else if (launch_search(e, o, true, s)) return -1;      // PUCT on the learned model: the search kernel
+  // the end of the move.  Gumbel: pick, pi' in the policy slots and env.step in one launch (mz_gumbel_selfplay.hip.h); else the PUCT move's (the true-rules tree is in the engine's own node records)
+#define GZ_MOVE(G_, KIND_) \
+  hipLaunchKernelGGL((k_gz_move_record<G_, KIND_>), dim3(B), dim3(64), 0, s, e->tv, e->gz, sp, e->sp_gumbel_value, (uint64_t)e->cfg.seed)
+#define GZ_MOVE_G(KIND_)                    \
+  switch (e->G) {                           \
+    case 4: GZ_MOVE(4, KIND_); break;       \
+    case 8: GZ_MOVE(8, KIND_); break;       \
+    case 16: GZ_MOVE(16, KIND_); break;     \
+    default: GZ_MOVE(32, KIND_); break;     \
+  }
+  if (mode == MZ_SP_GUMBEL && sp.env_kind == 2) { GZ_MOVE_G(2) }
+  else if (mode == MZ_SP_GUMBEL && sp.env_kind == 3) { GZ_MOVE_G(3) }
+  else if (mode == MZ_SP_GUMBEL) { GZ_MOVE_G(1) }
+  else if (sp.env_kind == 2) hipLaunchKernelGGL(k_cartpole_step_record, per_env, threads, 0, s, e->tv, sp, B, A, e->cfg.seed);
+  else if (sp.env_kind == 3) hipLaunchKernelGGL(k_board_step_record<3>, per_env, threads, 0, s, e->tv, sp, B, A, e->cfg.seed);
+  else hipLaunchKernelGGL(k_board_step_record<1>, per_env, threads, 0, s, e->tv, sp, B, A, e->cfg.seed);
+#undef GZ_MOVE_G
+#undef GZ_MOVE
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -204,8 +227,7 @@ int mz_selfplay_set_env(mz_engine *e, int kind) {
   if (!e) return fail("mz_selfplay_set_env: null engine");
   MZ_ENTER(e);
   if (kind < 0 || kind > 3) return fail("mz_selfplay_set_env: unknown environment %d (0 synthetic, 1 TicTacToe, 2 CartPole, 3 Connect Four)", kind);
-  if (e->sp_gumbel) return fail("mz_selfplay_set_env: the self-play moves are searched with the Gumbel search, set for the current game (mz_selfplay_set_gumbel 0 first)");
-  if (e->sp_tm) return fail("mz_selfplay_set_env: the self-play moves are searched on the true rules of the current game (mz_selfplay_set_true_model 0 first)");
+  if (refuse_searched(e, "mz_selfplay_set_env", "set for the current game")) return -1;
   if (kind != 0 && game_shape(e, "mz_selfplay_set_env", kind)) return -1;
   if (kind == 3 && e->sp.obs_u8 == 2)
     return fail("mz_selfplay_set_env: packed byte observations are for the synthetic -ram- environments");
@@ -238,8 +260,7 @@ int mz_selfplay_set_draws(mz_engine *e, const double *noise, const double *unifo
   if (!e) return fail("mz_selfplay_set_draws: null engine");
   MZ_ENTER(e);
   if (e->sp.env_kind != 1) return fail("mz_selfplay_set_draws: only for the TicTacToe environment (mz_selfplay_set_env)");
-  if (e->sp_gumbel) return fail("mz_selfplay_set_draws: the self-play moves are searched with the Gumbel search, which draws its own noise on the device (mz_selfplay_set_gumbel 0 first)");
-  if (e->sp_tm) return fail("mz_selfplay_set_draws: the self-play moves are searched on the true rules, a mode that draws its noise on the device (mz_selfplay_set_true_model 0 first)");
+  if (refuse_searched(e, "mz_selfplay_set_draws", "a mode that draws its noise on the device")) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (noise) HIPCHECK(hipMemcpyAsync(e->tv.noise, noise, (size_t)e->B * e->A * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (uniform) HIPCHECK(hipMemcpyAsync(e->draw_uniform, uniform, (size_t)e->B * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -249,6 +270,24 @@ int mz_selfplay_set_draws(mz_engine *e, const double *noise, const double *unifo
   e->draws_set = noise || uniform;
   return 0;
 }
+
+// ---- how the moves are searched (mz_selfplay_mode.inc; DESIGN s7l).  Both switches: the facts, mz_sp_switch_ok's sentence, then the new mode and its parameter par
+static int selfplay_set_mode(mz_engine *e, const char *fn, MzSpMode which, int on, int par) {
+  if (!e) return fail("%s: null engine", fn);
+  MZ_ENTER(e);
+  const MzSpFacts facts = {e->sp_mode, e->sp.env_kind, e->gz.on != 0, e->tm.kind, e->draws_set, e->tv.sim_io != nullptr, e->ring.undrained()};
+  char why[256];
+  MzSpMode next = e->sp_mode;
+  if (!mz_sp_switch_ok(facts, fn, which, on != 0, par, &next, why, sizeof why)) return fail("%s", why);
+  HIPCHECK(hipDeviceSynchronize());      // (moves in flight were launched under the other plan)
+  e->sp_mode = next;
+  if (which == MZ_SP_GUMBEL) { e->sp_gumbel_value = on ? par : 0; e->gz.root_set = false; }
+  else { e->sp_tm_fused = on != 0 && par != 0; e->tm.root_set = false; }
+  drop_graphs(e, false);
+  return 0;
+}
+int mz_selfplay_set_gumbel(mz_engine *e, int on, int value_kind) { return selfplay_set_mode(e, "mz_selfplay_set_gumbel", MZ_SP_GUMBEL, on, value_kind); }
+int mz_selfplay_set_true_model(mz_engine *e, int on, int fused) { return selfplay_set_mode(e, "mz_selfplay_set_true_model", MZ_SP_TRUE_RULES, on, fused); }
 
 // keep != 0: every move of the self-play loop also stores its Dirichlet draw in a per-move log (as many moves as the
 // experience ring holds); mz_selfplay_read_noise fetches the draw of one move.  Test instrumentation: a move played in the
@@ -280,8 +319,7 @@ int mz_sim_io(mz_engine *e, int mode, float *buf, int keep_moves) {
   MZ_ENTER(e);
   if (mode < 0 || mode > 2) return fail("mz_sim_io: mode %d (0 off, 1 log, 2 inject)", mode);
   if (mode && (!buf || keep_moves < 1)) return fail("mz_sim_io: a buffer of keep_moves >= 1 moves is required");
-  if (mode && e->sp_gumbel) return fail("mz_sim_io: the self-play moves are searched with the Gumbel search, which the fused kernels do not run (mz_selfplay_set_gumbel 0 first)");
-  if (mode && e->sp_tm) return fail("mz_sim_io: the self-play moves are searched on the true rules, which the fused kernels do not run (mz_selfplay_set_true_model 0 first)");
+  if (mode && refuse_searched(e, "mz_sim_io", "which the fused kernels do not run")) return -1;
   HIPCHECK(hipDeviceSynchronize());
   e->tv.sim_io = mode ? buf : nullptr;
   e->tv.sim_io_keep = mode == 2 ? -keep_moves : (mode == 1 ? keep_moves : 0);
@@ -434,8 +472,8 @@ int mz_selfplay_steps_timed(mz_engine *e, int k, float *ms_out, void *stream) {
   if (!e || !ms_out) return fail("mz_selfplay_steps_timed: null argument");
   MZ_ENTER(e);
   hipStream_t s = (hipStream_t)stream;
-  const char *own = e->sp_gumbel ? "the moves are searched with the Gumbel search, which has no single search dispatch to clock" :
-                    e->sp_tm ? "the moves are searched on the true rules, a search without a clocked dispatch (mz_selfplay_set_true_model 0 first)" :
+  char searched[256];      // (produce_begin puts the name in front)
+  const char *own = e->sp_mode != MZ_SP_PUCT ? mz_sp_refusal(searched, sizeof searched, nullptr, e->sp_mode, "a search without a clocked dispatch", "the moves") :
                     fused_usable(e) ? nullptr : "fused kernel not in use";
   const int brc = produce_begin(e, "mz_selfplay_steps_timed", own, k, INT_MAX, true, s);
   if (brc > 0) return fail("mz_selfplay_steps_timed: %d moves do not fit the undrained ring", k);

@@ -9,7 +9,7 @@ int mz_set_true_model(mz_engine *e, int kind) {
   if (kind != 0 && kind != 1 && kind != 3)
     return fail("mz_set_true_model: kind must be 0 (off), 1 (TicTacToe) or 3 (Connect Four), got %d", kind);
   if (kind != 0 && game_shape(e, "mz_set_true_model", kind)) return -1;
-  if (kind != e->tm.kind && e->sp_tm)
+  if (kind != e->tm.kind && e->sp_mode == MZ_SP_TRUE_RULES)
     return fail("mz_set_true_model: the self-play loop searches the true rules of the current game on this engine (mz_selfplay_set_true_model 0 first)");
   if (kind != 0 && e->gz.on) return fail("mz_set_true_model: the Gumbel search is set on this engine; an engine takes one of the two (mz_set_gumbel off first)");
   TmState &tm = e->tm;
@@ -152,57 +152,6 @@ int mz_tm_export(mz_engine *e, int8_t *boards, int8_t *mover, int32_t *step, uin
   return 0;
 }
 
-// ---- self-play on the true rules (DESIGN s7k)
-// One self-play move of a board game whose search runs on the true rules, on the stream, no host round trip: a PUCT move's
-// observe, initial inference, Dirichlet draw keyed by the environments' move counter and root (launch_move_game), then the root's
-// position from the environment itself (k_tm_root_selfplay), all the simulations -- one launch of k_tm_search, or the two-launch
-// loop --, and the PUCT move's end, unchanged: the true-rules tree lives in the engine's own node records.  The host side of the
-// step protocol starts over at every move, so that k moves may follow one another inside one chunk or one capture.
-static int launch_move_true_model(mz_engine *e, hipStream_t s) {
-  SelfplayState &sp = e->sp;
-  const int B = e->B, A = e->A;
-  hipLaunchKernelGGL(k_game_observe, dim3((B + 127) / 128), dim3(128), 0, s, sp, B, e->O, A);
-  if (launch_root(e, sp.obs, false, s)) return -1;
-  hipLaunchKernelGGL(k_dirichlet, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, (const uint8_t *)sp.legal,
-                     e->cfg.root_dirichlet_alpha, e->cfg.seed, 0ull, (const unsigned long long *)sp.movecnt, sp.env_offset);
-  TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)sp.to_play, (const uint8_t *)sp.legal, (const double *)e->tv.noise,
-              e->cfg.root_exploration_fraction, 1);
-  TREE_LAUNCH(k_tm_root_selfplay, s, e->tv, e->tm, e->O, sp);
-  HIPCHECK(hipGetLastError());
-  e->sims_done = 0;
-  e->root_ready = true;
-  e->root_noise = true;
-  e->gz.root_set = false;
-  e->tm.root_set = true;
-  e->selection_valid = true;
-  if (e->sp_tm_fused ? tm_simulations_fused(e, "mz_selfplay_steps", e->sims, s) : tm_simulations(e, "mz_selfplay_steps", e->sims, s))
-    return -1;
-  if (sp.env_kind == 3) hipLaunchKernelGGL(k_board_step_record<3>, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
-  else hipLaunchKernelGGL(k_board_step_record<1>, dim3((B + 127) / 128), dim3(128), 0, s, e->tv, sp, B, A, e->cfg.seed);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-int mz_selfplay_set_true_model(mz_engine *e, int on, int fused) {
-  if (!e) return fail("mz_selfplay_set_true_model: null engine");
-  MZ_ENTER(e);
-  if (on) {
-    if (e->sp_gumbel) return fail("mz_selfplay_set_true_model: the self-play moves are searched with the Gumbel search (mz_selfplay_set_gumbel 0 first)");
-    if (e->sp.env_kind != 1 && e->sp.env_kind != 3)
-      return fail("mz_selfplay_set_true_model: the true-rules self-play runs on the device board games; set one first (mz_selfplay_set_env 1 or 3)");
-    if (e->tm.kind != e->sp.env_kind)
-      return fail("mz_selfplay_set_true_model: the true-rules search of the environment's game is not set on this engine (call mz_set_true_model %d first)", e->sp.env_kind);
-    if (e->draws_set) return fail("mz_selfplay_set_true_model: host-given draws are set (mz_selfplay_set_draws); this mode draws its noise on the device");
-    if (e->tv.sim_io) return fail("mz_selfplay_set_true_model: mz_sim_io instruments the fused search kernels, which this mode does not run (mz_sim_io 0 first)");
-  }
-  if (e->ring.undrained()) return fail("mz_selfplay_set_true_model: %llu moves wait in the device ring; drain them first", e->ring.undrained());
-  HIPCHECK(hipDeviceSynchronize());      // (moves in flight were launched under the other plan)
-  e->sp_tm = on != 0;
-  e->sp_tm_fused = on != 0 && fused != 0;
-  e->tm.root_set = false;
-  drop_graphs(e, false);
-  return 0;
-}
 #undef TM_LAUNCH
 
 // the host twin mz_tm_search_host: its own file, so that a stand-alone host program can compile it (tests/truemodel_host.cpp)

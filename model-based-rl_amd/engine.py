@@ -886,6 +886,7 @@ class Engine(object):
     _abi.check(self.lib.mz_selfplay_set_draws(self._h, _ptr(noise), _ptr(uniform), self.stream), 'mz_selfplay_set_draws')
 
   SELFPLAY_GUMBEL_VALUES = {'mean': 0, 'vmix': 1}
+  selfplay_search = 'puct'      # how the self-play loop searches a move: 'puct', 'gumbel' or 'true_rules' (selfplay_set_gumbel / _true_model)
 
   def selfplay_set_gumbel(self, on=True, value='mean'):
     """mz_selfplay_set_gumbel (DESIGN s7i): while on, the self-play moves of a device game are searched with the Gumbel search
@@ -895,14 +896,19 @@ class Engine(object):
     if value not in self.SELFPLAY_GUMBEL_VALUES:
       raise ValueError("selfplay_set_gumbel: value is 'mean' or 'vmix', got %r" % (value,))
     _abi.check(self.lib.mz_selfplay_set_gumbel(self._h, int(bool(on)), self.SELFPLAY_GUMBEL_VALUES[value]), 'mz_selfplay_set_gumbel')
-    self.selfplay_gumbel = bool(on)
+    self._selfplay_switched('gumbel', on)
 
   def selfplay_set_true_model(self, on=True, fused=True):
     """mz_selfplay_set_true_model (DESIGN s7k): while on, the self-play moves of a device board game are PUCT moves searched on
     the true rules (set_true_model with the game's kind first); fused: a move's simulations in one launch (tm_search_fused),
     else tm_search's two launches per simulation, with the same records.  After selfplay_set_env, with the ring drained."""
     _abi.check(self.lib.mz_selfplay_set_true_model(self._h, int(bool(on)), int(bool(fused))), 'mz_selfplay_set_true_model')
-    self.selfplay_true_model = bool(on)
+    self._selfplay_switched('true_rules', on)
+
+  def _selfplay_switched(self, mode, on):      # (switching off a mode that is not on leaves the current one)
+    self.selfplay_search = mode if on else 'puct' if self.selfplay_search == mode else self.selfplay_search
+  selfplay_gumbel = property(lambda self: self.selfplay_search == 'gumbel')
+  selfplay_true_model = property(lambda self: self.selfplay_search == 'true_rules')
 
   def selfplay_export_trees(self, keep=True):
     _abi.check(self.lib.mz_selfplay_export_trees(self._h, int(bool(keep))), 'mz_selfplay_export_trees')

@@ -22,7 +22,7 @@ import torch
 from .actors import _call
 from .engine import Engine, REC_EXTRA
 from .envs import KIND_OF_ENV
-from .selfplay_gumbel import selfplay_gumbel_params
+from .selfplay_search import selfplay_gumbel_params
 
 KINDS = KIND_OF_ENV      # (envs.DEVICE_GAMES; anything else: 0, all actions legal)
 

@@ -17,8 +17,7 @@ from . import rayshim as ray
 from .actors import Actor
 from .config import build_parser, Config, env_shapes
 from .envs import KIND_OF_ENV
-from .selfplay_gumbel import refuse_selfplay_gumbel
-from .selfplay_true_model import refuse_selfplay_true_model
+from .selfplay_search import refuse_selfplay_gumbel, refuse_selfplay_search, refuse_selfplay_true_model  # noqa: F401 (the per-flag views: imported from here)
 from .learners import Learner
 from .networks import FCNetwork
 from .replay_buffer import PrioritizedReplay
@@ -330,8 +329,7 @@ def main(argv=None):
   refuse_reanalyse_gumbel(cfg)                                                # (--reanalyse_gumbel: likewise)
   from .symmetry import refuse_symmetry
   refuse_symmetry(cfg)                                                        # (--symmetry: likewise)
-  refuse_selfplay_gumbel(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))   # (--selfplay_gumbel: likewise)
-  refuse_selfplay_true_model(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))   # (--selfplay_true_model: likewise)
+  refuse_selfplay_search(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))   # (--selfplay_gumbel, --selfplay_true_model: likewise)
   if spawn:                         # `train --ranks N` without a launcher: pre-flight here (one sentence instead of N tracebacks), then the ranks
     _preflight_ranks(ranks, cfg)
     raise SystemExit(_spawn_ranks(ranks, argv))

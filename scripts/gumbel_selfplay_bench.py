@@ -50,7 +50,7 @@ def child(a):
   from model_based_rl_amd.config import make_config
   from model_based_rl_amd.networks import get_network
   from model_based_rl_amd.replay_buffer import PrioritizedReplay
-  from model_based_rl_amd.selfplay_gumbel import refuse_selfplay_gumbel
+  from model_based_rl_amd.selfplay_search import refuse_selfplay_gumbel
   from model_based_rl_amd.shared_storage import SharedStorage
   sims, extra, _ = CONFIGS[a.child]
   cfg = make_config(['--environment', a.game] + RECIPE + ['--num_envs', str(a.num_envs), '--num_simulations', str(sims),

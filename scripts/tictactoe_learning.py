@@ -12,10 +12,10 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
                                        [--reanalyse_rows N [--reanalyse_every K] [--reanalyse_gumbel [--reanalyse_gumbel_scale S]]]
 --reanalyse_rows / --reanalyse_every / --reanalyse_gumbel / --reanalyse_gumbel_scale are train's flags, passed on to the training run
 (--reanalyse_gumbel: Reanalyse with the Gumbel search for a --selfplay_gumbel run, reanalyse.py).
---selfplay_gumbel adds train's flag (self-play searched with the Gumbel search, the learner trained on pi'; selfplay_gumbel.py) with
+--selfplay_gumbel adds train's flag (self-play searched with the Gumbel search, the learner trained on pi'; selfplay_search.py) with
 its --selfplay_gumbel_* parameters, and --num_simulations sets the simulations of the TRAINING run's self-play; the evaluation
 blocks below stay as they are -- PUCT at 30 simulations unless --gumbel is given.
---selfplay_true_model adds train's flag (self-play searched on the game's true rules below the root, selfplay_true_model.py;
+--selfplay_true_model adds train's flag (self-play searched on the game's true rules below the root, selfplay_search.py;
 --selfplay_true_model_loop: its two-launch form) to the training run; the evaluation blocks stay as they are.
 --environment ConnectFour runs the same recipe on the device Connect Four environment and plays the matches through the
 evaluator's device-environment path (evaluate.Evaluator.play_games(device_env=True): the games never leave the GPU).

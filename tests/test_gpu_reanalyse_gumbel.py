@@ -209,7 +209,7 @@ def test_end_to_end_targets_are_the_new_networks_improved_policy(tmp_path):
   from model_based_rl_amd.engine import Engine
   from model_based_rl_amd.reanalyse import Reanalyser, refuse_reanalyse, refuse_reanalyse_gumbel
   from model_based_rl_amd.replay_buffer import PrioritizedReplay
-  from model_based_rl_amd.selfplay_gumbel import refuse_selfplay_gumbel
+  from model_based_rl_amd.selfplay_search import refuse_selfplay_gumbel
   from model_based_rl_amd.shared_storage import SharedStorage
   cfg = base.ttt_config(tmp_path, '--selfplay_gumbel', '--selfplay_gumbel_value', 'vmix', '--reanalyse_rows', '4096', '--reanalyse_gumbel',
                         '--weight_sync_frequency', '1000')      # (no pull inside the 16 moves: the actor itself runs no pass here)

@@ -3,7 +3,7 @@ s7k).  The records of the device loop against a second engine driven move by mov
 initial_inference, root_prepare with the device's Dirichlet draw, tm_root, tm_search, finalize: the same kernels on the same
 inputs under the same RNG keys, so the int32 views of whole records are EQUAL --, with the move's simulations in one launch and in
 the two-launch loop; the captured graph against direct launches; a game's records in two batches; the mode switched off; the actor
-and the learner; the refusals.  B = 40 environments (three 16-tree workgroups, the last one padded), random FCNetwork weights."""
+and the learner; one engine through all three modes of the loop (DESIGN s7l); the refusals.  B = 40 environments (three 16-tree workgroups, the last one padded), random FCNetwork weights."""
 import functools
 import os
 
@@ -231,6 +231,71 @@ def test_actor_and_learner(tmp_path):
     assert np.isfinite(before[k]) and np.isfinite(after[k]), k
   actor.close(); actor.engine.close()
   assert after['policy'] < before['policy']
+
+
+def test_one_engine_through_the_modes():
+  """One TicTacToe engine of 16 environments (one workgroup's trees) at 30 simulations goes PUCT -> Gumbel -> off -> true rules (one
+  launch per move) -> off -> Gumbel, its ring drained between the switches, and plays 4 moves of fresh games in each: every
+  segment's records EQUAL those of an engine that was only ever in that mode and was given the same move counter (what keys the
+  draws).  While the true rules are on, switching the Gumbel mode off succeeds and leaves them on."""
+  import torch
+  from model_based_rl_amd.engine import Engine
+  gumbel = dict(max_considered=16, c_visit=50.0, c_scale=1.0, gumbel_scale=1.0)
+
+  def engine():
+    eng = Engine(16, 9, 9, 30, seed=SEED, **TWO)
+    eng.set_weights(random_weights(9, 9, 3))
+    eng.selfplay_set_env('tictactoe')
+    return eng
+
+  def segment(eng, index):      # 4 moves of fresh games under the move counter of the index-th segment
+    eng.selfplay_reset(9, 1.0)
+    eng.selfplay_set_moves(4 * index)
+    eng.selfplay_steps(4)
+    buf, n = eng.selfplay_drain()
+    torch.cuda.synchronize()
+    assert n == 4
+    return buf[:n].numpy().copy().view(np.int32)
+
+  def to_gumbel(eng):
+    eng.set_gumbel(True, **gumbel)
+    eng.selfplay_set_gumbel(True)
+
+  def to_true_rules(eng):
+    eng.set_true_model(1)
+    eng.selfplay_set_true_model(True)
+
+  def gumbel_off(eng):
+    eng.selfplay_set_gumbel(False)
+    eng.set_gumbel(False)      # (an engine takes the Gumbel search or the true-rules search)
+
+  def true_rules_off(eng):
+    eng.selfplay_set_true_model(False)
+    eng.set_true_model(0)
+
+  # (the switch before the segment, the mode it plays in)
+  walk = ((None, 'puct'), (to_gumbel, 'gumbel'), (gumbel_off, 'puct'), (to_true_rules, 'true_rules'),
+          (lambda eng: eng.selfplay_set_gumbel(False), 'true_rules'),      # off of the mode that is not on: the true rules stay
+          (true_rules_off, 'puct'), (to_gumbel, 'gumbel'))
+  eng = engine()
+  whole_moves = eng.selfplay_moves_per_launch()
+  got = []
+  for index, (switch, mode) in enumerate(walk):
+    if switch:
+      switch(eng)
+    assert eng.selfplay_search == mode and (eng.selfplay_gumbel, eng.selfplay_true_model) == (mode == 'gumbel', mode == 'true_rules')
+    assert eng.selfplay_moves_per_launch() == (whole_moves if mode == 'puct' else 0)
+    got.append(segment(eng, index))
+  eng.close()
+  for mode, enter in (('puct', None), ('gumbel', to_gumbel), ('true_rules', to_true_rules)):
+    only = engine()
+    if enter:
+      enter(only)
+    for index, (_, m) in enumerate(walk):
+      want = segment(only, index)
+      same = np.array_equal(got[index], want)
+      assert same == (m == mode), (mode, index, m)      # (and at one counter the three modes leave different records)
+    only.close()
 
 
 def test_engine_refusals():

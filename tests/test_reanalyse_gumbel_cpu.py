@@ -28,7 +28,7 @@ def test_flags_reach_the_config_with_their_defaults():
 
 def test_preflight_sentences():
   from model_based_rl_amd.reanalyse import refuse_reanalyse, refuse_reanalyse_gumbel
-  from model_based_rl_amd.selfplay_gumbel import refuse_selfplay_gumbel
+  from model_based_rl_amd.selfplay_search import refuse_selfplay_gumbel
   for argv in (BASE, BASE + ['--reanalyse_gumbel_scale', '1'], BASE + ['--selfplay_gumbel_value', 'vmix'],
                ['--environment', 'ConnectFour'] + BASE[2:], PLAIN, PLAIN + ['--reanalyse_rows', '512'],
                PLAIN + ['--reanalyse_gumbel_scale', '-1']):      # (the scale alone, the flag off: nothing is asked)
@@ -62,7 +62,7 @@ def test_reanalyse_rows_own_refusals_apply_as_before():
 
 
 def test_the_old_refusal_stands_without_the_flag_and_is_gone_with_it():
-  from model_based_rl_amd.selfplay_gumbel import refuse_selfplay_gumbel
+  from model_based_rl_amd.selfplay_search import refuse_selfplay_gumbel
   with pytest.raises(SystemExit) as exc:
     refuse_selfplay_gumbel(_config(PLAIN + ['--selfplay_gumbel', '--reanalyse_rows', '512']))
   msg = str(exc.value)
@@ -125,7 +125,7 @@ def _script():
 
 def test_learning_script_passes_the_flags_on():
   from model_based_rl_amd.reanalyse import refuse_reanalyse, refuse_reanalyse_gumbel
-  from model_based_rl_amd.selfplay_gumbel import refuse_selfplay_gumbel
+  from model_based_rl_amd.selfplay_search import refuse_selfplay_gumbel
   mod = _script()
   ap = mod.build_parser()
   base, extra = mod.recipe(ap.parse_args(['--reanalyse_rows', '4096']))

@@ -16,7 +16,7 @@ def _config(argv):
 
 
 def test_flags_reach_the_config_with_their_defaults():
-  from model_based_rl_amd.selfplay_gumbel import selfplay_gumbel_params
+  from model_based_rl_amd.selfplay_search import selfplay_gumbel_params
   off = _config(BASE[:-1])
   assert off.selfplay_gumbel is False
   cfg = _config(BASE)
