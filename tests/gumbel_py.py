@@ -3,7 +3,9 @@ after the reference's mcts.py (the same expand / backpropagate / MinMaxStats, ma
 sequential halving through seq), the rule below the root and the improved policy from completed Q-values.  Nothing of the
 native code is imported.  Also the fake network every side of the tests evaluates: a function of (tree, parent slot, action)
 through Philox words, on a coarse grid so that exact ties occur -- logits in eighths, values and rewards in sixteenths, the
-given Gumbel draws in 1/64 -- so the device, the host twin and this restatement receive bit-identical float32 outputs."""
+given Gumbel draws in 1/64 -- so the device, the host twin and this restatement receive bit-identical float32 outputs.  Last
+the table of committed test sets (SETS: per set its shape, seed, simulations, trees and search parameters) and the hand-built
+roots (HAND) for the guarded branches: priors that underflow to 0, and exact ties across every child of every node."""
 import math
 
 import numpy as np
@@ -230,42 +232,135 @@ class Search(object):
     return d
 
 
-# ---- the committed test sets: B = 12 trees, 16 simulations, roots with 1, 2 and 3 legal actions among them
+# ---- the committed test sets.  Trees 0, 1, 2 have one, two and three legal actions (as many as A allows)
+SEED_CANDIDATES = tuple(range(0x6C01, 0x6C09))
 SETS = {
-    # name: (A, two_players, known_bounds, discount, seed of the fake network)
-    'tictactoe': (9, True, (-1.0, 1.0), 0.997, 0x6B01),
-    'connect_four': (7, True, (-1.0, 1.0), 0.997, 0x6B02),
-    'single_player': (4, False, (None, None), 0.997, 0x6B03),
+    # name: (A, two_players, known_bounds, discount, seed of the fake network, simulations, trees, the search's parameters)
+    'tictactoe': (9, True, (-1.0, 1.0), 0.997, 0x6B01, SIMS, TREES, {}),
+    'connect_four': (7, True, (-1.0, 1.0), 0.997, 0x6B02, SIMS, TREES, {}),
+    'single_player': (4, False, (None, None), 0.997, 0x6B03, SIMS, TREES, {}),
+    # The sets below reach what the three above do not: the lane groups G = 4 with idle lanes (A = 2) and G = 32 (A = 17 .. 32),
+    # max_considered below the number of legal actions, other simulation counts, c_visit / c_scale and discount 1.  Each seed
+    # is the first of SEED_CANDIDATES for which the host twin's min_gap is >= 1e-9 at gumbel_scale 1 and 0 and the set reaches
+    # its cases (tests/test_gumbel_cpu.py: test_the_margin_condition, test_the_sets_reach_the_cases_that_can_go_wrong, and
+    # test_the_seeds_are_the_first_that_hold).  (c_visit + simulations) * c_scale <= 100 in every one of them.
+    'a2_s8': (2, False, (None, None), 0.997, 0x6C01, 8, TREES, {}),
+    'a18_s30': (18, False, (None, None), 0.997, 0x6C01, 30, TREES, {}),
+    'a18_s30_m4': (18, False, (None, None), 0.997, 0x6C01, 30, TREES, dict(max_considered=4)),
+    'a32_s50': (32, False, (None, None), 0.997, 0x6C01, 50, TREES, {}),
+    'a32_two_m8': (32, True, (-1.0, 1.0), 1.0, 0x6C01, 16, TREES, dict(max_considered=8, c_scale=0.1)),
+    'a9_s30_m4': (9, True, (-1.0, 1.0), 1.0, 0x6C01, 30, TREES, dict(max_considered=4)),
+    'a7_s50_cv0': (7, True, (-1.0, 1.0), 1.0, 0x6C01, 50, TREES, dict(c_visit=0.0, c_scale=2.0)),
+    'a13_s33_m5': (13, False, (-2.0, 2.0), 0.9, 0x6C01, 33, TREES, dict(max_considered=5)),
+    'a18_b70_s8': (18, False, (None, None), 0.997, 0x6C01, 8, 70, {}),
 }
+NEW_SETS = tuple(n for n in SETS if n not in ('tictactoe', 'connect_four', 'single_player'))
 
 
-def case(name):
-  """the roots of a test set: dict(A, two, bounds, discount, seed, to_play [B] int8, legal [B, A] uint8, root_value [B],
-  root_logits [B, A] float32, G [B, A] float64)"""
-  A, two, bounds, discount, seed = SETS[name]
+def group_width(A):
+  """the lanes per tree of the device kernels (the engine's shape table): 4, 8, 16 or 32"""
+  return 4 if A <= 4 else 8 if A <= 8 else 16 if A <= 16 else 32
+
+
+def case(name, seed=None):
+  """the roots of a test set: dict(A, two, bounds, discount, seed, sims, trees, kw, to_play [B] int8, legal [B, A] uint8,
+  root_value [B], root_logits [B, A] float32, G [B, A] float64).  seed: another fake-network seed than the committed one.
+  A hand-built root (HAND) has its own outputs under 'eval' instead of the fake network's."""
+  if name in HAND:
+    return HAND[name]()
+  A, two, bounds, discount, seed0, sims, trees, kw = SETS[name]
+  seed = seed0 if seed is None else seed
   rng = np.random.RandomState(seed)
-  legal = np.zeros((TREES, A), np.uint8)
-  for b in range(TREES):
-    k = b + 1 if b < 3 else int(rng.randint(3, A + 1))      # trees 0, 1, 2: one, two and three legal actions
+  legal = np.zeros((trees, A), np.uint8)
+  for b in range(trees):
+    k = min(b + 1, A) if b < 3 else int(rng.randint(min(3, A), A + 1))      # trees 0, 1, 2: one, two and three legal actions
     legal[b, rng.choice(A, k, replace=False)] = 1
-  to_play = np.array([1 if not two or b % 2 == 0 else -1 for b in range(TREES)], np.int8)
-  roots = [fake_root(seed, b, A) for b in range(TREES)]
-  return dict(A=A, two=two, bounds=bounds, discount=discount, seed=seed, to_play=to_play, legal=legal,
-              root_value=np.array([r[0] for r in roots], np.float32), root_logits=np.stack([r[1] for r in roots]).astype(np.float32),
-              G=np.stack([r[2] for r in roots]))
+  if A == 32:
+    legal[3] = 1                                                             # every bit of the mask, 31 included
+  to_play = np.array([1 if not two or b % 2 == 0 else -1 for b in range(trees)], np.int8)
+  roots = [fake_root(seed, b, A) for b in range(trees)]
+  return dict(A=A, two=two, bounds=bounds, discount=discount, seed=seed, sims=sims, trees=trees, kw=dict(kw), to_play=to_play,
+              legal=legal, root_value=np.array([r[0] for r in roots], np.float32),
+              root_logits=np.stack([r[1] for r in roots]).astype(np.float32), G=np.stack([r[2] for r in roots]))
 
 
-def search_batch(c, gumbel_scale, sims=SIMS, num_simulations=None, **kw):
-  """the trees of case c in lock-step on the fake network; returns the stacked arrays of Search.arrays"""
+def net(c):
+  """eval_fn(sim, parent_slot [n], action [n]) of case c: its own outputs (a hand-built root), or the fake network"""
+  return c['eval'] if 'eval' in c else fake_eval(c['seed'], c['A'])
+
+
+def considered(c):
+  """m [B] of the roots of case c: min(max_considered, legal actions)"""
+  return np.minimum(c['kw'].get('max_considered', 16), c['legal'].sum(1).astype(np.int64))
+
+
+def search_batch(c, gumbel_scale, sims=None, num_simulations=None, **kw):
+  """the trees of case c in lock-step on its network; returns the stacked arrays of Search.arrays"""
+  sims = c['sims'] if sims is None else sims
+  kw = dict(c['kw'], **kw)
+  n = c['trees']
   trees = [Search(c['A'], sims, int(c['to_play'][b]), [a for a in range(c['A']) if c['legal'][b, a]], c['root_value'][b],
                   c['root_logits'][b], c['G'][b], two_players=c['two'], discount=c['discount'], known_bounds=c['bounds'],
-                  gumbel_scale=gumbel_scale, **kw) for b in range(TREES)]
-  for _ in range(sims if num_simulations is None else num_simulations):
+                  gumbel_scale=gumbel_scale, **kw) for b in range(n)]
+  f = net(c)
+  for s in range(sims if num_simulations is None else num_simulations):
+    sel = [t.select() for t in trees]
+    v, r, lg = f(s, np.array([x[0] for x in sel], np.int32), np.array([x[1] for x in sel], np.int32))
     for b, t in enumerate(trees):
-      slot, action = t.select()
-      t.expand_backup(*fake_leaf(c['seed'], b, slot, action, c['A']))
+      t.expand_backup(v[b], r[b], lg[b])
   per = [t.arrays() for t in trees]
   return {k: np.stack([np.asarray(p[k]) for p in per]) for k in per[0]}
+
+
+# ---- hand-built roots: the outputs are a plain function of (parent slot, action), the same float32 values for every side
+def _hand(A, two, bounds, discount, sims, legal, root_value, root_logits, G, ev):
+  legal = np.asarray(legal, np.uint8)
+  n = len(legal)
+  return dict(A=A, two=two, bounds=bounds, discount=discount, seed=0, sims=sims, trees=n, kw={}, legal=legal,
+              to_play=np.array([1 if not two or b % 2 == 0 else -1 for b in range(n)], np.int8),
+              root_value=np.asarray(root_value, np.float32), root_logits=np.asarray(root_logits, np.float32),
+              G=np.asarray(G, np.float64), eval=ev)
+
+
+UNDERFLOW = ((5, 17), (17, 0), (0, 16), (9, 3))      # per tree: (the action with logit 0, the action with G = 900)
+
+
+def underflow():
+  """A = 18, every action legal (tree 3: ten of them): one logit is 0, the others are -800, so every prior but one is
+  exp(-800) = 0 in float64; G is 900 on one of the -800 actions, which the first simulation therefore visits.  From then
+  until the logit-0 action has its visit the root has sum N > 0 and sp == 0: v_mix is v^.  On a grid, as the fake network."""
+  A, n = 18, len(UNDERFLOW)
+  logits, G, legal = np.full((n, A), -800.0, np.float32), np.zeros((n, A)), np.ones((n, A), np.uint8)
+  for b, (one, up) in enumerate(UNDERFLOW):
+    logits[b, one], G[b, up] = 0.0, 900.0
+  legal[3, [1, 2, 4, 5, 6, 7, 8, 10]] = 0
+
+  def ev(sim, slot, act):
+    slot, act = np.asarray(slot, np.int64), np.asarray(act, np.int64)
+    v = (((slot * 7 + act * 3 + np.arange(len(slot))) % 16) - 8) / 16.0
+    r = (((slot + act * 5) % 8) - 4) / 16.0
+    lg = (((act[:, None] * 5 + slot[:, None] + 3 * np.arange(A)[None, :]) % 17) - 8) / 8.0
+    return v.astype(np.float32), r.astype(np.float32), lg.astype(np.float32)
+  return _hand(A, False, (None, None), 0.997, 24, legal, [0.25, -0.5, 0.125, 0.0625], logits, G, ev)
+
+
+def _ties(A, two, bounds, discount):
+  """every logit, value, reward and G is 0: every arg-max, at the root and below it, is an exact tie across all the
+  existing children.  Tree 0: every action legal; tree 1: the largest is not; tree 2: actions 0, 1 and A - 2 alone"""
+  legal = np.ones((3, A), np.uint8)
+  legal[1, A - 1] = 0
+  legal[2] = 0
+  legal[2, [0, 1, A - 2]] = 1
+  z = lambda sim, slot, act: (np.zeros(len(slot), np.float32), np.zeros(len(slot), np.float32), np.zeros((len(slot), A), np.float32))
+  return _hand(A, two, bounds, discount, 20, legal, np.zeros(3), np.zeros((3, A)), np.zeros((3, A)), z)
+
+
+HAND = {
+    'underflow': underflow,
+    'ties18': lambda: _ties(18, False, (None, None), 0.997),
+    'ties32': lambda: _ties(32, True, (-1.0, 1.0), 1.0),
+}
+HAND_RUNS = (('underflow', 1.0), ('ties18', 1.0), ('ties18', 0.0), ('ties32', 1.0), ('ties32', 0.0))      # (root, gumbel_scale)
 
 
 TREE_FIELDS = ('N', 'W', 'P', 'R', 'E', 'TP')

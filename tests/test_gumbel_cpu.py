@@ -3,10 +3,17 @@
   twin       mz_gz_search_host -- sequential C++ through the per-node body the kernels run -- equals the Python restatement
              of tests/gumbel_py.py: every integer field, W and R bit for bit (both use glibc on the same float32 network
              outputs), P, pi' and v_mix to 1e-12
-  by hand    one root with three legal actions and four simulations, from the formulas
+             -- on the first three sets (A = 9, 7, 4; 16 simulations) and on those added to reach the lane groups G = 4 with
+             idle lanes and G = 32, m < legal actions, 8 .. 50 simulations, other c_visit / c_scale, discount 1 and 70 trees
+             (gp.SETS), each of which is asserted to reach what it is there for
+  by hand    one root with three legal actions and four simulations, from the formulas; the guarded branches of mz_gz_node on
+             roots built for them (gp.HAND): sum N > 0 with sp == 0, and exact ties across every child of every node
   margin     min_gap >= 1e-9 on every committed test set: a device / host difference of about 1e-13 (8 ulp of exp on values
              <= 1, a few roundings on scores below 2^7) cannot flip a decision the host takes with that margin, so the GPU
-             tests demand equality with no allowance.  Exact ties have gap 0 and are allowed (they break to the largest action)
+             tests demand equality with no allowance.  Exact ties have gap 0 and are allowed (they break to the largest action).
+             Every set keeps (c_visit + simulations) * c_scale <= 100, so sigma <= 100 and g + logit + sigma < 2^7; on the
+             underflow root the scores reach 100 + 74 and -800, where a rounding is 1.2e-13 at the most: the same argument
+  seeds      a set's fake-network seed is the first of gp.SEED_CANDIDATES that holds the margin and reaches the set's cases
   refusals   one test per sentence of evaluate.refuse_gumbel, the flags, label and --out key on a stub engine"""
 import json
 import math
@@ -20,26 +27,30 @@ from tests import gumbel_py as gp
 SIMS = gp.SIMS
 
 
-def _cfg(c, n=gp.TREES, sims=SIMS):
+def _cfg(c):
   from model_based_rl_amd.engine import mz_config
-  return mz_config(n, 4, c['A'], sims, two_players=c['two'], known_bounds=c['bounds'], discount=c['discount'])
+  return mz_config(c['trees'], 4, c['A'], c['sims'], two_players=c['two'], known_bounds=c['bounds'], discount=c['discount'])
 
 
 def host_search(c, scale, **kw):
+  """the host twin on case c (a set of gp.SETS or a hand-built root): simulations, trees and parameters are the case's"""
   from model_based_rl_amd.engine import gz_search_host
-  return gz_search_host(_cfg(c), c['root_value'], c['root_logits'], gp.fake_eval(c['seed'], c['A']), to_play=c['to_play'],
-                        legal=c['legal'], gumbel=c['G'] if scale else None, gumbel_scale=scale, **kw)
+  return gz_search_host(_cfg(c), c['root_value'], c['root_logits'], gp.net(c), to_play=c['to_play'],
+                        legal=c['legal'], gumbel=c['G'] if scale else None, gumbel_scale=scale, **dict(c['kw'], **kw))
+
+
+class _Searched(dict):
+  """per (set or hand-built root, gumbel_scale): (the host twin's trees, the restatement's), searched when first asked for"""
+
+  def __missing__(self, key):
+    c = gp.case(key[0])
+    self[key] = (host_search(c, key[1]), gp.search_batch(c, key[1]))
+    return self[key]
 
 
 @pytest.fixture(scope='module')
 def searched():
-  """per (set, gumbel_scale): (the host twin's trees, the restatement's)"""
-  out = {}
-  for name in gp.SETS:
-    c = gp.case(name)
-    for scale in (1.0, 0.0):
-      out[name, scale] = (host_search(c, scale), gp.search_batch(c, scale))
-  return out
+  return _Searched()
 
 
 def test_seq_against_the_hand_listed_sequences():
@@ -52,8 +63,8 @@ def test_seq_against_the_hand_listed_sequences():
 
 def test_seq_invariants():
   from model_based_rl_amd.engine import gz_seq
-  for m in range(1, 10):
-    for n in range(1, 33):
+  for m in range(1, 33):      # every row of the device's table [A + 1][sims], A <= 32
+    for n in range(1, 65):
       s = gz_seq(m, n).tolist()
       assert s == gp.seq(m, n), (m, n)
       assert len(s) == n
@@ -68,7 +79,11 @@ def test_seq_invariants():
 @pytest.mark.parametrize('name', list(gp.SETS))
 @pytest.mark.parametrize('scale', [1.0, 0.0], ids=['given_G', 'no_noise'])
 def test_host_twin_equals_the_restatement(searched, name, scale):
-  host, want = searched[name, scale]
+  _twin_equals_the_restatement(searched[name, scale], gp.case(name))
+
+
+def _twin_equals_the_restatement(pair, c):
+  host, want = pair
   ex = want['EX'] == 1
   for key in ('N', 'E', 'TP', 'W', 'R'):
     diff = np.argwhere((host[key] != want[key]) & ex)
@@ -77,8 +92,8 @@ def test_host_twin_equals_the_restatement(searched, name, scale):
   for key in ('legal', 'minmax', 'vhat', 'sel_slot', 'sel_action', 'paths', 'plens', 'action', 'pred_reward'):
     assert np.array_equal(host[key], np.asarray(want[key]).astype(host[key].dtype)), key
   assert np.abs(host['pi'] - want['pi']).max() <= 1e-12 and np.abs(host['v_mix'] - want['v_mix']).max() <= 1e-12
-  assert np.all(host['pi'][gp.case(name)['legal'] == 0] == 0) and np.allclose(host['pi'].sum(1), 1, atol=1e-12)
-  assert (host['N'][:, 0] == SIMS).all()
+  assert np.all(host['pi'][c['legal'] == 0] == 0) and np.allclose(host['pi'].sum(1), 1, atol=1e-12)
+  assert (host['N'][:, 0] == c['sims']).all()
 
 
 @pytest.mark.parametrize('name', list(gp.SETS))
@@ -99,11 +114,49 @@ def test_host_twin_reproduces_the_pinned_outputs(searched, name, scale):
 @pytest.mark.parametrize('name', list(gp.SETS))
 def test_the_sets_reach_the_cases_that_can_go_wrong(searched, name):
   c = gp.case(name)
-  assert sorted(c['legal'].sum(1).tolist())[:3] == [1, 2, 3]
   host, _ = searched[name, 1.0]
-  assert host['plens'].max() >= 4, 'no descent goes two levels below the root'
   plain, _ = searched[name, 0.0]
-  assert (plain['action'] != host['action']).any() or (plain['sel_action'] != host['sel_action']).any(), 'G changes nothing'
+  assert _unreached(name, c, host, plain) == []
+
+
+def _unreached(name, c, host, plain):
+  """what set `name` (roots c, the twin's searches at gumbel_scale 1 and 0) does not reach of what it is there for"""
+  A, no = c['A'], []
+  nl = c['legal'].sum(1)
+  if sorted(nl.tolist())[:3] != [min(k, A) for k in (1, 2, 3)] or nl[0] != 1:
+    no.append('no roots with one, two and three legal actions')
+  if host['plens'].max() < 4:
+    no.append('no descent goes two levels below the root')
+  if not ((plain['action'] != host['action']).any() or (plain['sel_action'] != host['sel_action']).any()):
+    no.append('G changes nothing')
+  binds = int((gp.considered(c) < nl).sum())      # roots where sequential halving starts from fewer than the legal actions
+  if 'max_considered' in c['kw'] and binds < 4:
+    no.append('max_considered binds on %d roots, fewer than 4' % binds)
+  if name == 'a18_s30' and binds < 1:
+    no.append('no root with more than 16 legal actions')
+  if name == 'a2_s8' and sorted(set(gp.considered(c).tolist())) != [1, 2]:
+    no.append('m = 1 and m = 2 do not both occur')
+  if A == 32 and not (nl == 32).any():
+    no.append('no root with 32 legal actions')
+  if gp.group_width(A) == 32:
+    for d in (host, plain):      # a descent or a pick in the upper half of the lane group, and of its last action
+      taken = np.concatenate([d['sel_action'].ravel(), d['action'].ravel()])
+      if not (taken >= 16).any():
+        no.append('no descent or pick of an action >= 16')
+      if not (taken == A - 1).any():
+        no.append('no descent or pick of action A - 1')
+  return no
+
+
+def test_the_seeds_are_the_first_that_hold():
+  """the seed rule of the sets added after the first three (gp.SETS): a set's seed is the first of gp.SEED_CANDIDATES with
+  which the twin's min_gap is >= 1e-9 at both scales and the set reaches its cases.  That the committed seed holds both is
+  what test_the_margin_condition and test_the_sets_reach_the_cases_that_can_go_wrong assert; here: no earlier one does"""
+  for name in gp.NEW_SETS:
+    for seed in gp.SEED_CANDIDATES[:gp.SEED_CANDIDATES.index(gp.SETS[name][4])]:
+      c = gp.case(name, seed=seed)
+      host, plain = host_search(c, 1.0), host_search(c, 0.0)
+      assert min(host['min_gap'], plain['min_gap']) < 1e-9 or _unreached(name, c, host, plain), (name, hex(seed))
 
 
 @pytest.mark.parametrize('name', list(gp.SETS))
@@ -160,6 +213,67 @@ def test_one_root_by_hand():
   assert host['action'][0] == 2 and host['pred_reward'][0] == np.float32(leaf_r[2])      # the only action with two visits
   assert np.abs(host['pi'][0] - np.array(pi)).max() <= 1e-12 and host['pi'][0, 1] == 0
   assert abs(host['v_mix'][0] - v_mix) <= 1e-12
+
+
+@pytest.mark.parametrize('name,scale', gp.HAND_RUNS)
+def test_hand_built_roots_twin_equals_the_restatement(searched, name, scale):
+  """the guarded branches of mz_gz_node (gp.underflow, gp._ties), with the bars of test_host_twin_equals_the_restatement; the
+  margin holds on them as on the sets, so the GPU test demands equality on them too"""
+  _twin_equals_the_restatement(searched[name, scale], gp.case(name))
+  assert searched[name, scale][0]['min_gap'] >= 1e-9
+
+
+def check_underflow_is_reached(first, whole, c):
+  """first: the search after ONE simulation, whole: after all of them (the twin's, the restatement's or the device's arrays).
+  The first simulation visits the action G lifts, whose prior is 0: sum N > 0 and sp == 0 at the root, so v_mix is v^ to
+  the bit and pi' is the prior -- 1 on the logit-0 action, 0 on every P == 0 child"""
+  A = c['A']
+  for b, (one, up) in enumerate(gp.UNDERFLOW):
+    kids = np.asarray(first['N'])[b, 1:1 + A]
+    assert kids[up] == 1 and kids.sum() == 1 and np.asarray(first['P'])[b, 1 + up] == 0
+    assert first['v_mix'][b] == np.float64(c['root_value'][b]), 'v_mix is not v^'
+    zero = (np.asarray(whole['P'])[b, 1:1 + A] == 0) & (c['legal'][b] == 1)
+    assert zero.sum() == c['legal'][b].sum() - 1 and not zero[one]
+    assert first['pi'][b, one] == 1 and not np.asarray(first['pi'])[b, np.arange(A) != one].any()
+    assert (np.asarray(whole['pi'])[b, zero] == 0).all() and whole['pi'][b, one] == 1
+    assert (np.asarray(whole['N'])[b, 1:1 + A][zero] > 0).any()      # (visited children among them)
+
+
+def test_prior_underflow_by_hand(searched):
+  c = gp.case('underflow')
+  host, want = searched['underflow', 1.0]
+  first = host_search(c, 1.0, num_simulations=1)
+  check_underflow_is_reached(first, host, c)
+  check_underflow_is_reached(gp.search_batch(c, 1.0, num_simulations=1), want, c)
+  assert np.array_equal(first['v_mix'], gp.search_batch(c, 1.0, num_simulations=1)['v_mix'])
+
+
+def check_ties_break_to_the_largest_action(d, c):
+  """d: a search of a gp._ties root.  The first m simulations stay at the root and take its legal actions in descending
+  order.  The next m (seq asks for one visit) go through the same actions in the same order -- the largest of those visited
+  once -- and on below the root, where no child is visited yet, to action A - 1.  The move is the largest legal action"""
+  A = c['A']
+  for b in range(c['trees']):
+    legal = [a for a in range(A) if c['legal'][b, a]]
+    m = min(16, len(legal))
+    top = sorted(legal, reverse=True)[:m]
+    assert d['sel_action'][b, :m].tolist() == top and not d['sel_slot'][b, :m].any(), b
+    assert d['plens'][b, :m].tolist() == [2] * m
+    again = np.arange(m, min(2 * m, c['sims']))
+    assert len(again) >= 3 and (d['sel_action'][b, again] == A - 1).all() and (d['plens'][b, again] == 3).all(), b
+    assert [(int(k) - 1) % A for k in d['paths'][b, again, 1]] == top[:len(again)], b      # (the path's first step: the root's choice)
+    assert d['sel_slot'][b, again].tolist() == list(range(1, 1 + len(again))), b           # (its slot: first taken, first revisited)
+    assert d['action'][b] == top[0] and d['sel_action'][b].max() < A
+
+
+@pytest.mark.parametrize('name', ['ties18', 'ties32'])
+def test_all_ties_by_hand(searched, name):
+  c = gp.case(name)
+  for scale in (1.0, 0.0):
+    host, want = searched[name, scale]
+    check_ties_break_to_the_largest_action(host, c)
+    check_ties_break_to_the_largest_action(want, c)
+    assert np.array_equal(host['sel_action'], want['sel_action'])
 
 
 def test_host_twin_refusals():
