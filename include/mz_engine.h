@@ -25,6 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mz_record.h"      /* the experience record's layout: MZ_REC_EXTRA, the tail's offsets, the flag bits */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -563,10 +565,7 @@ int mz_padded_envs(const mz_engine *e);
  * (mz_selfplay_set_obs: byte-valued observations and --norm_obs for the -ram- shapes.)
  * mz_selfplay_steps runs `moves` complete moves: obs -> initial inference -> root -> search ->
  * select_action -> env.step -> experience record appended to a device ring.
- * Each record is rec_floats() = obs_dim + action_space + MZ_REC_EXTRA float32 slots: obs[O] (raw, as History keeps
- * it), child_visits[A], root_value and error as float64 in two slots each (the reference's Python floats,
- * actors.py:147-148, game.py:112), reward, then as int32 bit patterns: action, flags (bit 0 = done, bit 1 = the mover was
- * player -1: History.to_play, game.py:100-101; always clear for the single-player environments), step, env_id, episode.
+ * Each record is rec_floats() = MZ_REC_FLOATS(obs_dim, action_space, packed) float32 slots, laid out as mz_record.h states.
  * mz_selfplay_drain copies the records produced since the last drain into `out` [host, pinned
  * preferred] asynchronously on `stream` and returns their count through *n_records after the
  * stream is synchronised by the caller (records are laid out move-major: [moves][B]).  `stream` may be a
@@ -581,7 +580,6 @@ int mz_padded_envs(const mz_engine *e);
  * stagger != 0: env i starts its first episode at t0 = hash(env id) % episode_len (uniform episode ends).
  * temperature: Config.visit_softmax_temperature at reset; mz_selfplay_set_temperature changes what every env's
  * NEXT game starts with (actors.py:128-129: evaluated once per game), games in progress keep theirs. */
-#define MZ_REC_EXTRA 10
 int mz_selfplay_reset(mz_engine *e, int episode_len, double temperature, int stagger, void *stream);
 int mz_selfplay_set_temperature(mz_engine *e, double temperature, void *stream);
 /* The move counter of every environment (Actor's count of moves played, actors.py:87-124: keys the device RNG by (seed, env, move)

@@ -19,6 +19,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mz_record.h"      /* the experience record's layout */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -40,7 +42,7 @@ typedef struct mzr_config {
   int32_t episode_life;       /* --episode_life: `terminal` (end of game) differs from `done` (game.py:90) */
   int32_t ingest_threads;     /* threads mzr_ingest_records* splits the environments of a call over (0 or 1: the caller only) */
   int32_t obs_u8;             /* observations are bytes (image / -ram- frames, game.py:93-96 keeps the raw uint8 observation): a record
-                               * carries them packed, 4 per float slot -- rec_floats = ceil(obs_dim / 4) + action_space + MZR_REC_EXTRA;
+                               * carries them packed, 4 per float slot -- rec_floats = MZ_REC_FLOATS(obs_dim, action_space, 1), mz_record.h;
                                * mzr_save_history still takes float32 observations (values 0..255), mzr_sample_batch returns float32 */
 } mzr_config;
 
@@ -75,15 +77,12 @@ int mzr_save_history(mz_replay *r, int64_t n, const double *errors, int64_t igno
                      const float *obs, const float *child_visits, const double *root_values, const float *rewards,
                      const int32_t *actions, const uint8_t *dones, const int8_t *to_play);
 
-/* Bulk ingest of device records (layout of mz_selfplay_drain: [n_moves][B][rec_floats], rec = obs[O],
- * child_visits[A] (float32), root_value and error as float64 in two float slots each (the reference keeps both as
- * Python floats: actors.py:147-148, game.py:112 -- priorities and value targets built from records are therefore
- * the reference's doubles), reward (float32), then int32 bits action, flags, step, env_id, episode:
- * rec_floats = obs_dim + action_space + MZR_REC_EXTRA.
+/* Bulk ingest of device records (what mz_selfplay_drain hands out: [n_moves][B][rec_floats], every record laid out as
+ * mz_record.h states; rec_floats = MZ_REC_FLOATS(obs_dim, action_space, obs_u8)).
  * Re-creates per environment what Actor.play_game does after each move (actors.py:160-173): histories are
  * accumulated per env and flushed to save_history when max_history_length steps were collected (with the
  * overlap/ignore rules) or the episode is done.  frames/games: PrioritizedReplay.throughput.
- * The flags word of a record carries `done` (bit 0) and the mover (bit 1 set = to_play -1; History.to_play,
+ * The flags word of a record carries `done` (MZ_REC_FLAG_DONE) and the mover (MZ_REC_FLAG_P2 set = to_play -1; History.to_play,
  * game.py:100-101 -- n-step targets flip the sign of the other player's rewards by it, replay_buffer.py:187-189); the
  * single-player device loops leave bit 1 clear (to_play = +1), the device TicTacToe loop sets it.  `done` ends the game
  * (terminal == done): a replay created with episode_life (terminal != done, game.py:90) REFUSES records (-1,
@@ -98,7 +97,7 @@ int mzr_save_history(mz_replay *r, int64_t n, const double *errors, int64_t igno
  * mzr_ingest_records_from: the B environments of this call are the replay's environments env_base .. env_base+B-1
  * (one replay fed by several actor ranks: rank r passes env_base = r * B; actors.py:169 -- every reference actor
  * sends to the ONE replay buffer, train.py:71-72). */
-#define MZR_REC_EXTRA 10
+#define MZR_REC_EXTRA MZ_REC_EXTRA
 int mzr_ingest_records(mz_replay *r, const float *records, int n_moves, int B, int rec_floats);
 int mzr_ingest_records_from(mz_replay *r, const float *records, int n_moves, int B, int rec_floats, int env_base);
 /* One replay fed by many ranks (train --ranks N): the per-record work of the replay's host that does NOT need the replay is done

@@ -10,7 +10,7 @@ import subprocess
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 _SO = os.environ.get('MZ_HIP_LIB') or os.path.join(_CSRC, 'libmz_hip.so')      # (MZ_HIP_LIB: A/B runs of two builds on one box)
-_SOURCES = ['mz_engine.hip', 'mz_comm.inc', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_fcl_plan.inc', 'mz_fcl_sizes.h', 'mz_pack.inc', 'mz_stream_sizes.h', 'mz_inst.hip', 'mz_kernels.inc', 'mz_common.h', 'mz_games.h', 'mz_net.hip.h', 'mz_tree.hip.h', 'mz_tree_host.h', 'mz_rng.h', 'mz_eval.hip.h',
+_SOURCES = ['mz_engine.hip', 'mz_comm.inc', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_fcl_plan.inc', 'mz_fcl_sizes.h', 'mz_pack.inc', 'mz_stream_sizes.h', 'mz_inst.hip', 'mz_kernels.inc', 'mz_common.h', 'mz_games.h', 'mz_record.h', 'mz_net.hip.h', 'mz_tree.hip.h', 'mz_tree_host.h', 'mz_rng.h', 'mz_eval.hip.h',
             'mz_selfplay.hip.h', 'mz_selfplay_abi.inc', 'mz_selfplay_mode.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_playout.hip.h', 'mz_playout_abi.inc', 'mz_solve.hip.h', 'mz_solve_abi.inc', 'mz_unroll.hip.h', 'mz_unroll_abi.inc', 'mz_truemodel.hip.h', 'mz_truemodel_abi.inc', 'mz_truemodel_host.inc', 'mz_gumbel.hip.h', 'mz_gumbel_selfplay.hip.h', 'mz_gumbel_abi.inc', 'mz_gumbel_host.inc', 'mz_fused.hip.h', 'mz_root.hip.h', 'mz_fused_h2.hip.h', 'mz_symmetry.hip.h']
 _ENGINE_ONLY = ('mz_engine.hip', 'mz_tree_host.h', 'mz_comm.inc', 'mz_eval.hip.h', 'mz_learner.hip.h', 'mz_fcl.hip.h', 'mz_fcl_abi.inc', 'mz_fcl_plan.inc', 'mz_fcl_sizes.h', 'mz_pack.inc', 'mz_selfplay_abi.inc', 'mz_selfplay_mode.inc', 'mz_eval_abi.inc', 'mz_eval_env.hip.h', 'mz_match.hip.h', 'mz_match_abi.inc', 'mz_reanalyse.hip.h', 'mz_reanalyse_abi.inc', 'mz_playout.hip.h', 'mz_playout_abi.inc', 'mz_solve.hip.h', 'mz_solve_abi.inc', 'mz_unroll.hip.h', 'mz_unroll_abi.inc', 'mz_truemodel.hip.h', 'mz_truemodel_abi.inc', 'mz_truemodel_host.inc', 'mz_gumbel.hip.h', 'mz_gumbel_selfplay.hip.h', 'mz_gumbel_abi.inc', 'mz_gumbel_host.inc', 'mz_symmetry.hip.h')      # included by mz_engine.hip alone
 _lib = None
@@ -66,7 +66,7 @@ def stale():
   if not os.path.exists(_SO):
     return True
   t = os.path.getmtime(_SO)
-  inc = [os.path.join(_CSRC, '..', '..', 'include', h) for h in ('mz_engine.h', 'mz_engine_debug.h')]
+  inc = [os.path.join(_CSRC, '..', '..', 'include', h) for h in ('mz_engine.h', 'mz_engine_debug.h', 'mz_record.h')]
   srcs = [os.path.join(_CSRC, s) for s in _SOURCES] + inc
   return any(os.path.exists(s) and os.path.getmtime(s) > t for s in srcs)
 
@@ -90,7 +90,7 @@ def build(force=False, verbose=False, out=None, extra=None, jobs=None):
     # an object is kept when its command line is unchanged and none of the sources its unit includes is newer (the search
     # kernels' units do not include the learner / host-side files: a learner edit recompiles one unit, not thirteen)
     deps = [s for s in _SOURCES if src == 'mz_engine.hip' or s not in _ENGINE_ONLY]
-    deps = deps + [os.path.join('..', '..', 'include', h) for h in (('mz_engine.h', 'mz_engine_debug.h') if src == 'mz_engine.hip' else ('mz_engine.h',))]
+    deps = deps + [os.path.join('..', '..', 'include', h) for h in (('mz_engine.h', 'mz_record.h', 'mz_engine_debug.h') if src == 'mz_engine.hip' else ('mz_engine.h', 'mz_record.h'))]
     stamp = obj + '.cmd'
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == ' '.join(cmd):
       t = os.path.getmtime(obj)
@@ -344,9 +344,9 @@ def build_replay(force=False, verbose=False, out=None, extra=None):
   """out / extra: another library file and other optimisation / instrumentation flags than -O3 (the sanitizer builds of
   tests/test_sanitizers.py)"""
   src = os.path.join(_CSRC, 'mz_replay.cpp')
-  hdr = os.path.join(_CSRC, '..', '..', 'include', 'mz_replay.h')
+  deps = [src, os.path.join(_CSRC, 'mz_record.h')] + [os.path.join(_CSRC, '..', '..', 'include', h) for h in ('mz_replay.h', 'mz_record.h')]
   target = out or os.path.join(_CSRC, 'libmz_replay.so')
-  if force or out or not os.path.exists(target) or os.path.getmtime(target) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+  if force or out or not os.path.exists(target) or os.path.getmtime(target) < max(os.path.getmtime(d) for d in deps):
     # -mavx2: the sum tree's per-level running sums are 4-wide double vectors (every x86-64 host of an MI355X box has
     # AVX2; no FMA is enabled and contraction stays off: the sums are the reference's, term by term)
     cmd = ['g++'] + (list(extra) if extra is not None else ['-O3']) + REPLAY_FLAGS + ['mz_replay.cpp', '-o', target]

@@ -533,7 +533,7 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
   const int pos = __popc(legal & ((1u << lane) - 1u));
   if (ok) { d[pos] = (double)c; acts[pos] = lane; }
   const unsigned long long move = envs ? *(const unsigned long long *)envs : sp.movecnt[b];
-  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * t.B + b) * sp.rec_floats;
+  float *rec = mz_rec_slot(sp.ring, move, sp.ring_moves, t.B, b, sp.rec_floats);
   const int OS = sp.obs_slots;       // float slots of the observation in the record (O, or ceil(O / 4) for packed bytes)
   // (lanes 0..3 read the LDS words lane 0 overwrites further down, with no barrier between: the TL lanes of a tree share a
   // wavefront and the read precedes the write in program order -- as for the synthetic environment's copy below)
@@ -581,11 +581,7 @@ __device__ __forceinline__ void mz_finalize_record(const TreeView &t, const Tree
     }
     const int tt = envs ? envs[2] : sp.t[b], ep = envs ? envs[3] : sp.episode[b];
     const int done = (tt + 1 >= sp.episode_len) ? 1 : 0;
-    mz_rec_put_double(rec + OS + A + 0, rv);
-    mz_rec_put_double(rec + OS + A + 2, err);
-    rec[OS + A + 4] = mz_synth_reward(seed, env, (uint32_t)ep, (uint32_t)tt);
-    int32_t *ri = (int32_t *)(rec + OS + A + 5);
-    ri[0] = action; ri[1] = done; ri[2] = tt; ri[3] = (int32_t)env; ri[4] = ep;
+    mz_rec_put_tail(rec, OS, A, rv, err, mz_synth_reward(seed, env, (uint32_t)ep, (uint32_t)tt), action, done, tt, (int32_t)env, ep);
     if (done) {      // the next game starts: its temperature is evaluated now (actors.py:128-129)
       const double tn = *sp.temp_next;
       sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = tn;

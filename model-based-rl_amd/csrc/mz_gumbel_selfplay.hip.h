@@ -28,7 +28,7 @@ __global__ __launch_bounds__(64) void k_gz_move_record(TreeView t, GzState gz, S
   float cR;
   const int best = mz_gz_root_pick<G>(t, gz, b, lane, &pi, &vmix, &cR);
   (void)cR;
-  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * t.B + b) * sp.rec_floats;
+  float *rec = mz_rec_slot(sp.ring, move, sp.ring_moves, t.B, b, sp.rec_floats);
   for (int k = wl; k < O; k += 64) rec[k] = sp.obs[(size_t)b * O + k];
   if (wl < A) {
     rec[O + wl] = (float)pi;
@@ -46,8 +46,7 @@ __global__ __launch_bounds__(64) void k_gz_move_record(TreeView t, GzState gz, S
     for (int k = 0; k < 4; ++k) st[k] = sp.cart[(size_t)b * 4 + k];
     const int done = mz_cartpole_apply(sp, b, action, rv, err, rec, A, st, tt, ep, seed);
     for (int k = 0; k < 4; ++k) sp.cart[(size_t)b * 4 + k] = st[k];
-    if (done) { sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next; }
-    else sp.t[b] = tt + 1;
+    mz_store_next_move(sp, b, mz_next_move(sp, done, tt, ep));
   } else {
     mz_board_apply<KIND>(sp, b, action, rv, err, rec, A);
   }

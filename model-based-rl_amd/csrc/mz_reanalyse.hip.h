@@ -20,6 +20,7 @@
 #include "mz_common.h"
 #include "mz_tree.hip.h"
 #include "mz_gumbel.hip.h"
+#include "mz_record.h"
 
 // Separate from SelfplayState / EvalState / MatchState: self-play, evaluation and matches on the same engine are untouched.
 struct ReanalyseState {
@@ -44,8 +45,7 @@ __host__ __device__ inline uint32_t mz_reanalyse_legal_mask(int kind, const floa
   return mask;
 }
 
-// rows: the chunk's first row, [n][R] with R = O + A + MZR_REC_EXTRA; the flags word is the int32 at float slot O + A + 6 (bit 1:
-// to_play == -1).  One thread per (row, observation element): neighbouring threads read neighbouring floats of the host row;
+// rows: the chunk's first row, [n][R] of unpacked records (include/mz_record.h; the mover is read from the flags word).  One thread per (row, observation element): neighbouring threads read neighbouring floats of the host row;
 // the row's first thread also derives legal / to_play.  Rows b >= n of the chunk get what k_eval_observe feeds a finished game:
 // a zero observation, every action legal, to_play +1.
 static __global__ void k_reanalyse_observe(ReanalyseState rs, const float *rows, int n, int R, int kind, int B, int O, int A) {
@@ -59,8 +59,8 @@ static __global__ void k_reanalyse_observe(ReanalyseState rs, const float *rows,
   uint8_t *legal = rs.legal + (size_t)b * A;
   const uint32_t mask = real ? mz_reanalyse_legal_mask(kind, row, A) : 0xFFFFFFFFu;
   for (int a = 0; a < A; ++a) legal[a] = (uint8_t)((mask >> a) & 1u);
-  const int32_t flags = real ? ((const int32_t *)(row + O + A + 5))[1] : 0;
-  rs.to_play[b] = (flags & 2) ? (int8_t)-1 : (int8_t)1;
+  const int32_t flags = real ? mz_rec_flags(mz_rec_tail(row, O, A)) : 0;
+  rs.to_play[b] = (flags & MZ_REC_FLAG_P2) ? (int8_t)-1 : (int8_t)1;
 }
 
 // fresh: the chunk's first row, [n][A + 2]; nothing is stored for b >= n.  One thread per (row, float slot): slots 0..A-1 the

@@ -8,8 +8,8 @@ int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats,
   if (!e) return fail("mz_reanalyse: null engine");
   MZ_ENTER(e);
   if (!e->weights_set) return fail("mz_reanalyse: weights not set (call mz_set_weights)");
-  if (rec_floats != e->O + e->A + MZ_REC_EXTRA)      // (= MZR_REC_EXTRA of include/mz_replay.h: one record layout)
-    return fail("mz_reanalyse: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, e->O + e->A + MZ_REC_EXTRA);
+  if (rec_floats != MZ_REC_FLOATS(e->O, e->A, 0))
+    return fail("mz_reanalyse: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, MZ_REC_FLOATS(e->O, e->A, 0));
   if (kind < 0 || kind > 3)
     return fail("mz_reanalyse: kind must be 0 (synthetic), 1 (TicTacToe), 2 (CartPole) or 3 (Connect Four), got %d", kind);
   if (kind != 0 && game_shape(e, "mz_reanalyse", kind)) return -1;
@@ -68,8 +68,8 @@ int mz_reanalyse_gumbel(mz_engine *e, int kind, const float *rows_host, int rec_
   if (!e->gz.on) return fail("mz_reanalyse_gumbel: no Gumbel search is set on this engine (call mz_set_gumbel first)");
   if (value_kind != 0 && value_kind != 1)
     return fail("mz_reanalyse_gumbel: value_kind %d (0 the root's mean value, 1 its v_mix)", value_kind);
-  if (rec_floats != e->O + e->A + MZ_REC_EXTRA)
-    return fail("mz_reanalyse_gumbel: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, e->O + e->A + MZ_REC_EXTRA);
+  if (rec_floats != MZ_REC_FLOATS(e->O, e->A, 0))
+    return fail("mz_reanalyse_gumbel: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, MZ_REC_FLOATS(e->O, e->A, 0));
   if (kind < 0 || kind > 3)
     return fail("mz_reanalyse_gumbel: kind must be 0 (synthetic), 1 (TicTacToe), 2 (CartPole) or 3 (Connect Four), got %d", kind);
   if (kind != 0 && game_shape(e, "mz_reanalyse_gumbel", kind)) return -1;

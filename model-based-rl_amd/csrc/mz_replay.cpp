@@ -3,7 +3,8 @@
 // PrioritizedReplay (replay_buffer.py) exactly; see the header for the citations.
 //
 // Layout.  A history slice (HistorySlice, game.py:5-16) is kept as the experience records it was made from: one row
-// of rec_floats = O + A + MZR_REC_EXTRA float32 per step, exactly the device's record (include/mz_engine.h).  The bulk
+// of rec_floats float32 per step, exactly the device's record (include/mz_record.h states the layout, mz_record.h here has the
+// accessors; nothing below spells an offset).  The bulk
 // ingest therefore moves every record ONCE -- appended to its environment's open buffer, which becomes the slice when
 // the game ends -- and sample_batch reads its fields straight from the rows.
 // Threads.  mzr_ingest_records* splits the environments of a call over the handle's ingest threads (per-environment
@@ -11,6 +12,7 @@
 // afterwards in (move, environment) order on the calling thread, so leaves, sums and counters are those of a
 // single-threaded walk, bit for bit (replay_buffer.py:19-40 is order dependent in float64).
 #include "../../include/mz_replay.h"
+#include "mz_record.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -38,9 +40,8 @@ static int fail(const char *fmt, ...) {
   return -1;
 }
 
-// One HistorySlice as record rows; leaves point into it as (history, step).  Row layout (R = OS + A + MZR_REC_EXTRA floats,
-// OS = O float32 slots, or ceil(O / 4) when the observations are bytes -- mzr_config.obs_u8): obs, child_visits[A], root_value (float64, 2 slots), error (float64, 2 slots), reward, then int32 bits: action,
-// flags (bit 0 done, bit 1 to_play == -1), step, env_id, episode.
+// One HistorySlice as record rows (R = MZ_REC_FLOATS(O, A, mzr_config.obs_u8) floats each, OS of them the observation);
+// leaves point into it as (history, step).
 struct Hist {
   int64_t n = 0;                // steps of the slice
   int64_t off = 0;              // first row of the slice inside `rows` (a finished game hands its whole buffer over)
@@ -49,9 +50,6 @@ struct Hist {
   uint64_t picked = 0;          // the reanalyse ticket that last took this slice (mzr_reanalyse_pick: a pass takes a slice once)
   std::vector<float> rows;
 };
-
-#define MZR_FLAG_DONE 1
-#define MZR_FLAG_P2 2           // to_play == -1 (two-player games; single-player records leave it clear: to_play = +1)
 
 // what Game/Actor keep per environment between flushes (game.py:54-77, actors.py:160-169)
 struct EnvGame {
@@ -384,13 +382,6 @@ static void tree_add(mz_replay *r, const double *priorities, int64_t n, Hist *h,
   }
 }
 
-static inline void row_put_double(float *dst, double v) { memcpy(dst, &v, sizeof v); }
-static inline double row_double(const float *p) {     // a float64 stored in two float slots (4-byte aligned)
-  double v;
-  memcpy(&v, p, sizeof v);
-  return v;
-}
-
 static int save_history(mz_replay *r, int64_t n, const double *errors, int64_t ignore, int terminal,
                         const float *obs, const float *child_visits, const double *root_values,
                         const float *rewards, const int32_t *actions, const uint8_t *dones, const int8_t *to_play) {
@@ -406,18 +397,18 @@ static int save_history(mz_replay *r, int64_t n, const double *errors, int64_t i
     h->rows.assign((size_t)n * R, 0.f);
     for (int64_t i = 0; i < n; ++i) {
       float *q = h->rows.data() + (size_t)i * R;
-      int32_t *qi = (int32_t *)(q + OS + A + 5);
+      float *tail = mz_rec_tail(q, OS, A);
       if (obs) {
         if (r->c.obs_u8) { uint8_t *qb = (uint8_t *)q; for (int k = 0; k < O; ++k) qb[k] = (uint8_t)obs[i * O + k]; }
         else memcpy(q, obs + i * O, O * sizeof(float));
       }
       if (child_visits) memcpy(q + OS, child_visits + i * A, A * sizeof(float));
-      if (root_values) row_put_double(q + OS + A, root_values[i]);
-      row_put_double(q + OS + A + 2, errors[i]);
-      if (rewards) q[OS + A + 4] = rewards[i];
-      qi[0] = actions ? actions[i] : 0;
-      qi[1] = ((dones && dones[i]) ? MZR_FLAG_DONE : 0) | ((to_play && to_play[i] < 0) ? MZR_FLAG_P2 : 0);
-      qi[2] = (int32_t)i;
+      if (root_values) mz_rec_put_double(tail + MZ_REC_ROOT_VALUE, root_values[i]);
+      mz_rec_put_double(tail + MZ_REC_ERROR, errors[i]);
+      if (rewards) tail[MZ_REC_REWARD] = rewards[i];
+      mz_rec_put_int(tail, MZ_REC_ACTION, actions ? actions[i] : 0);
+      mz_rec_put_int(tail, MZ_REC_FLAGS, ((dones && dones[i]) ? MZ_REC_FLAG_DONE : 0) | ((to_play && to_play[i] < 0) ? MZ_REC_FLAG_P2 : 0));
+      mz_rec_put_int(tail, MZ_REC_STEP, (int32_t)i);
     }
   }
   if ((int64_t)r->pri.size() < keep) r->pri.resize(keep);
@@ -444,8 +435,8 @@ int mzr_create(const mzr_config *cfg, mz_replay **out) {
   if (cfg->ingest_threads < 0 || cfg->ingest_threads > 64) return fail("mzr_create: ingest_threads must be in [0, 64]");
   mz_replay *r = new mz_replay();
   r->c = *cfg;
-  r->OS = cfg->obs_u8 ? (cfg->obs_dim + 3) / 4 : cfg->obs_dim;
-  r->R = r->OS + cfg->action_space + MZR_REC_EXTRA;
+  r->OS = MZ_REC_OBS_SLOTS(cfg->obs_dim, cfg->obs_u8);
+  r->R = MZ_REC_FLOATS(cfg->obs_dim, cfg->action_space, cfg->obs_u8);
   r->max_capacity = cfg->window_size;
   r->capacity_step = cfg->window_step;
   r->capacity = cfg->window_step;
@@ -714,8 +705,7 @@ static void ingest_range(const AsmCfg &ac, EnvGame *envs, Scratch &sc, const flo
       bool flush = false, done = false;
       int64_t hidx = g.history_idx;
       for (; e < n_moves; ++e) {
-        const int32_t *ri = (const int32_t *)(row(b, e) + OS + A + 5);
-        done = (ri[1] & MZR_FLAG_DONE) != 0;
+        done = (mz_rec_flags(mz_rec_tail(row(b, e), OS, A)) & MZ_REC_FLAG_DONE) != 0;
         ++hidx;
         if (done || (hidx - g.previous_collect_to) == ac.max_history_length) { flush = true; break; }
       }
@@ -747,7 +737,7 @@ static void ingest_range(const AsmCfg &ac, EnvGame *envs, Scratch &sc, const flo
       double *pri = sc.pris.data() + off;
       const float *q = g.recs.data() + (size_t)(collect_from - g.base) * R;
       for (int64_t i = 0; i < n; ++i, q += R) {
-        const double e_ = fabs(row_double(q + OS + A + 2)) + ac.epsilon;
+        const double e_ = fabs(mz_rec_error(mz_rec_tail(q, OS, A))) + ac.epsilon;
         pri[i] = ac.alpha == 1.0 ? e_ : pow(e_, ac.alpha);
       }
       h->off = collect_from - g.base;
@@ -930,8 +920,9 @@ int mzr_sample_batch(const mz_replay *r, const double *draws, int bs, float *obs
     if (!h->payload) return 2;
     const float *rows = h->rows.data() + (size_t)h->off * R;
     auto row = [&](int64_t s) { return rows + (size_t)s * R; };
-    auto reward = [&](int64_t s) { return row(s)[OS + A + 4]; };
-    auto flags = [&](int64_t s) { return ((const int32_t *)(row(s) + OS + A + 5))[1]; };
+    auto tail = [&](int64_t s) { return mz_rec_tail(row(s), OS, A); };
+    auto reward = [&](int64_t s) { return mz_rec_reward(tail(s)); };
+    auto flags = [&](int64_t s) { return mz_rec_flags(tail(s)); };
     if (r->c.obs_u8) {                                                                        // 147 (bytes -> float32, as np.float32(obs))
       const uint8_t *ob = (const uint8_t *)row(step);
       for (int k = 0; k < O; ++k) obs[(size_t)i * O + k] = (float)ob[k];
@@ -941,21 +932,21 @@ int mzr_sample_batch(const mz_replay *r, const double *draws, int bs, float *obs
     // (History: observations has one entry more than the other lists, game.py:93-96; every other list has h->n entries)
     const int64_t end_index = h->n, n_rewards = h->n;
     for (int k = 0; k < K; ++k)                                                        // 149-152
-      actions[(size_t)i * K + k] = (step + k < end_index) ? ((const int32_t *)(row(step + k) + OS + A + 5))[0] : -1;
+      actions[(size_t)i * K + k] = (step + k < end_index) ? mz_rec_action(tail(step + k)) : -1;
     // insert_target, replay_buffer.py:165-198
     for (int j = 0; j < TL; ++j) {
       const int64_t cur = step + j;
       const float last_reward = (cur > 0 && cur <= n_rewards) ? reward(cur - 1) : 0.f;
       float *pol = target_policies + ((size_t)i * TL + j) * A;
       if (cur < end_index) {
-        const int tp = flags(cur) & MZR_FLAG_P2;
+        const int tp = flags(cur) & MZ_REC_FLAG_P2;
         const int64_t boot = cur + td;
-        double value = boot < end_index ? row_double(row(boot) + OS + A) * disc_td : 0.0;
+        double value = boot < end_index ? mz_rec_root_value(tail(boot)) * disc_td : 0.0;
         const int64_t hi = boot < n_rewards ? boot : n_rewards;
         if (hi > cur) {
           float acc = 0.f;
           for (int64_t q = cur; q < hi; ++q) {
-            const float rw = ((flags(q) & MZR_FLAG_P2) != tp) ? -reward(q) : reward(q);      // 187-189
+            const float rw = ((flags(q) & MZ_REC_FLAG_P2) != tp) ? -reward(q) : reward(q);      // 187-189
             acc += rw * disc[q - cur];
           }
           value += (double)acc;
@@ -1166,8 +1157,7 @@ int mzr_asm_create(const mzr_config *cfg, int num_envs, mz_assembler **out) {
   if (!cfg || !out || num_envs < 1) return fail("mzr_asm_create: bad argument");
   if (cfg->episode_life) return fail("mzr_asm_create: records carry one end-of-game flag (no episode_life)");
   mz_assembler *a = new mz_assembler();
-  const int OS = cfg->obs_u8 ? (cfg->obs_dim + 3) / 4 : cfg->obs_dim;
-  a->ac = asm_cfg_of(*cfg, OS, OS + cfg->action_space + MZR_REC_EXTRA);
+  a->ac = asm_cfg_of(*cfg, MZ_REC_OBS_SLOTS(cfg->obs_dim, cfg->obs_u8), MZ_REC_FLOATS(cfg->obs_dim, cfg->action_space, cfg->obs_u8));
   a->B = num_envs;
   a->envs.resize((size_t)num_envs);
   *out = a;
@@ -1368,6 +1358,7 @@ int64_t mzr_reanalyse_write(mz_replay *r, uint64_t ticket, const float *fresh, i
     return fail("mzr_reanalyse_write: the ticket holds %lld rows, the caller brings %lld", (long long)r->re_rows, (long long)n_rows);
   const int OS = r->OS, A = r->c.action_space;
   const size_t R = (size_t)r->R, F = (size_t)A + 2;
+  static_assert(MZ_REC_ROOT_VALUE == 0, "a fresh row is a record's child_visits and root_value: the root value opens the tail");
   int64_t written = 0, at = 0;
   double dv = 0.0, dp = 0.0;
   for (Hist *h : r->re_slices) {
@@ -1376,8 +1367,8 @@ int64_t mzr_reanalyse_write(mz_replay *r, uint64_t ticket, const float *fresh, i
       const float *f = fresh + (size_t)at * F;
       for (int64_t i = 0; i < h->n; ++i, q += R, f += F) {
         for (int a = 0; a < A; ++a) dp += fabs((double)f[a] - (double)q[a]);
-        dv += fabs(row_double(f + A) - row_double(q + A));
-        memcpy(q, f, F * sizeof(float));                  // child_visits[A], root_value: the row's own layout from OS on
+        dv += fabs(mz_rec_get_double(f + A) - mz_rec_root_value(q + A));
+        memcpy(q, f, F * sizeof(float));                  // child_visits[A], root_value: the row's own layout from OS on (q + A is its tail)
       }
       written += h->n;
     }

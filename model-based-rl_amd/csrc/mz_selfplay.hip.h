@@ -6,6 +6,7 @@
 #include "mz_rng.h"
 #include "mz_tree.hip.h"
 #include "mz_games.h"
+#include "mz_record.h"
 
 struct SelfplayState {
   int episode_len;
@@ -114,17 +115,7 @@ static __global__ void k_dirichlet(TreeView t, const uint8_t *legal, double alph
   }
 }
 
-// Experience record of one move: obs[O], child_visits[A] (float32), root_value and error as float64 (two float
-// slots each: the reference keeps both as Python floats, actors.py:147-148, game.py:112), reward (float32), then int32
-// bit patterns: action, flags (bit 0 done, bit 1 to_play == -1: game.py:100-101 appends the mover), step (pre-step),
-// env_id, episode.
-#ifndef MZ_REC_EXTRA
-#define MZ_REC_EXTRA 10     // (include/mz_engine.h)
-#endif
-__device__ __forceinline__ void mz_rec_put_double(float *dst, double v) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  ((uint32_t *)dst)[0] = (uint32_t)u; ((uint32_t *)dst)[1] = (uint32_t)(u >> 32);
-}
+// The experience record of one move: include/mz_record.h states its layout, mz_record.h here has the accessors.
 
 // float slot k of a record's observation: obs[k], or -- packed byte observations (obs_u8 == 2) -- the bytes obs[4k .. 4k + 3]
 // (History keeps the raw uint8 observation, game.py:93-96; the values are exact small integers in float32)
@@ -136,6 +127,22 @@ __device__ __forceinline__ float mz_rec_obs_slot(const SelfplayState &sp, const 
   return __builtin_bit_cast(float, w);
 }
 
+// Where environment b stands after a move from step t of episode ep: at the next step of its game, or -- the move ended the
+// game -- at step 0 of its next game, whose temperature is evaluated now (actors.py:128-129: once per game).  A game that goes
+// on keeps its episode and temperature: those two are meaningful, and stored, only with new_game.
+// The launch-per-step kernels call this.  The ends of a move that are compiled into the whole-moves search kernels --
+// mz_board_apply and the two in mz_finalize_record (mz_fused.hip.h), which also mirror the result into LDS -- spell the same
+// rule out: going through this function changed those kernels' code, and they are held to it byte for byte.
+struct MzNextMove { int t, episode; double temp; bool new_game; };
+__device__ __forceinline__ MzNextMove mz_next_move(const SelfplayState &sp, int done, int t, int ep) {
+  if (done) return {0, ep + 1, *sp.temp_next, true};
+  return {t + 1, ep, 0.0, false};
+}
+__device__ __forceinline__ void mz_store_next_move(const SelfplayState &sp, int b, const MzNextMove &nx) {
+  if (nx.new_game) { sp.t[b] = nx.t; sp.episode[b] = nx.episode; sp.temp[b] = nx.temp; }
+  else sp.t[b] = nx.t;
+}
+
 // Game.apply (game.py:79-104) on the synthetic env + the experience record of this move.
 static __global__ void k_env_step_record(TreeView tv, SelfplayState sp, int B, int O, int A, uint64_t seed) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,23 +152,15 @@ static __global__ void k_env_step_record(TreeView tv, SelfplayState sp, int B, i
   // Config.select_action + store_search_statistics + root error for this tree (same code as mz_finalize)
   mz_finalize_tree(tv, b, sp.temp, nullptr, seed, move, sp.env_offset, sp.action, sp.child_visits, sp.root_value,
                    sp.error, nullptr);
-  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
+  float *rec = mz_rec_slot(sp.ring, move, sp.ring_moves, B, b, sp.rec_floats);
   const int t = sp.t[b], ep = sp.episode[b];
   const int OS = sp.obs_slots;
   for (int k = 0; k < OS; ++k) rec[k] = mz_rec_obs_slot(sp, sp.obs + (size_t)b * O, O, k);
   for (int a = 0; a < A; ++a) rec[OS + a] = (float)sp.child_visits[(size_t)b * A + a];
   const float reward = mz_synth_reward(seed, (uint32_t)(sp.env_offset + b), (uint32_t)ep, (uint32_t)t);
   const int done = (t + 1 >= sp.episode_len) ? 1 : 0;
-  mz_rec_put_double(rec + OS + A + 0, sp.root_value[b]);
-  mz_rec_put_double(rec + OS + A + 2, sp.error[b]);
-  rec[OS + A + 4] = reward;
-  int32_t *ri = (int32_t *)(rec + OS + A + 5);
-  ri[0] = sp.action[b]; ri[1] = done; ri[2] = t; ri[3] = sp.env_offset + b; ri[4] = ep;
-  if (done) {      // the next game starts: its temperature is evaluated now (actors.py:128-129)
-    sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next;
-  } else {
-    sp.t[b] = t + 1;
-  }
+  mz_rec_put_tail(rec, OS, A, sp.root_value[b], sp.error[b], reward, sp.action[b], done, t, sp.env_offset + b, ep);
+  mz_store_next_move(sp, b, mz_next_move(sp, done, t, ep));
 }
 
 // ---- a real game as the environment (mz_selfplay_set_env; the games themselves: mz_games.h).  TicTacToe keeps its board
@@ -189,12 +188,9 @@ __device__ __forceinline__ void mz_board_apply(const SelfplayState &sp, int b, i
   int8_t *bd = sp.board + (size_t)b * O;
   bool won;
   const int done = mz_game_step(KIND, bd, turn, action, t, &won) ? 1 : 0;
-  mz_rec_put_double(rec + O + A + 0, root_value);
-  mz_rec_put_double(rec + O + A + 2, error);
-  rec[O + A + 4] = won ? 1.f : 0.f;
-  int32_t *ri = (int32_t *)(rec + O + A + 5);
-  ri[0] = action; ri[1] = done | (turn < 0 ? 2 : 0); ri[2] = t; ri[3] = sp.env_offset + b; ri[4] = ep;
-  if (done) {
+  mz_rec_put_tail(rec, O, A, root_value, error, won ? 1.f : 0.f, action,
+                  (done ? MZ_REC_FLAG_DONE : 0) | (turn < 0 ? MZ_REC_FLAG_P2 : 0), t, sp.env_offset + b, ep);
+  if (done) {      // (mz_next_move, spelled out: this runs inside the whole-moves search kernels, whose code is held as it is)
     for (int k = 0; k < O; ++k) bd[k] = 0;
     sp.turn[b] = 1; sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next;
   } else {
@@ -215,7 +211,7 @@ static __global__ void k_board_step_record(TreeView tv, SelfplayState sp, int B,
   mz_finalize_tree(tv, b, sp.temp, KIND == 1 ? sp.draw_uniform : nullptr, seed, move, sp.env_offset, sp.action, sp.child_visits,
                    sp.root_value, sp.error, nullptr);
   constexpr int O = mz_game_info(KIND).cells;
-  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
+  float *rec = mz_rec_slot(sp.ring, move, sp.ring_moves, B, b, sp.rec_floats);
   for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
   for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
   mz_board_apply<KIND>(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A);
@@ -231,11 +227,7 @@ __device__ __forceinline__ int mz_cartpole_apply(const SelfplayState &sp, int b,
   const int O = 4;
   const bool out = mz_cartpole_step(st, action);
   const int done = (out || tt + 1 >= sp.episode_len) ? 1 : 0;      // termination, or gym's TimeLimit
-  mz_rec_put_double(rec + O + A + 0, root_value);
-  mz_rec_put_double(rec + O + A + 2, error);
-  rec[O + A + 4] = 1.f;
-  int32_t *ri = (int32_t *)(rec + O + A + 5);
-  ri[0] = action; ri[1] = done; ri[2] = tt; ri[3] = sp.env_offset + b; ri[4] = ep;
+  mz_rec_put_tail(rec, O, A, root_value, error, 1.f, action, done, tt, sp.env_offset + b, ep);
   if (done) mz_cartpole_reset_state(seed, (uint32_t)(sp.env_offset + b), (uint32_t)(ep + 1), st);
   return done;
 }
@@ -249,7 +241,7 @@ static __global__ void k_cartpole_step_record(TreeView tv, SelfplayState sp, int
   mz_finalize_tree(tv, b, sp.temp, sp.draw_uniform, seed, move, sp.env_offset, sp.action, sp.child_visits, sp.root_value,
                    sp.error, nullptr);
   const int O = 4;
-  float *rec = sp.ring + ((size_t)(move % (unsigned long long)sp.ring_moves) * B + b) * sp.rec_floats;
+  float *rec = mz_rec_slot(sp.ring, move, sp.ring_moves, B, b, sp.rec_floats);
   for (int k = 0; k < O; ++k) rec[k] = sp.obs[(size_t)b * O + k];
   for (int a = 0; a < A; ++a) rec[O + a] = (float)sp.child_visits[(size_t)b * A + a];
   const int tt = sp.t[b], ep = sp.episode[b];
@@ -257,6 +249,5 @@ static __global__ void k_cartpole_step_record(TreeView tv, SelfplayState sp, int
   for (int k = 0; k < 4; ++k) st[k] = sp.cart[(size_t)b * 4 + k];
   const int done = mz_cartpole_apply(sp, b, sp.action[b], sp.root_value[b], sp.error[b], rec, A, st, tt, ep, seed);
   for (int k = 0; k < 4; ++k) sp.cart[(size_t)b * 4 + k] = st[k];
-  if (done) { sp.t[b] = 0; sp.episode[b] = ep + 1; sp.temp[b] = *sp.temp_next; }
-  else sp.t[b] = tt + 1;
+  mz_store_next_move(sp, b, mz_next_move(sp, done, tt, ep));
 }

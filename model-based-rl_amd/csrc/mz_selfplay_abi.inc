@@ -15,8 +15,8 @@ static int selfplay_alloc(mz_engine *e) {
 #define DM(p, n) if (dmalloc(e, &(p), (n))) return -1;
   DM(sp.t, nb) DM(sp.episode, nb) DM(sp.obs, nb * e->O) DM(sp.temp, nb) DM(sp.temp_next, 1) DM(sp.action, nb)
   DM(sp.child_visits, nb * e->A) DM(sp.root_value, nb) DM(sp.error, nb) DM(sp.movecnt, nb)
-  sp.obs_slots = sp.obs_u8 == 2 ? (e->O + 3) / 4 : e->O;
-  sp.rec_floats = e->O + e->A + MZ_REC_EXTRA;      // (the ring is sized for unpacked observations; set_obs may shrink the record)
+  sp.obs_slots = MZ_REC_OBS_SLOTS(e->O, sp.obs_u8 == 2);
+  sp.rec_floats = MZ_REC_FLOATS(e->O, e->A, 0);      // (the ring is sized for unpacked observations; set_obs may shrink the record)
   sp.ring_moves = e->ring.capacity = RecordRing::capacity_for((size_t)e->B * sp.rec_floats * sizeof(float));
   DM(sp.ring, (size_t)sp.ring_moves * e->B * sp.rec_floats)
 #undef DM
@@ -187,8 +187,8 @@ int mz_selfplay_set_obs(mz_engine *e, int uint8_obs, const float *obs_min, const
   if (selfplay_alloc(e)) return -1;
   if (e->ring.undrained()) return fail("mz_selfplay_set_obs: drain the ring first (the record layout may change)");
   sp.obs_u8 = uint8_obs;
-  sp.obs_slots = uint8_obs == 2 ? (e->O + 3) / 4 : e->O;
-  sp.rec_floats = sp.obs_slots + e->A + MZ_REC_EXTRA;
+  sp.obs_slots = MZ_REC_OBS_SLOTS(e->O, uint8_obs == 2);
+  sp.rec_floats = MZ_REC_FLOATS(e->O, e->A, uint8_obs == 2);
   if (obs_min) {
     for (int k = 0; k < e->O; ++k)
       if (!(obs_range[k] != 0.f)) return fail("mz_selfplay_set_obs: obs_range[%d] is zero", k);
@@ -465,7 +465,7 @@ int mz_selfplay_moves_per_launch(const mz_engine *e) {
   if (!e) return -1;
   return search_plan(e).persist ? MZ_GRAPH_MOVES : 0;
 }
-int mz_selfplay_rec_floats(const mz_engine *e) { return e ? (e->sp.t ? e->sp.rec_floats : e->O + e->A + MZ_REC_EXTRA) : -1; }
+int mz_selfplay_rec_floats(const mz_engine *e) { return e ? (e->sp.t ? e->sp.rec_floats : MZ_REC_FLOATS(e->O, e->A, 0)) : -1; }
 int mz_selfplay_ring_moves(const mz_engine *e) { return (e && e->sp.t) ? e->ring.capacity : -1; }
 
 int mz_selfplay_steps_timed(mz_engine *e, int k, float *ms_out, void *stream) {

@@ -93,24 +93,7 @@ def config_scale_check(config):
   return lambda flat: weights_scale_ok(flat, O, A, sv, sr)
 
 
-REC_EXTRA = 10      # include/mz_engine.h MZ_REC_EXTRA
-
-
-def records_view(rec, O, A, obs_u8=False):
-  """Named views into experience records (numpy float32, layout of include/mz_engine.h / include/mz_replay.h):
-  obs, child_visits, root_value / error (float64), reward, action / done / step / env_id / episode (int32).
-  obs_u8: the observation is O bytes packed into ceil(O / 4) float slots (image frames, torch_search.TorchSelfplay)."""
-  rec = np.asarray(rec)
-  OS = (O + 3) // 4 if obs_u8 else O
-  assert rec.dtype == np.float32 and rec.shape[-1] == OS + A + REC_EXTRA, (rec.dtype, rec.shape)
-  ints = rec[..., OS + A + 5:].view(np.int32)
-  flags = ints[..., 1]                   # bit 0 done, bit 1 the mover was player -1 (History.to_play, game.py:100-101)
-  obs = np.ascontiguousarray(rec[..., :OS]).view(np.uint8)[..., :O] if obs_u8 else rec[..., :O]
-  return dict(obs=obs, child_visits=rec[..., OS:OS + A],
-              root_value=np.ascontiguousarray(rec[..., OS + A:OS + A + 2]).view(np.float64)[..., 0],
-              error=np.ascontiguousarray(rec[..., OS + A + 2:OS + A + 4]).view(np.float64)[..., 0],
-              reward=rec[..., OS + A + 4], action=ints[..., 0], done=flags & 1, to_play=1 - (flags & 2), step=ints[..., 2],
-              env_id=ints[..., 3], episode=ints[..., 4])
+from .record import REC_EXTRA, rec_floats, records_view  # noqa: E402,F401  (the record's layout: record.py; callers import these from here)
 
 
 def _ptr(t):
@@ -785,7 +768,7 @@ class Engine(object):
 
   # ---- Reanalyse of stored replay rows (mz_reanalyse, include/mz_engine.h)
   def reanalyse(self, rows, fresh, n_rows, kind, num_simulations=None):
-    """mz_reanalyse: rows [>= n_rows, O + A + REC_EXTRA] and fresh [>= n_rows, A + 2], both PINNED float32 host tensors; the
+    """mz_reanalyse: rows [>= n_rows, rec_floats(O, A)] and fresh [>= n_rows, A + 2], both PINNED float32 host tensors; the
     first n_rows rows are searched again under the current weights in chunks of B, without exploration noise, and fresh
     receives child_visits (float32) and root_value (float64 in two slots) per row -- what PrioritizedReplay.reanalyse_write
     takes.  kind: an ENVS / EVAL_ENVS name or 0..3.  Returns when the last chunk has been stored."""

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from .actors import _call
-from .engine import Engine, REC_EXTRA
+from .engine import Engine
+from .record import rec_floats
 from .envs import KIND_OF_ENV
 from .selfplay_search import selfplay_gumbel_params
 
@@ -90,7 +91,7 @@ class Reanalyser(object):
 
   def _size(self, max_rows):
     if max_rows > self.max_rows:
-      self.rows = torch.empty(max_rows, self.O + self.A + REC_EXTRA, dtype=torch.float32).pin_memory()
+      self.rows = torch.empty(max_rows, rec_floats(self.O, self.A), dtype=torch.float32).pin_memory()
       self.fresh = torch.empty(max_rows, self.A + 2, dtype=torch.float32).pin_memory()
       self.max_rows = max_rows
 

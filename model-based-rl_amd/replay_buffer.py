@@ -63,10 +63,10 @@ class SumTree(object):
     _abi.check_replay(self.lib.mzr_leaf_info(self._h, idx, C.byref(pri), C.byref(step), C.byref(n), C.byref(has)), 'mzr_leaf_info')
     history = None
     if has.value:
-      from .engine import REC_EXTRA, records_view
+      from .record import rec_floats, records_view
       from .game import HistorySlice
       u8, O, A = self._rows
-      rows = np.zeros((n.value, ((O + 3) // 4 if u8 else O) + A + REC_EXTRA), np.float32)
+      rows = np.zeros((n.value, rec_floats(O, A, u8)), np.float32)
       _abi.check_replay(self.lib.mzr_leaf_history(self._h, idx, _p(rows), n.value), 'mzr_leaf_history')
       v = records_view(rows, O, A, obs_u8=u8)
       history = HistorySlice(list(v['obs']), [list(map(float, c)) for c in v['child_visits']], v['root_value'].tolist(),
@@ -195,9 +195,9 @@ class PrioritizedReplay(object):
   # ---- reanalyse (include/mz_replay.h): whole history slices out, fresh child_visits / root_value back in
   @property
   def rec_floats(self):
-    from .engine import REC_EXTRA
+    from .record import rec_floats
     u8, O, A = self.tree._rows
-    return ((O + 3) // 4 if u8 else O) + A + REC_EXTRA
+    return rec_floats(O, A, u8)
 
   @staticmethod
   def _float_rows(a, name, width):

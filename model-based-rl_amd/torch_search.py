@@ -18,7 +18,8 @@ the layout of include/mz_engine.h, handed to the native replay.
 import numpy as np
 import torch
 
-from .engine import Engine, REC_EXTRA
+from .engine import Engine
+from .record import obs_slots, rec_floats, records_fill
 
 
 class BatchedSearch(object):
@@ -123,8 +124,8 @@ class TorchSelfplay(object):
     # the frames are bytes and stay bytes in the experience record (game.py:93-96 keeps the raw observation): O bytes in
     # ceil(O / 4) float slots -- a quarter of the D2H traffic and of the replay's memory (include/mz_replay.h obs_u8)
     self.obs_u8 = self.envs.obs.dtype == torch.uint8
-    self.OS = (self.O + 3) // 4 if self.obs_u8 else self.O
-    self.rec_floats = self.OS + self.A + REC_EXTRA
+    self.OS = obs_slots(self.O, self.obs_u8)
+    self.rec_floats = rec_floats(self.O, self.A, self.obs_u8)
     self.norm = norm                   # (obs_min, obs_range) device tensors or None (actors.py:134-137)
     self.move = 0
     self.temperature = torch.full((self.B,), 1.0, dtype=torch.float64, device=self.device)
@@ -140,7 +141,7 @@ class TorchSelfplay(object):
   @torch.inference_mode()
   def play_move(self, out):
     """One move of every environment; the experience records go to out [B, rec_floats] (device float32 tensor)."""
-    envs, B, O, A = self.envs, self.B, self.OS, self.A
+    envs, B = self.envs, self.B
     raw = envs.obs
     obs = raw.to(torch.float32)                                     # actors.py:134
     if self.norm is not None:
@@ -148,14 +149,9 @@ class TorchSelfplay(object):
     self.search.run(obs, move=self.move)
     fin = self.search.finalize(self.temperature, None, move=self.move)
     reward, done, step, episode = envs.step()
-    if self.obs_u8:                                                 # History keeps the raw observation (game.py:93-96)
-      out.view(torch.uint8)[:, :self.O].copy_(raw.reshape(B, self.O))
-    else:
-      out[:, :O].copy_(raw.reshape(B, self.O))
-    out[:, O:O + A].copy_(fin['child_visits'])
-    out[:, O + A:O + A + 4].copy_(torch.stack((fin['root_value'], fin['error']), 1).view(torch.float32))
-    out[:, O + A + 4].copy_(reward)
-    out[:, O + A + 5:].copy_(torch.stack((fin['action'], done, step, envs.env_id, episode), 1).view(torch.float32))
+    records_fill(out, self.O, self.A, self.obs_u8, obs=raw.reshape(B, self.O),      # History keeps the raw observation (game.py:93-96)
+                 child_visits=fin['child_visits'], root_value=fin['root_value'], error=fin['error'], reward=reward,
+                 action=fin['action'], flags=done, step=step, env_id=envs.env_id, episode=episode)
     self.temperature = torch.where(done.bool(), torch.full_like(self.temperature, self.next_temperature), self.temperature)
     self.move += 1
     return fin

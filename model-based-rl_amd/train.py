@@ -20,6 +20,7 @@ from .envs import KIND_OF_ENV
 from .selfplay_search import refuse_selfplay_gumbel, refuse_selfplay_search, refuse_selfplay_true_model  # noqa: F401 (the per-flag views: imported from here)
 from .learners import Learner
 from .networks import FCNetwork
+from .record import rec_floats
 from .replay_buffer import PrioritizedReplay
 from .shared_storage import SharedStorage
 
@@ -113,7 +114,7 @@ def launch_ranks(config, max_moves, selfplay_only=False, learner_steps=None, sta
   torch_net = config.architecture != 'FCNetwork'
   O, A = int(np.prod(config.obs_space)), int(config.action_space)
   from .actors import selfplay_chunk
-  rec, chunk = ((O + 3) // 4 if getattr(config, 'obs_u8', False) else O) + A + 10, selfplay_chunk(config)
+  rec, chunk = rec_floats(O, A, getattr(config, 'obs_u8', False)), selfplay_chunk(config)
   torch.manual_seed(config.seed or 0)
   probe = get_network(config, torch.device('cpu'))
   n_flat = flat_size(probe) if torch_net else sum(v.numel() for v in probe.state_dict().values())
@@ -245,7 +246,7 @@ def _preflight_ranks(n, config):
   from .actors import selfplay_chunk
   try:
     O, A = int(np.prod(config.obs_space)), int(config.action_space)
-    rec = ((O + 3) // 4 if getattr(config, 'obs_u8', False) else O) + A + 10
+    rec = rec_floats(O, A, getattr(config, 'obs_u8', False))
     need = D.ring_bytes(n, selfplay_chunk(config), int(config.num_envs), rec)
   except (AttributeError, TypeError, ValueError):
     need = 0

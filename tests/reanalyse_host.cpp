@@ -21,7 +21,7 @@
 #define MZ_MAX_ACTIONS_K MZ_MAX_ACTIONS      // (as mz_engine.hip sets it before the kernel headers)
 #include "mz_reanalyse.hip.h"
 
-static const int O = 9, A = 9, K = 5, TD = 3, W = 64, MH = 8, R = O + A + MZR_REC_EXTRA, B = 6;
+static const int O = 9, A = 9, K = 5, TD = 3, W = 64, MH = 8, R = MZ_REC_FLOATS(O, A, 0), B = 6;
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
 static uint32_t rnd() {      // xorshift64*
@@ -49,12 +49,11 @@ struct Feed {                // B environments' running step counters
         for (int a = 0; a < A; ++a) { q[O + a] = (float)unit() + 0.01f; sum += q[O + a]; }
         for (int a = 0; a < A; ++a) q[O + a] /= sum;
         const double rv = 2.0 * unit() - 1.0, err = 2.0 * unit() - 1.0;
-        memcpy(q + O + A, &rv, 8);
-        memcpy(q + O + A + 2, &err, 8);
-        q[O + A + 4] = (float)(rnd() % 2u);
+        const float reward = (float)(rnd() % 2u);
         const bool done = unit() < p_done;
-        int32_t ints[5] = {(int32_t)(rnd() % (uint32_t)A), (done ? 1 : 0) | ((step[b] & 1) ? 2 : 0), step[b], b, episode[b]};
-        memcpy(q + O + A + 5, ints, sizeof ints);
+        const int32_t action = (int32_t)(rnd() % (uint32_t)A);
+        mz_rec_put_tail(q, O, A, rv, err, reward, action, (done ? MZ_REC_FLAG_DONE : 0) | ((step[b] & 1) ? MZ_REC_FLAG_P2 : 0), step[b], b,
+                        episode[b]);
         if (done) { step[b] = 0; ++episode[b]; } else ++step[b];
       }
     return rec.data();

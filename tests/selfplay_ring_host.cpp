@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mz_selfplay_ring.inc"
+#include "../include/mz_record.h"      // MZ_REC_FLOATS: the record's width
 
 #define CHECK(cond, ...) do { if (!(cond)) { printf("MISMATCH " __VA_ARGS__); printf("\n"); exit(1); } } while (0)
 
@@ -211,11 +212,10 @@ static void direct_origin() {
 }
 
 static void capacity() {
-  const int extra = 10;      // MZ_REC_EXTRA (include/mz_engine.h)
-  CHECK(RecordRing::capacity_for((size_t)2100 * (4000 + 3 + extra) * 4) == 32, "capacity of B 2100, O 4000, A 3");
-  CHECK(RecordRing::capacity_for((size_t)16 * (8 + 4 + extra) * 4) == 256, "capacity of B 16, O 8, A 4");
-  CHECK(RecordRing::capacity_for((size_t)4096 * (8 + 4 + extra) * 4) == 256, "capacity of B 4096, O 8, A 4");
-  CHECK(RecordRing::capacity_for((size_t)4096 * (128 + 6 + extra) * 4) == 56, "capacity of B 4096, O 128, A 6");      // (128 MiB / 2 359 296 bytes)
+  CHECK(RecordRing::capacity_for((size_t)2100 * MZ_REC_FLOATS(4000, 3, 0) * 4) == 32, "capacity of B 2100, O 4000, A 3");
+  CHECK(RecordRing::capacity_for((size_t)16 * MZ_REC_FLOATS(8, 4, 0) * 4) == 256, "capacity of B 16, O 8, A 4");
+  CHECK(RecordRing::capacity_for((size_t)4096 * MZ_REC_FLOATS(8, 4, 0) * 4) == 256, "capacity of B 4096, O 8, A 4");
+  CHECK(RecordRing::capacity_for((size_t)4096 * MZ_REC_FLOATS(128, 6, 0) * 4) == 56, "capacity of B 4096, O 128, A 6");      // (128 MiB / 2 359 296 bytes)
   CHECK(RecordRing::capacity_for((size_t)1 << 40) == 2 * MZ_GRAPH_MOVES, "the least capacity");
   cases += 5;
 }

@@ -66,6 +66,7 @@ def test_config_struct_size_matches_c():
 def test_header_is_plain_c():
   subprocess.check_call(['gcc', '-std=c99', '-fsyntax-only', '-x', 'c', os.path.join(ROOT, 'include', 'mz_engine.h')])
   subprocess.check_call(['gcc', '-std=c99', '-fsyntax-only', '-x', 'c', os.path.join(ROOT, 'include', 'mz_engine_debug.h')])
+  subprocess.check_call(['gcc', '-std=c99', '-fsyntax-only', '-x', 'c', os.path.join(ROOT, 'include', 'mz_record.h')])
 
 
 def test_no_cpu_fallback():

@@ -68,3 +68,58 @@ def test_packed_byte_observations_in_ram_records():
   (ob, ab, (tb, vb, pb)), ib, wb = rb.sample_batch()
   assert ia == ib and np.array_equal(oa, ob) and aa == ab and np.array_equal(ta, tb) and np.array_equal(va, vb) and np.array_equal(pa, pb)
   assert np.array_equal(wa, wb) and oa.dtype == np.float32
+
+
+def test_stand_alone_end_of_move_kernel_with_packed_bytes(monkeypatch):
+  """k_env_step_record -- the end of a synthetic move when the search runs as separate kernels (MZ_NO_FUSED) -- with byte
+  observations packed in the record and unpacked: one ragged workgroup (B = 17), 8 simulations, O = 5 (a last slot of one
+  byte), 5 moves of episodes of 3 steps, so that every environment ends a game and starts the next.  Every field of every
+  record against its definition: step / episode / done / env id by the episode arithmetic, observation and reward from
+  mz_synth_obs, the packed record's fields equal to the unpacked one's; and the last move's search statistics against the
+  tree the search left in the pool (visit shares, root value, error against the initial inference's value)."""
+  import numpy as np
+  import torch
+  import types
+  from model_based_rl_amd.engine import Engine, flatten_weights, records_view
+  from model_based_rl_amd.networks import FCNetwork
+  B, O, A, sims, T, moves = 17, 5, 4, 8, 3, 5
+  monkeypatch.setenv('MZ_NO_FUSED', '1')
+  torch.manual_seed(4)
+  w = flatten_weights(FCNetwork(O, A, torch.device('cpu'), types.SimpleNamespace()).state_dict())
+  out = {}
+  for packed in (False, True):
+    eng = Engine(B, O, A, sims, seed=31, env_id_offset=5)
+    eng.set_weights(w)
+    assert eng.search_kernel_info()['kind'] == 'standalone' and eng.selfplay_moves_per_launch() == 0
+    eng.selfplay_set_obs(uint8_obs=True, obs_min=[0.0], obs_range=[255.0], packed=packed)
+    eng.selfplay_export_trees(True)
+    eng.selfplay_reset(T, 1.0, stagger=False)
+    assert eng.rec_floats == (2 if packed else O) + A + 10
+    eng.selfplay_steps(moves)
+    buf, n = eng.selfplay_drain()
+    torch.cuda.synchronize()
+    assert n == moves
+    rec = buf[:n].numpy().copy()
+    v = records_view(rec, O, A, obs_u8=packed)
+    m = np.arange(moves)[:, None]
+    assert np.array_equal(v['step'], np.broadcast_to(m % T, (moves, B))) and np.array_equal(v['episode'], np.broadcast_to(m // T, (moves, B)))
+    assert np.array_equal(v['done'], np.broadcast_to(m % T == T - 1, (moves, B))) and np.all(v['to_play'] == 1)
+    assert np.array_equal(v['env_id'], np.broadcast_to(5 + np.arange(B), (moves, B)))
+    for mm in range(moves):
+      for b in range(B):
+        obs, rew = eng.synth_obs(5 + b, mm // T, mm % T)
+        assert np.array_equal(v['obs'][mm, b].astype(np.float32), obs) and v['reward'][mm, b] == np.float32(rew), (mm, b)
+    if packed:
+      assert not rec[..., :2].copy().view(np.uint8)[..., O:].any()      # the last slot's three spare bytes
+    t = eng.export_tree()
+    N, W = t['N'][:, 1:1 + A].astype(np.float64), t['W']
+    assert np.all(t['N'][:, 0] == sims)
+    assert np.array_equal(v['child_visits'][-1], (N / N.sum(1, keepdims=True)).astype(np.float32))
+    assert np.array_equal(v['root_value'][-1], W[:, 0] / t['N'][:, 0])
+    v0 = eng.root_outputs()[0].cpu().numpy().astype(np.float64)
+    assert np.array_equal(v['error'][-1], v['root_value'][-1] - v0)
+    assert np.all(np.take_along_axis(v['child_visits'], v['action'][..., None].astype(np.int64), -1) > 0)
+    out[packed] = v
+    eng.close()
+  for k in out[False]:
+    assert np.array_equal(np.asarray(out[False][k], np.float64 if k == 'obs' else None), np.asarray(out[True][k], np.float64 if k == 'obs' else None)), k

@@ -139,6 +139,15 @@ def test_vectorised_draws_are_random_uniform():
     assert np.array_equal(lo + (hi - lo) * u, want) and random.random() == nxt
 
 
+def make_records(shape, O, A, **fields):
+  """float32 experience records [*shape, rec_floats(O, A)]: the given fields through record.records_fill (each broadcast to
+  shape, obs to shape + [O], child_visits to shape + [A]), every other slot zero"""
+  from model_based_rl_amd.record import rec_floats, records_fill
+  wide = dict(obs=(O,), child_visits=(A,))
+  return records_fill(np.zeros(tuple(shape) + (rec_floats(O, A),), np.float32), O, A,
+                      **{k: np.broadcast_to(np.asarray(v), tuple(shape) + wide.get(k, ())) for k, v in fields.items()})
+
+
 def python_flush_rules(dones, errors, max_history_length, overlap):
   """actors.py:160-169 + replay_buffer.py:113-122 for one env's stream of steps: returns the list of
   priorities-in-order that reach the tree, frames and games."""
@@ -166,24 +175,23 @@ def test_ingest_records_flush_rules(T, mhl):
   from model_based_rl_amd.replay_buffer import PrioritizedReplay
   O, A, B, moves = 3, 2, 5, 260
   rng = np.random.RandomState(T)
-  rec = np.zeros((moves, B, O + A + 10), np.float32)
-  rec[..., :O] = rng.standard_normal((moves, B, O))
+  obs = rng.standard_normal((moves, B, O))
   err = rng.standard_normal((moves, B))                           # error: a float64 in two float slots
-  rec[..., O + A + 2:O + A + 4] = err[..., None].view(np.float32)
-  ints = rec[..., O + A + 5:].view(np.int32)
+  done, step = np.zeros((moves, B), np.int32), np.zeros((moves, B), np.int32)
   t0 = rng.randint(0, T, B)
   for b in range(B):
     t = t0[b]
     for m in range(moves):
-      ints[m, b, 1] = int(t + 1 >= T); ints[m, b, 2] = t; ints[m, b, 3] = b
+      done[m, b] = int(t + 1 >= T); step[m, b] = t
       t = 0 if t + 1 >= T else t + 1
+  rec = make_records((moves, B), O, A, obs=obs, error=err, flags=done, step=step, env_id=np.arange(B))
   rep = PrioritizedReplay(make_cfg(obs_space=(O,), action_space=A, max_history_length=mhl, window_size=4096))
   # feed in two chunks to exercise state carried between calls
   rep.ingest_records(rec[:100], 100, B)
   rep.ingest_records(rec[100:], moves - 100, B)
   # expected: the tree receives leaves in (move, env) arrival order of the flushes
   want, games = [], 0
-  per_env = [python_flush_rules(ints[:, b, 1].astype(bool), err[:, b], mhl, 15) for b in range(B)]
+  per_env = [python_flush_rules(done[:, b].astype(bool), err[:, b], mhl, 15) for b in range(B)]
   frames = sum(len(p[0]) for p in per_env); games = sum(p[1] for p in per_env)
   assert rep.get_throughput() == {'frames': frames, 'games': games}
   assert rep.size() == min(frames, 4096)
@@ -234,17 +242,16 @@ def test_sample_batch_matches_reference(path):
 
 
 def _bulk_records(rng, moves, B, O, A, T, two_player_bit=False):
-  rec = np.zeros((moves, B, O + A + 10), np.float32)
-  rec[..., :O + A] = rng.standard_normal((moves, B, O + A))
-  rec[..., O + A:O + A + 2] = rng.standard_normal((moves, B))[..., None].view(np.float32)        # root value (float64)
-  rec[..., O + A + 2:O + A + 4] = rng.standard_normal((moves, B))[..., None].view(np.float32)    # error (float64)
-  rec[..., O + A + 4] = rng.uniform(-1, 1, (moves, B))
-  ints = rec[..., O + A + 5:].view(np.int32)
+  head = rng.standard_normal((moves, B, O + A))
+  rootv, err = rng.standard_normal((moves, B)), rng.standard_normal((moves, B))      # root value, error (float64)
+  rew = rng.uniform(-1, 1, (moves, B))
+  act, done, step = (np.zeros((moves, B), np.int32) for _ in range(3))
   t = rng.randint(0, T, B)
   for m in range(moves):
-    ints[m, :, 0] = rng.randint(0, A, B); ints[m, :, 1] = t + 1 >= T; ints[m, :, 2] = t; ints[m, :, 3] = np.arange(B)
+    act[m] = rng.randint(0, A, B); done[m] = t + 1 >= T; step[m] = t
     t = np.where(t + 1 >= T, 0, t + 1)
-  return rec
+  return make_records((moves, B), O, A, obs=head[..., :O], child_visits=head[..., O:], root_value=rootv, error=err, reward=rew,
+                      action=act, flags=done, step=step, env_id=np.arange(B))
 
 
 @pytest.mark.parametrize('T,mhl,window', [(40, 500, 1 << 15), (23, 16, 1 << 15), (40, 500, 3000)])
@@ -410,12 +417,11 @@ def test_records_with_to_play_equal_save_history():
   rew = np.zeros(n, np.float32); rew[-1] = 1.0; rew[2] = 0.5       # (a mid-game reward makes the flips visible)
   act = rng.randint(0, A, n).astype(np.int32)
   tp = np.array([1, -1, 1, -1, 1, -1, 1], np.int8)
-  rec = np.zeros((n, 1, O + A + 10), np.float32)
-  rec[:, 0, :O] = obs; rec[:, 0, O:O + A] = cv
-  rec[:, 0, O + A:O + A + 2] = rootv[:, None].view(np.float32); rec[:, 0, O + A + 2:O + A + 4] = err[:, None].view(np.float32)
-  rec[:, 0, O + A + 4] = rew
-  ints = rec[..., O + A + 5:].view(np.int32)
-  ints[:, 0, 0] = act; ints[:, 0, 1] = (np.arange(n) == n - 1) | ((tp < 0) << 1); ints[:, 0, 2] = np.arange(n)
+  flags = ((np.arange(n) == n - 1) | ((tp < 0) << 1)).astype(np.int32)
+  with_flags = lambda fl: make_records((n, 1), O, A, obs=obs[:, None], child_visits=cv[:, None], root_value=rootv[:, None],
+                                       error=err[:, None], reward=rew[:, None], action=act[:, None], flags=fl[:, None],
+                                       step=np.arange(n)[:, None])
+  rec = with_flags(flags)
   out = []
   for via_records in (True, False):
     rep = PrioritizedReplay(make_cfg(window_size=64, two_players=True, batch_size=8, td_steps=3, seed=None))
@@ -431,7 +437,7 @@ def test_records_with_to_play_equal_save_history():
   for a, b in zip(*out):
     assert np.array_equal(np.asarray(a), np.asarray(b)) if not isinstance(a, dict) else a == b
   # and the flips are real: with every to_play = +1 the value targets differ
-  rec1 = rec.copy(); rec1[..., O + A + 5:].view(np.int32)[:, 0, 1] &= 1
+  rec1 = with_flags(flags & 1)
   rep = PrioritizedReplay(make_cfg(window_size=64, two_players=True, batch_size=8, td_steps=3, seed=None))
   rep.ingest_records(rec1, n, 1)
   random.seed(1); np.random.seed(2)
@@ -481,6 +487,17 @@ def test_deferred_insertion_is_invisible():
       assert np.array_equal(np.asarray(x), np.asarray(y)) if not isinstance(x, dict) else x == y, a[0]
 
 
+def _two_game_records(rng, n, B, O, A):
+  """n moves of B environments: one game of n // 2 + 1 moves (episode 0), then one of the rest (episode 1)"""
+  obs, cv = rng.standard_normal((n, B, O)), rng.dirichlet([1.0] * A, size=(n, B))
+  rootv, err = rng.standard_normal((n, B)), np.abs(rng.standard_normal((n, B))) + 0.05
+  rew, act = rng.uniform(-1, 1, (n, B)), rng.randint(0, A, (n, B))
+  m = np.arange(n)[:, None]
+  return make_records((n, B), O, A, obs=obs, child_visits=cv, root_value=rootv, error=err, reward=rew, action=act,
+                      flags=(m == n // 2) | (m == n - 1), step=np.where(m <= n // 2, m, m - n // 2 - 1), env_id=np.arange(B),
+                      episode=m > n // 2)
+
+
 def test_sample_batches_arrays_equals_consecutive_calls():
   """PrioritizedReplay.sample_batches_arrays(n) (one native call for the batches the learner samples ahead) against n
   sample_batch_arrays() calls on a twin replay from the same generator state: same draws, beta steps, weights, targets"""
@@ -489,16 +506,7 @@ def test_sample_batches_arrays_equals_consecutive_calls():
   rng = np.random.RandomState(3)
   O, A, B, n = 5, 3, 8, 40
   reps = [PrioritizedReplay(make_cfg(obs_space=(O,), action_space=A, window_size=4096, batch_size=32, discount=0.99)) for _ in range(2)]
-  rec = np.zeros((n, B, O + A + 10), np.float32)
-  rec[..., :O] = rng.standard_normal((n, B, O))
-  rec[..., O:O + A] = rng.dirichlet([1.0] * A, size=(n, B))
-  rec[..., O + A:O + A + 2] = np.ascontiguousarray(rng.standard_normal((n, B))).view(np.float32).reshape(n, B, 2)
-  rec[..., O + A + 2:O + A + 4] = np.ascontiguousarray(np.abs(rng.standard_normal((n, B))) + 0.05).view(np.float32).reshape(n, B, 2)
-  rec[..., O + A + 4] = rng.uniform(-1, 1, (n, B))
-  ints = rec[..., O + A + 5:].view(np.int32)
-  ints[..., 0] = rng.randint(0, A, (n, B)); ints[n // 2, :, 1] = 1; ints[-1, :, 1] = 1
-  ints[..., 2] = np.concatenate([np.arange(n // 2 + 1), np.arange(n - n // 2 - 1)])[:, None]; ints[..., 3] = np.arange(B)[None, :]
-  ints[n // 2 + 1:, :, 4] = 1
+  rec = _two_game_records(rng, n, B, O, A)
   for r in reps:
     r.ingest_records(rec, n, B)
   assert reps[0].size() == reps[1].size() > 100
@@ -528,16 +536,7 @@ def test_native_sample_batches_full_equals_the_python_path(beta0, A):
   O, B, n, bs, K = 5, 8, 40, 32, 5
   reps = [PrioritizedReplay(make_cfg(obs_space=(O,), action_space=A, window_size=4096, batch_size=bs, discount=0.99, beta=beta0))
           for _ in range(2)]
-  rec = np.zeros((n, B, O + A + 10), np.float32)
-  rec[..., :O] = rng.standard_normal((n, B, O))
-  rec[..., O:O + A] = rng.dirichlet([1.0] * A, size=(n, B))
-  rec[..., O + A:O + A + 2] = np.ascontiguousarray(rng.standard_normal((n, B))).view(np.float32).reshape(n, B, 2)
-  rec[..., O + A + 2:O + A + 4] = np.ascontiguousarray(np.abs(rng.standard_normal((n, B))) + 0.05).view(np.float32).reshape(n, B, 2)
-  rec[..., O + A + 4] = rng.uniform(-1, 1, (n, B))
-  ints = rec[..., O + A + 5:].view(np.int32)
-  ints[..., 0] = rng.randint(0, A, (n, B)); ints[n // 2, :, 1] = 1; ints[-1, :, 1] = 1
-  ints[..., 2] = np.concatenate([np.arange(n // 2 + 1), np.arange(n - n // 2 - 1)])[:, None]; ints[..., 3] = np.arange(B)[None, :]
-  ints[n // 2 + 1:, :, 4] = 1
+  rec = _two_game_records(rng, n, B, O, A)
   for r in reps:
     r.ingest_records(rec, n, B)
   nb = 4
