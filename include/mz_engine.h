@@ -540,6 +540,21 @@ int mz_reanalyse(mz_engine *e, int kind, const float *rows_host, int rec_floats,
 int mz_reanalyse_gumbel(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
                         int num_simulations, int value_kind, uint64_t draw_key, void *stream);
 
+/* Reanalyse on the true rules (DESIGN s7n), for the two board games (kind 1 TicTacToe, 3 Connect Four): mz_reanalyse's buffers,
+ * layouts, pinned-memory requirement and chunks, and what it stores -- visit shares and the root's mean value, the fields of a
+ * record of mz_selfplay_set_true_model --, but each chunk is searched as a self-play move of that mode is: observe,
+ * mz_initial_inference, the root WITHOUT noise, slot 0 of the true-rules tree from the stored row itself, then num_simulations
+ * of the true-rules search, in one launch (fused != 0, mz_tm_search_fused's kernel) or in the two-launch loop (mz_tm_search's).
+ * The root's position follows from the row alone: both games store mover * board, so board = to_play * observation with to_play
+ * from bit 1 of the flags word, and the plies played are the stones on it.  The two forms give the same bits, and the same as
+ * mz_root_prepare / mz_tm_root / mz_tm_search on those boards.  One synchronisation at the end; afterwards the engine's
+ * stepwise state is what mz_tm_search leaves after num_simulations on the last chunk.  A row must hold a live position (as for
+ * mz_reanalyse: not checked).
+ * Refused: weights not set; no true-rules search set (mz_set_true_model); kind other than 1 or 3 or other than the search's
+ * game; another rec_floats; n_rows < 0; num_simulations outside 1 .. the engine's; buffers that are not page-locked. */
+int mz_reanalyse_true_model(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
+                            int num_simulations, int fused, void *stream);
+
 /* Raw tree dump (Node objects of mcts.py:28-45 in SoA form) to [host] arrays, synchronous.
  * Each per-node array is [B][NN]; minmax [B][2]; legal_mask [B] (bit a = root child a exists);
  * noise [B][A] (the Dirichlet draw last mixed in).  Any pointer may be NULL. */

@@ -196,6 +196,7 @@ SIGNATURES = {
     'mz_match_log_capacity': (_I, [_VP]),
     'mz_reanalyse': (_I, [_VP, _I, _VP, _I, _I, _VP, _I, _VP]),
     'mz_reanalyse_gumbel': (_I, [_VP, _I, _VP, _I, _I, _VP, _I, _I, _U64, _VP]),
+    'mz_reanalyse_true_model': (_I, [_VP, _I, _VP, _I, _I, _VP, _I, _I, _VP]),
     'mz_export_tree': (_I, [_VP] * 11),
     'mz_affine_relu': (_I, [_VP, _VP, _VP, _VP, _SZ, _I, _I, _VP]),
     'mz_nodes_per_tree': (_I, [_VP]),

@@ -157,6 +157,10 @@ def build_parser():
   a('--reanalyse_gumbel_scale', type=float, default=0.0,
     help='--reanalyse_gumbel: the scale of the Gumbel noise at a reanalysed root; 0 (the default) draws none: a reanalysed root '
          'needs a policy target, not exploration')
+  a('--reanalyse_true_model', action='store_true',
+    help='--reanalyse_rows on TicTacToe / ConnectFour: the passes search the stored positions on the TRUE rules below the root, as '
+         '--selfplay_true_model searches its moves, and write visit shares and the root\'s mean value; with --selfplay_true_model '
+         '(one kind of target in the replay), or alone: PUCT self-play whose targets are refreshed on the true rules (reanalyse.py)')
   a('--selfplay_gumbel', action='store_true',
     help='TicTacToe / ConnectFour / CartPole-v0 / -v1 on the device: the self-play moves are searched with the Gumbel MuZero '
          'search at --num_simulations (8 or 16 are its range), the records carry the improved policy pi\' as the policy target and '

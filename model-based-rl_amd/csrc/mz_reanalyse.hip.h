@@ -16,10 +16,17 @@
 //
 //   k_reanalyse_store_gumbel  the root's improved policy pi' as float32 where k_reanalyse_store puts the visit shares, then the
 //                             root's mean value or its v_mix as the float64; k_gz_pick's mapping and mz_gz_root_pick, not restated
+//
+// Reanalyse on the true rules (mz_reanalyse_true_model; DESIGN s7n) keeps k_reanalyse_observe and k_reanalyse_store, and searches a
+// stored position as a self-play move of mz_selfplay_set_true_model does (mz_truemodel.hip.h), from
+//
+//   k_tm_root_reanalyse       slot 0 of the true-rules tree = the position the stored observation and the record's mover determine
+//                             (mz_reanalyse_position), then the root's first descent: k_tm_root_selfplay with the row as the environment
 #pragma once
 #include "mz_common.h"
 #include "mz_tree.hip.h"
 #include "mz_gumbel.hip.h"
+#include "mz_truemodel.hip.h"
 #include "mz_record.h"
 
 // Separate from SelfplayState / EvalState / MatchState: self-play, evaluation and matches on the same engine are untouched.
@@ -43,6 +50,20 @@ __host__ __device__ inline uint32_t mz_reanalyse_legal_mask(int kind, const floa
     mask = A >= 32 ? 0xFFFFFFFFu : ((1u << A) - 1u);
   }
   return mask;
+}
+
+// The position of a stored row of a board game (kind 1 TicTacToe: 9 cells, 3 Connect Four: 42), from its observation and its mover:
+// both games store mover * board, so the board is to_play * obs, and a ply puts one stone: *step = the non-zero cells.  to_play is
+// the record's (MZ_REC_FLAG_P2), never the stones' parity: a position is a position for either mover.  bd: the game's cells, no more.
+__host__ __device__ inline void mz_reanalyse_position(int kind, const float *obs, int to_play, int8_t *bd, int32_t *step) {
+  const int cells = mz_game_info(kind).cells;      // (mz_games.h: the one statement of the games' sizes)
+  int32_t n = 0;
+  for (int k = 0; k < cells; ++k) {
+    const int v = to_play * (int)obs[k];
+    bd[k] = (int8_t)v;
+    n += v != 0 ? 1 : 0;
+  }
+  *step = n;
 }
 
 // rows: the chunk's first row, [n][R] of unpacked records (include/mz_record.h; the mover is read from the flags word).  One thread per (row, observation element): neighbouring threads read neighbouring floats of the host row;
@@ -100,4 +121,27 @@ __global__ __launch_bounds__(64) void k_reanalyse_store_gumbel(TreeView t, GzSta
   const unsigned long long bits = (unsigned long long)__double_as_longlong(rv);
   ((uint32_t *)row)[A] = (uint32_t)bits;
   ((uint32_t *)row)[A + 1] = (uint32_t)(bits >> 32);
+}
+
+// mz_tm_root for a reanalysed row (mz_reanalyse_true_model; DESIGN s7n): k_tm_root_selfplay's shape, one G-lane group per tree, the
+// root's position from what k_reanalyse_observe left on the device -- rs.obs at stride O, rs.to_play --, no host copy.  A row past
+// the chunk's n is the empty board with +1 to move and every action legal; k_reanalyse_store stores nothing for it.
+template <int G>
+__global__ void k_tm_root_reanalyse(TreeView t, TmState tm, int O, ReanalyseState rs) {
+  const int gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = gt / G, lane = gt % G;
+  if (b >= t.B) return;
+  if (lane == 0) {
+    MzTmSlotBits u;
+    u.q[0] = u.q[1] = u.q[2] = u.q[3] = mz_i32x4{0, 0, 0, 0};
+    const int tp = (int)rs.to_play[b];
+    int32_t step;
+    mz_reanalyse_position(tm.kind, rs.obs + (size_t)b * O, tp, u.s.bd, &step);
+    u.s.mask = t.legal[b];
+    u.s.step = step;
+    u.s.mover = (int8_t)tp;
+    mz_tm_slot_store(tm.slots + (size_t)b * (size_t)(t.sims + 1), u);
+  }
+  __threadfence_block();
+  mz_tm_select<G>(t, tm, O, b, lane);
 }

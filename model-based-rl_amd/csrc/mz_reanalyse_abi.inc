@@ -130,3 +130,70 @@ int mz_reanalyse_gumbel(mz_engine *e, int kind, const float *rows_host, int rec_
   HIPCHECK(hipStreamSynchronize(s));
   return 0;
 }
+
+// Reanalyse on the true rules (DESIGN s7n): mz_reanalyse's buffers, chunks and stored fields -- visit shares and the root's mean
+// value, what a record of mz_selfplay_set_true_model holds --, searched as a self-play move of that mode is (launch_move_game,
+// mz_selfplay_abi.inc): the root without noise, slot 0 from the stored observation and the record's mover (k_tm_root_reanalyse),
+// then all simulations in one launch of k_tm_search (fused) or the two-launch loop.  k_tree_root leaves the first descent to
+// k_tm_root_reanalyse, which makes it with the leaf's position: the descent writes nothing but the selection.  The host side of
+// the step protocol starts over at every chunk and ends where the search leaves it.
+int mz_reanalyse_true_model(mz_engine *e, int kind, const float *rows_host, int rec_floats, int n_rows, float *fresh_host,
+                            int num_simulations, int fused, void *stream) {
+  if (!e) return fail("mz_reanalyse_true_model: null engine");
+  MZ_ENTER(e);
+  if (!e->weights_set) return fail("mz_reanalyse_true_model: weights not set (call mz_set_weights)");
+  if (!e->tm.kind) return fail("mz_reanalyse_true_model: no true-rules search is set on this engine (call mz_set_true_model first)");
+  if (kind != 1 && kind != 3)
+    return fail("mz_reanalyse_true_model: kind must be 1 (TicTacToe) or 3 (Connect Four), the games with true rules, got %d", kind);
+  if (kind != e->tm.kind)
+    return fail("mz_reanalyse_true_model: kind %d is not the game of the engine's true-rules search (mz_set_true_model %d)", kind, e->tm.kind);
+  if (rec_floats != MZ_REC_FLOATS(e->O, e->A, 0))
+    return fail("mz_reanalyse_true_model: rec_floats %d != obs_dim + action_space + %d = %d", rec_floats, MZ_REC_EXTRA, MZ_REC_FLOATS(e->O, e->A, 0));
+  if (n_rows < 0) return fail("mz_reanalyse_true_model: n_rows must be >= 0, got %d", n_rows);
+  if (num_simulations < 1 || num_simulations > e->sims)
+    return fail("mz_reanalyse_true_model: num_simulations must be in 1 .. %d (the engine's pool), got %d", e->sims, num_simulations);
+  if (n_rows == 0) return 0;
+  if (!rows_host || !fresh_host) return fail("mz_reanalyse_true_model: null buffer");
+  const float *rows_dev = nullptr;
+  float *fresh_dev = nullptr;
+  if (hipHostGetDevicePointer((void **)&rows_dev, (void *)rows_host, 0) != hipSuccess || !rows_dev ||
+      hipHostGetDevicePointer((void **)&fresh_dev, (void *)fresh_host, 0) != hipSuccess || !fresh_dev) {
+    (void)hipGetLastError();
+    return fail("mz_reanalyse_true_model: rows and fresh must be page-locked (pinned) host memory");
+  }
+  ReanalyseState &rs = e->ra;
+  const int B = e->B, O = e->O, A = e->A;
+  if (!rs.to_play) {      // (as mz_reanalyse: allocated on the first call of any of the three)
+    rs = ReanalyseState{};
+    if (dmalloc(e, &rs.obs, (size_t)e->Bp * O) || dmalloc(e, &rs.legal, (size_t)B * A) || dmalloc(e, &rs.to_play, (size_t)B)) {
+      rs = ReanalyseState{};
+      return -1;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 block(128), grid_obs(((size_t)B * O + 127) / 128), grid_store(((size_t)B * (A + 2) + 127) / 128);
+  // one chunk; a launch that fails leaves rc set, and what it had enqueued is waited for below
+  auto chunk = [&](int at, int n) -> int {
+    hipLaunchKernelGGL(k_reanalyse_observe, grid_obs, block, 0, s, rs, rows_dev + (size_t)at * rec_floats, n, rec_floats, kind, B, O, A);
+    if (hipGetLastError() != hipSuccess) return fail("mz_reanalyse_true_model: k_reanalyse_observe did not launch");
+    if (mz_initial_inference(e, rs.obs, s)) return -1;
+    TREE_LAUNCH(k_tree_root, s, e->tv, (const int8_t *)rs.to_play, (const uint8_t *)rs.legal, (const double *)nullptr,
+                e->cfg.root_exploration_fraction, 0);
+    step_restart(e, false, MZ_SP_TRUE_RULES);
+    TREE_LAUNCH(k_tm_root_reanalyse, s, e->tv, e->tm, O, rs);
+    HIPCHECK(hipGetLastError());
+    if (fused ? tm_simulations_fused(e, "mz_reanalyse_true_model", num_simulations, s)
+              : tm_simulations(e, "mz_reanalyse_true_model", num_simulations, s)) return -1;
+    hipLaunchKernelGGL(k_reanalyse_store, grid_store, block, 0, s, e->tv, fresh_dev + (size_t)at * (A + 2), n);
+    if (hipGetLastError() != hipSuccess) return fail("mz_reanalyse_true_model: k_reanalyse_store did not launch");
+    return 0;
+  };
+  int rc = 0;
+  for (int at = 0; at < n_rows && !rc; at += B) rc = chunk(at, n_rows - at < B ? n_rows - at : B);
+  if (rc) {      // what was enqueued still reads / writes the caller's buffers: let it end before they are handed back
+    (void)hipStreamSynchronize(s);
+    return -1;
+  }
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}

@@ -801,6 +801,15 @@ class Engine(object):
                                             self.SELFPLAY_GUMBEL_VALUES[value], int(draw_key) & 0xFFFFFFFFFFFFFFFF, self.stream),
                'mz_reanalyse_gumbel')
 
+  def reanalyse_true_model(self, rows, fresh, n_rows, kind, num_simulations=None, fused=True):
+    """mz_reanalyse_true_model (DESIGN s7n; set_true_model with the game's kind first): reanalyse's buffers, chunks and stored
+    fields -- visit shares and the root's mean value, what a record of selfplay_set_true_model holds --, searched on the true
+    rules of TicTacToe / Connect Four from the position the stored observation and the record's mover determine.  fused: the
+    simulations of a chunk in one launch (tm_search_fused), else tm_search's two launches per simulation; the same bits."""
+    kind, n_rows, sims = self._reanalyse_args('reanalyse_true_model', rows, fresh, n_rows, kind, num_simulations)
+    _abi.check(self.lib.mz_reanalyse_true_model(self._h, kind, _ptr(rows), int(rows.shape[1]), n_rows, _ptr(fresh), sims,
+                                                int(bool(fused)), self.stream), 'mz_reanalyse_true_model')
+
   def export_tree(self, hidden=False):
     B, NN, A = self.B, self.NN, self.A
     d = dict(N=np.zeros((B, NN), np.int32), W=np.zeros((B, NN)), P=np.zeros((B, NN)),

@@ -8,6 +8,8 @@ statistics back in place.  The replay builds its n-step targets at sampling time
                           search, store (csrc/mz_reanalyse.hip.h; no host work between chunks)    -> pinned fresh
                           (--reanalyse_gumbel: Engine.reanalyse_gumbel, the Gumbel search, pi' and
                           the value kind of --selfplay_gumbel's records; DESIGN s7j)
+                          (--reanalyse_true_model: Engine.reanalyse_true_model, PUCT on the true rules
+                          of TicTacToe / ConnectFour below the stored position; DESIGN s7n)
   replay.reanalyse_write  child_visits and root_value of exactly those rows                       <- pinned fresh
 
 Not part of this: exploration noise at the reanalysed root; refreshing the stored error or the priorities (the learner's own
@@ -22,7 +24,7 @@ import torch
 from .actors import _call
 from .engine import Engine
 from .record import rec_floats
-from .envs import KIND_OF_ENV
+from .envs import BOARD_KINDS, KIND_OF_ENV
 from .selfplay_search import selfplay_gumbel_params
 
 KINDS = KIND_OF_ENV      # (envs.DEVICE_GAMES; anything else: 0, all actions legal)
@@ -45,6 +47,23 @@ def refuse_reanalyse_gumbel(config):
   scale = float(getattr(config, 'reanalyse_gumbel_scale', 0.0))
   if not scale >= 0:
     raise no('--reanalyse_gumbel_scale must not be negative, got %g.' % scale)
+
+
+def refuse_reanalyse_true_model(config):
+  """what --reanalyse_true_model is not built for, one sentence each, before any device is touched (--reanalyse_rows' own refusals
+  apply beside these: refuse_reanalyse).  Without --selfplay_true_model it is allowed: PUCT self-play on the learned model whose
+  targets are refreshed on the true rules -- visit shares and mean values on both sides, one kind of target in the replay"""
+  if not getattr(config, 'reanalyse_true_model', False):
+    return
+  no = lambda why: SystemExit('--reanalyse_true_model: ' + why)
+  if int(getattr(config, 'reanalyse_rows', 0) or 0) <= 0:
+    raise no('it chooses the search of the Reanalyse passes and does nothing without --reanalyse_rows above 0.')
+  if str(getattr(config, 'environment', '')) not in BOARD_KINDS:
+    raise no('the true rules are those of the device board games (%s), %s has none.' % (', '.join(BOARD_KINDS), config.environment))
+  if int(getattr(config, 'stack_obs', 1) or 1) > 1:
+    raise no('--stack_obs above 1 stores several frames per row, and a position is read from one board.')
+  if getattr(config, 'selfplay_gumbel', False) or getattr(config, 'reanalyse_gumbel', False):
+    raise no('--selfplay_gumbel and --reanalyse_gumbel put pi\' into the replay and this writes visit shares; a replay holds one of the two.')
 
 
 def refuse_reanalyse(config, ranks=0):
@@ -70,7 +89,9 @@ def refuse_reanalyse(config, ranks=0):
 class Reanalyser(object):
   """Reanalyser(config, replay, device=None, batch=None): an Engine of its own (B = batch or min(num_envs, 4096), the actor's
   search settings) and two pinned buffers; set_weights(flat or state_dict), then run(max_rows) per pass.  With
-  config.reanalyse_gumbel the engine searches with the Gumbel search and run(max_rows, draw_key) writes pi' (DESIGN s7j)."""
+  config.reanalyse_gumbel the engine searches with the Gumbel search and run(max_rows, draw_key) writes pi' (DESIGN s7j); with
+  config.reanalyse_true_model it searches the true rules of the board game, all simulations of a chunk in one launch, and
+  run(max_rows) writes what it always does (DESIGN s7n)."""
 
   def __init__(self, config, replay, device=None, batch=None, max_rows=None):
     self.config, self.replay = config, replay
@@ -85,6 +106,10 @@ class Reanalyser(object):
     self.gumbel_value = getattr(config, 'selfplay_gumbel_value', 'mean') if self.gumbel else None
     if self.gumbel:
       self.engine.set_gumbel(True, *selfplay_gumbel_params(config)[:3], float(getattr(config, 'reanalyse_gumbel_scale', 0.0) or 0.0))
+    # --reanalyse_true_model (DESIGN s7n): the stored positions are searched on the game's own rules; no draw, no key
+    self.true_model = bool(getattr(config, 'reanalyse_true_model', False))
+    if self.true_model:
+      self.engine.set_true_model(self.kind)
     self.rows = self.fresh = None
     self.max_rows = 0
     self._size(int(max_rows or getattr(config, 'reanalyse_rows', 0) or 0))
@@ -99,7 +124,8 @@ class Reanalyser(object):
     self.engine.set_weights(weights)
 
   def run(self, max_rows=None, draw_key=0):
-    """one pass: pick -> Engine.reanalyse (Engine.reanalyse_gumbel under --reanalyse_gumbel, draw_key in the key of its draws) -> write.  -> dict(rows, slices, skipped_slices, seconds, mean_abs_value_change,
+    """one pass: pick -> Engine.reanalyse (Engine.reanalyse_gumbel under --reanalyse_gumbel, draw_key in the key of its draws;
+    Engine.reanalyse_true_model under --reanalyse_true_model) -> write.  -> dict(rows, slices, skipped_slices, seconds, mean_abs_value_change,
     mean_policy_l1, busy): rows written, and the means over them of |new - old root_value| and of the L1 distance between the old
     and the new child_visits.  busy: another pass over the same replay holds its one ticket (several actors share a replay and
     pull weights at the same steps): this pass is skipped, nothing is searched or written"""
@@ -114,6 +140,8 @@ class Reanalyser(object):
       try:
         if self.gumbel:
           self.engine.reanalyse_gumbel(self.rows, self.fresh, n, self.kind, value=self.gumbel_value, draw_key=draw_key)
+        elif self.true_model:
+          self.engine.reanalyse_true_model(self.rows, self.fresh, n, self.kind, fused=True)
         else:
           self.engine.reanalyse(self.rows, self.fresh, n, self.kind)
       except BaseException:

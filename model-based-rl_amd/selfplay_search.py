@@ -42,7 +42,8 @@ _GUMBEL = (
 )
 _TRUE_RULES = (
     (lambda c, ranks, m: _get(c, 'selfplay_gumbel'), _TWO),
-    (lambda c, ranks, m: _reanalyse(c), '--reanalyse_rows would write learned-model targets into the same replay; a true-rules Reanalyse is not built.'),
+    # (--reanalyse_true_model is the way through: reanalyse.refuse_reanalyse_true_model, DESIGN s7n)
+    (lambda c, ranks, m: _reanalyse(c) and not _get(c, 'reanalyse_true_model'), '--reanalyse_rows would write learned-model targets into the same replay; a true-rules Reanalyse is not built.'),
 )
 Mode = collections.namedtuple('Mode', 'flag options envs words requires')
 # In the order train's preflight asks.  A new mode is one more row here (and one in csrc/mz_selfplay_mode.inc).

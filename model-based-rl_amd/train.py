@@ -325,9 +325,10 @@ def main(argv=None):
     cfg.seed = 0
   if cfg.run_tag is None:           # train.py:83-90: a date-stamped run directory (the launcher's start time under --ranks)
     cfg.run_tag = os.environ.get('MZ_RUN_TAG') or time.strftime('%Y-%m-%d_%H-%M-%S')
-  from .reanalyse import refuse_reanalyse, refuse_reanalyse_gumbel
+  from .reanalyse import refuse_reanalyse, refuse_reanalyse_gumbel, refuse_reanalyse_true_model
   refuse_reanalyse(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))      # (before any rank or device exists)
   refuse_reanalyse_gumbel(cfg)                                                # (--reanalyse_gumbel: likewise)
+  refuse_reanalyse_true_model(cfg)                                            # (--reanalyse_true_model: likewise)
   from .symmetry import refuse_symmetry
   refuse_symmetry(cfg)                                                        # (--symmetry: likewise)
   refuse_selfplay_search(cfg, ranks or int(os.environ.get('WORLD_SIZE', '1')))   # (--selfplay_gumbel, --selfplay_true_model: likewise)

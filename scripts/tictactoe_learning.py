@@ -9,9 +9,11 @@ opponent on the host's TicTacToe rules, 512 games as each side, next to the untr
                                        [--opp_playouts 1024] [--symmetry] [--grade [--grade_table] [--grade_unroll K]] [--true_model] [--gumbel]
                                        [--selfplay_gumbel [--num_simulations 8] [--selfplay_gumbel_value vmix] ...]
                                        [--selfplay_true_model [--selfplay_true_model_loop]]
-                                       [--reanalyse_rows N [--reanalyse_every K] [--reanalyse_gumbel [--reanalyse_gumbel_scale S]]]
---reanalyse_rows / --reanalyse_every / --reanalyse_gumbel / --reanalyse_gumbel_scale are train's flags, passed on to the training run
-(--reanalyse_gumbel: Reanalyse with the Gumbel search for a --selfplay_gumbel run, reanalyse.py).
+                                       [--reanalyse_rows N [--reanalyse_every K] [--reanalyse_gumbel [--reanalyse_gumbel_scale S]]
+                                                           [--reanalyse_true_model]]
+--reanalyse_rows / --reanalyse_every / --reanalyse_gumbel / --reanalyse_gumbel_scale / --reanalyse_true_model are train's flags, passed
+on to the training run (--reanalyse_gumbel: Reanalyse with the Gumbel search for a --selfplay_gumbel run; --reanalyse_true_model:
+Reanalyse on the game's true rules, with --selfplay_true_model or with plain PUCT self-play; reanalyse.py).
 --selfplay_gumbel adds train's flag (self-play searched with the Gumbel search, the learner trained on pi'; selfplay_search.py) with
 its --selfplay_gumbel_* parameters, and --num_simulations sets the simulations of the TRAINING run's self-play; the evaluation
 blocks below stay as they are -- PUCT at 30 simulations unless --gumbel is given.
@@ -105,6 +107,8 @@ def build_parser():
   ap.add_argument('--reanalyse_gumbel', action='store_true',
                   help='train --reanalyse_gumbel: with --selfplay_gumbel and --reanalyse_rows, the passes search with the Gumbel search and write pi\'')
   ap.add_argument('--reanalyse_gumbel_scale', type=float, default=None, help='train --reanalyse_gumbel_scale')
+  ap.add_argument('--reanalyse_true_model', action='store_true',
+                  help='train --reanalyse_true_model: with --reanalyse_rows, the passes search the stored positions on the true rules')
   ap.add_argument('--keep_checkpoint', default=None, help='copy the run\'s last checkpoint to this file')
   ap.add_argument('--match_against', default=None, help='a checkpoint kept by another run: the last checkpoint also plays it, from both seats')
   ap.add_argument('--opp_playouts', type=int, default=0,
@@ -150,6 +154,8 @@ def recipe(a):
     extra += ['--reanalyse_gumbel']
     if a.reanalyse_gumbel_scale is not None:
       extra += ['--reanalyse_gumbel_scale', str(a.reanalyse_gumbel_scale)]
+  if a.reanalyse_true_model:      # (given without --reanalyse_rows: train's preflight says so)
+    extra += ['--reanalyse_true_model']
   if a.symmetry:
     extra += ['--symmetry']
   if a.num_simulations is not None:
@@ -252,6 +258,12 @@ def main():
                                  'trained': {'agent_first (win, draw, loss)': after[1], 'agent_second': after[-1]}},
          'match_last_vs_first': dict(vs_first, a='checkpoint %d' % int(state['training_step']), b=opponent, seeds=256,
                                      opening_plies=2)}
+  if a.reanalyse_rows:      # what the actor logged per pass (actors._maybe_reanalyse): how much of the replay the passes rewrote
+    from model_based_rl_amd.logger import read_metrics
+    logged = [read_metrics(f) for f in glob.glob(os.path.join(saves, '**', 'metrics.csv'), recursive=True)]
+    tag = lambda t: [v for m in logged for _, v in m.get('reanalyse/' + t, [])]
+    out['reanalyse'] = {'passes': len(tag('rows')), 'rows': int(sum(tag('rows'))), 'seconds': float(sum(tag('seconds'))),
+                        'mean_policy_l1_last': (tag('mean_policy_l1') or [None])[-1]}
   if a.opp_playouts:
     out['vs_%d_playout_search_512_games' % a.opp_playouts] = {
         name: {'agent_first (win, draw, loss)': r[1], 'agent_second': r[-1]} for name, r in vs_playouts.items()}
